@@ -10,7 +10,7 @@ kept between steps except the HIP runtime itself (the process), the OS page cach
 pool (t1k_capi.hip, T1K_POOL_GB: blocks a finished job frees are handed to the next one instead of going back to the driver, which
 would zero them again at ~35 ms/GB; what is left of a finished job's host memory is released by a detached thread) -- so a step is a
 WARM-process figure.  The cold figure -- a fresh `genotyper` process on the same files, stopwatch from exec to exit -- is measured
-beside it on rank 0 and printed as config.executable_cold_run (--no-executable-check skips it).
+beside it on rank 0 by --full and printed as config.executable_cold_run (--no-executable-check skips it).
 
 Workload at N=1: 10 M synthetic 2x150 bp pairs against the HLA-like rna reference (north_star's "10M synthetic 2x150 bp HLA reads";
 the real hlaidx_rna_seq.fa cannot be downloaded: tools/t1k_synth generates a reference of the same shape, seed 20250614);
@@ -21,10 +21,17 @@ launches the ranks, hands rank 0's ncclUniqueId to the others and provides the b
 
   python bench.py --gpus 1 --steps 3 --warmup 1            (single GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full     (everything below as well)
+  python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
 
-Rank 0 prints ONE JSON line with the contract fields plus "roofline" (dominant kernel: algorithmic bytes / HIP-event time vs the
-8 TB/s HBM peak, and the whole pipeline's algorithmic bytes over the step time) and "cpu_baseline" (the reference genotyper built
-from /root/reference by oracle/Makefile, timed here on a bounded sample of the same workload with -t = all host cores).
+A plain run sets up (inputs generated once per parameter set and cached in --workdir), warms up, times the K steps and prints ONE JSON
+line on rank 0 with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of one timed step) and the
+step's counts and phase times under "config".  --dump-outputs DIR then writes what the last timed step computed as DIR/*.npy (see
+dump_outputs).  --full adds, on the same line: "roofline" (dominant kernel: algorithmic bytes / HIP-event time vs the 8 TB/s HBM peak,
+measured on an untimed one-pipeline step behind the timed ones, and the whole pipeline's algorithmic bytes over the step time),
+the md5 check of every step's files against the reference's (tests/golden/full_size_md5.json; "reference_md5_ok", exit status 3 on a
+difference), "peak_device_gb", the fresh-process runs (value_cold) and "cpu_baseline" (the reference genotyper built by oracle/Makefile
+into oracle/_ref, timed on a bounded sample of the same workload on the host cores).
 """
 import argparse
 import json
@@ -139,6 +146,57 @@ def md5_file(path):
     return h.hexdigest()
 
 
+def _hash52(b):
+    """52-bit content hash of a byte string, exact in a float64"""
+    import hashlib
+    return float(int.from_bytes(hashlib.blake2b(b, digest_size=8).digest(), "little") >> 12)
+
+
+def _line_ends(path, chunk=1 << 28):
+    """offsets of every b'\\n' of a (possibly multi-GB) file, read in chunks"""
+    import numpy as np
+    mm = np.memmap(path, dtype=np.uint8, mode="r") if os.path.getsize(path) else np.zeros(0, dtype=np.uint8)
+    ends = [np.flatnonzero(mm[o:o + chunk] == 10) + o for o in range(0, len(mm), chunk)]
+    return mm, (np.concatenate(ends) if ends else np.zeros(0, dtype=np.int64))
+
+
+def dump_outputs(d, text, counts, out_prefix, barcodes, sample=200000):
+    """--dump-outputs: what a caller of the genotyper stage receives from the last timed step, as float64 arrays in d/<name>.npy.  Names
+    (genes, alleles, read ids) and sequences are 52-bit hashes, so that two builds compare value for value:
+      genotype.npy   one row per gene of *_genotype.tsv: gene, allele count, then (allele, abundance, quality) for the two called alleles
+      allele.npy     one row per line of *_allele.tsv: allele, the number that follows it
+      counts.npy     fragments, assigned fragments, groups, equivalence classes, EM iterations, records of aligned_1 / aligned_2 / aligned_bc
+      aligned_1.npy, aligned_2.npy (aligned_bc.npy)  (record index, id hash, sequence hash) of a fixed seeded sample of at most `sample`
+                     records of each *_aligned_*.fa (all of them when there are fewer)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    h = lambda s: _hash52(s.encode())  # noqa: E731
+    rows = []
+    for line in text.splitlines():
+        f = line.rstrip("\t").split("\t")
+        rows.append([h(f[0]), float(f[1])] + [v for j in range(2, 8, 3) for v in (h(f[j]), float(f[j + 1]), float(f[j + 2]))])
+    np.save(os.path.join(d, "genotype.npy"), np.array(rows, dtype=np.float64).reshape(-1, 8))
+    rows = []
+    for line in open(out_prefix + "_allele.tsv"):
+        f = line.split()
+        if f:
+            rows.append([h(f[0]), float(f[1])])
+    np.save(os.path.join(d, "allele.npy"), np.array(rows, dtype=np.float64).reshape(-1, 2))
+    n_rec = []
+    for suf in ("_aligned_1", "_aligned_2") + (("_aligned_bc",) if barcodes else ()):
+        path = out_prefix + suf + ".fa"
+        mm, ends = _line_ends(path)
+        n = len(ends) // 2  # records of two lines: ">id", sequence
+        n_rec.append(n)
+        pick = np.sort(np.random.default_rng(20250614).choice(n, sample, replace=False)) if n > sample else np.arange(n)
+        starts = np.concatenate([[0], ends[:-1] + 1]) if len(ends) else ends
+        rows = [(float(i), _hash52(mm[starts[2 * i] + 1:ends[2 * i]].tobytes()), _hash52(mm[starts[2 * i + 1]:ends[2 * i + 1]].tobytes())) for i in pick]
+        np.save(os.path.join(d, suf[1:] + ".npy"), np.array(rows, dtype=np.float64).reshape(-1, 3))
+        del mm
+    np.save(os.path.join(d, "counts.npy"), np.array([counts["fragments"], counts["assigned_fragments"], counts["groups"], counts["ecs"],
+                                                     counts["em_iterations"]] + n_rec, dtype=np.float64))
+
+
 def reference_hashes(pairs, genes, scale, barcodes):
     """md5 sums of the files the REFERENCE genotyper wrote for this very input on an MI355X host (tools/full_size_parity_r03.sh; the
     10 M-pair run takes the reference most of an hour at -t 64), committed as tests/golden/full_size_md5.json"""
@@ -230,7 +288,15 @@ def main():
     ap.add_argument("--no-roofline-step", action="store_true", help="skip the untimed one-pipeline step the roofline figures are measured on")
     ap.add_argument("--cold-runs", type=int, default=5, help="fresh `genotyper` processes timed for value_cold (median; all of them listed)")
     ap.add_argument("--barcodes", type=int, default=0, help="BASELINE configs[4]: the reads carry this many 10x-style barcodes (--barcode file; log-uniform usage)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the reference md5 check of every step's files, peak device memory, "
+                         "the untimed one-pipeline roofline step, the fresh `genotyper` processes (value_cold) and the CPU baseline.  Off: set up, warm up, "
+                         "time the steps and print the line, nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; a fixed seeded sample of the aligned-read records)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -276,7 +342,7 @@ def main():
         if dist is not None:
             dist.barrier()
     out_prefix = os.path.join(a.workdir, "out")
-    want = reference_hashes(a.pairs, a.genes, a.scale, a.barcodes) if world == 1 else None
+    want = reference_hashes(a.pairs, a.genes, a.scale, a.barcodes) if world == 1 and a.full else None
     hashes_ok = []
     last = {}
     comm = anchor = None
@@ -352,7 +418,8 @@ def main():
                 pass
             time.sleep(0.05)
     mem_thread = threading.Thread(target=mem_sampler, daemon=True)
-    mem_thread.start()
+    if a.full:
+        mem_thread.start()
 
     for _ in range(a.warmup):
         step()
@@ -376,13 +443,16 @@ def main():
         dist.destroy_process_group()
     st, counts, text = last["stats"], last["counts"], last["text"]
     mem["stop"] = True
-    mem_thread.join()
+    if a.full:
+        mem_thread.join()
+    if a.dump_outputs and rank == 0:  # before the roofline step below, which writes the same files again
+        dump_outputs(a.dump_outputs, text, counts, out_prefix, barcode_file is not None)
     # roofline step (untimed, after the K timed steps): the same job once more with ONE pipeline, so that every family's HIP-event time is
     # the time of kernels that had the device to themselves -- the overlapped streams of the timed steps stretch each other by 2 - 2.5 x and
     # by a different amount from run to run (frac swung 0.021 <-> 0.034 on identical code).  Checked against the reference's
     # hashes like every other step.
     st1 = None
-    if world == 1 and not a.no_roofline_step:
+    if world == 1 and a.full and not a.no_roofline_step:
         keep_env, keep_seg = os.environ.get("T1K_PIPELINES"), dict(seg)
         os.environ["T1K_PIPELINES"] = "1"
         try:
@@ -398,41 +468,7 @@ def main():
     import ctypes
     ctypes.CDLL(None).fflush(None)  # RCCL prints its banner through C stdio: get it out before the JSON line
     if rank == 0:
-        ms = {"k_seed_groups": st["ms_seed"], "chain kernels": st["ms_chain"], "k_extend": st["ms_extend"], "k_select": st["ms_select"],
-              "fullalign kernels": st["ms_fullalign"], "k_pair": st["ms_pair"]}
-        kb = kernel_bytes(st)       # per-kernel re-count (a family's own lower bound; terms repeat across families)
-        kb8 = kernel_bytes_8d(st)   # SURVEY 8d as written, every term once
-        # the dominant kernel (family) is the one with the most MEASURED time (HIP events on the launch streams, summed over the timed
-        # step's ranges); a "launch" of a family is one pass over one range of distinct read-ends (k_pair: one range of fragments).
-        # With several pipelines per GPU those event times are STREAM times: the streams overlap, so their sum exceeds the step's wall
-        # time and `frac` is a lower bound; `frac_alone` prices the same bytes with the family's kernel time in a one-pipeline run.
-        # roofline.frac / achieved are measured on the untimed ONE-pipeline step behind the timed ones (kernels alone on the device: event
-        # time = kernel time); the overlapped-stream figure of the timed steps is kept as frac_overlapped_streams.
-        fam = lambda x: {"k_seed_groups": x["ms_seed"], "chain kernels": x["ms_chain"], "k_extend": x["ms_extend"], "k_select": x["ms_select"],  # noqa: E731
-                         "fullalign kernels": x["ms_fullalign"], "k_pair": x["ms_pair"]}
-        ms1 = fam(st1) if st1 is not None else None
-        dom = max(ms1, key=lambda k: ms1[k]) if ms1 else max(ms, key=lambda k: ms[k])
-        launches = max(1, st["batches"])
-        launches1 = max(1, st1["batches"]) if st1 is not None else launches
-        kb1 = kernel_bytes(st1) if st1 is not None else kb
-        achieved_overlapped = kb[dom] / (ms[dom] * 1e-3) / 1e9 if ms[dom] > 0 else 0.0
-        achieved = (kb1[dom] / (ms1[dom] * 1e-3) / 1e9 if ms1[dom] > 0 else 0.0) if ms1 else achieved_overlapped
         step_s = dt / a.steps
-        alone, alone_other, alone_src = alone_ms_per_step(a.pairs) if world == 1 else (None, None, None)
-        # HBM traffic by the PMC counters: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of THIS command line (tools/profile_r04.sh
-        # writes profiles/r04_traffic.json: per kernel family, bytes per step, FETCH x 2 calibrated + WRITE); not measured in this run
-        traffic = traffic_src = None
-        traffic_all = {}
-        import glob
-        tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))
-        tfiles = [f for f in tfiles if "seed_traffic" not in f]
-        if tfiles:
-            tj = json.load(open(tfiles[-1]))
-            if tj.get("pairs") == a.pairs and world == 1:
-                traffic_all = tj.get("bytes_per_step", {})
-                if dom in traffic_all:
-                    traffic = traffic_all[dom] / launches
-                traffic_src = "%s: %s" % (os.path.relpath(tfiles[-1], ROOT), tj.get("note", ""))
         out = {
             "metric": "genotyped reads/sec (end-to-end genotyper stage, 2x150 bp HLA)",
             "value": total_pairs * a.steps / dt,
@@ -450,7 +486,7 @@ def main():
                                    "END TO END per step: reference FASTA -> index -> FASTQ parse -> GPU -> genotype.tsv + allele.tsv + aligned_{1,2}.fa written"
                                    % (a.pairs, a.genes, a.scale, sum(1 for l in open(ref) if l.startswith(">")),
                                       ", --barcode with %d barcodes (BASELINE configs[4]; + aligned_bc.fa written)" % a.barcodes if a.barcodes else ""),
-                       "process_state": "warm: device-memory pool and HIP runtime kept across steps (see executable_cold_run for a fresh process)",
+                       "process_state": "warm: device-memory pool and HIP runtime kept across steps (--full: executable_cold_run for a fresh process)",
                        "parallelism": ("one sample of %d pairs sharded over %d GPUs by contiguous fragment slices (%d per GPU); RCCL inside libt1k_gpu.so: int32 all-reduce of the coverage arrays, "
                                        "all-to-all of fragment rows to their pattern owners, all-gather of group tables, all-gather of the ranks' contribution slices in every EM update; "
                                        "communicator created once outside the steps" % (total_pairs, world, a.pairs)) if world > 1 else "1 GPU",
@@ -464,38 +500,73 @@ def main():
                        "calls_ms": {k: v / a.steps for k, v in seg.items()},
                        "calls_note": ("job_create_reference = t1k_job_create with t1k_reads_open on a second thread (the executable does the same); load_reads = the join + t1k_job_attach_reads"
                                       if world == 1 and not os.environ.get("T1K_SERIAL_OPEN") else "t1k_job_create, then t1k_job_load_reads")},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "frac_source": ("live: HIP-event time of the family's kernels in an untimed ONE-pipeline step of the same job behind the timed steps (kernels alone on the device)"
-                                         if ms1 else "overlapped streams of the timed steps (no one-pipeline step in this run)"),
-                         "frac_overlapped_streams": achieved_overlapped / HBM_PEAK_GBS, "achieved_overlapped_streams": achieved_overlapped,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel_choice": "the kernel family with the most measured time (HIP events) in the one-pipeline step",
-                         "launches_per_step": launches1, "pipelines_per_gpu": int(os.environ.get("T1K_PIPELINES", "3")), "algorithmic_bytes_per_launch": kb1[dom] / launches1,
-                         "avg_launch_ms": (ms1[dom] / launches1) if ms1 else ms[dom] / launches,
-                         "one_pipeline_step": ({"ms_device_loop": st1["ms_device"], "all_kernels_ms": ms1, "sum_ms": sum(ms1.values()),
-                                                "all_kernels_frac": {k: (kb1[k] / (ms1[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if ms1[k] > 0 else 0.0) for k in ms1}} if ms1 else None),
-                         "all_kernels_ms_per_step": ms,
-                         "all_kernels_algorithmic_GBs": {k: (kb[k] / (ms[k] * 1e-3) / 1e9 if ms[k] > 0 else 0.0) for k in ms},
-                         "all_kernels_frac_overlapped_streams": {k: (kb[k] / (ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if ms[k] > 0 else 0.0) for k in ms},
-                         "all_kernels_traffic_bytes_per_step": traffic_all or None,
-                         "bytes_model": "achieved / frac / all_kernels_*: PER-KERNEL RE-COUNT (each family's own lower bound: the allele window is counted per group in the chain family, "
-                                        "again per candidate in extension and per near-best alignment; not 8d's formula).  pipeline_frac_8d: SURVEY 8d as written, every term once",
-                         "time_model": "frac: family's HIP-event time in the one-pipeline step (no other stream on the device).  *_overlapped_streams: event time on the launch streams of the timed "
-                                       "steps; with %d pipelines the streams overlap (sum over families %.0f ms for a %.0f ms step) and stretch each other by a factor that differs from run to run.  "
-                                       "frac_alone_rocprof: the same family's kernel time in the committed rocprofv3 one-pipeline summary at this size (%s) -- must agree with frac"
-                                       % (int(os.environ.get("T1K_PIPELINES", "3")), sum(ms.values()), step_s * 1e3, alone_src or "none committed for this size"),
-                         "alone_ms_per_step": alone, "alone_source": alone_src,
-                         "frac_alone_rocprof": (kb[dom] / (alone[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if alone and alone.get(dom) else None,
-                         "all_kernels_frac_alone_rocprof": ({k: (kb[k] / (alone[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if alone[k] > 0 else 0.0) for k in ms} if alone else None),
-                         "pipeline_8d_bytes_per_step": sum(kb8.values()), "pipeline_8d_bytes_by_term": kb8,
-                         "pipeline_frac_8d": sum(kb8.values()) / step_s / 1e9 / HBM_PEAK_GBS,
-                         "pipeline_frac_8d_device_loop": sum(kb8.values()) / max(st["ms_device"] * 1e-3, 1e-9) / 1e9 / HBM_PEAK_GBS,
-                         "pipeline_recount_bytes_per_step": sum(kb.values()),
-                         "pipeline_frac_recount": sum(kb.values()) / step_s / 1e9 / HBM_PEAK_GBS,
-                         "pipeline_frac_recount_device_loop": sum(kb.values()) / max(st["ms_device"] * 1e-3, 1e-9) / 1e9 / HBM_PEAK_GBS,
-                         "dp_cell_updates_per_s": st["dp_cells"] / max(st["ms_fullalign"] * 1e-3, 1e-9) if st.get("dp_cells") else None,
-                         "em_ms": st["ms_em"], "job_ms_total": st["ms_total"]},
         }
+        if a.full:  # roofline: the families' HIP-event times, the untimed one-pipeline step, committed profiles
+            ms = {"k_seed_groups": st["ms_seed"], "chain kernels": st["ms_chain"], "k_extend": st["ms_extend"], "k_select": st["ms_select"],
+                  "fullalign kernels": st["ms_fullalign"], "k_pair": st["ms_pair"]}
+            kb = kernel_bytes(st)       # per-kernel re-count (a family's own lower bound; terms repeat across families)
+            kb8 = kernel_bytes_8d(st)   # SURVEY 8d as written, every term once
+            # the dominant kernel (family) is the one with the most MEASURED time (HIP events on the launch streams, summed over the timed
+            # step's ranges); a "launch" of a family is one pass over one range of distinct read-ends (k_pair: one range of fragments).
+            # With several pipelines per GPU those event times are STREAM times: the streams overlap, so their sum exceeds the step's wall
+            # time and `frac` is a lower bound; `frac_alone` prices the same bytes with the family's kernel time in a one-pipeline run.
+            # roofline.frac / achieved are measured on the untimed ONE-pipeline step behind the timed ones (kernels alone on the device: event
+            # time = kernel time); the overlapped-stream figure of the timed steps is kept as frac_overlapped_streams.
+            fam = lambda x: {"k_seed_groups": x["ms_seed"], "chain kernels": x["ms_chain"], "k_extend": x["ms_extend"], "k_select": x["ms_select"],  # noqa: E731
+                             "fullalign kernels": x["ms_fullalign"], "k_pair": x["ms_pair"]}
+            ms1 = fam(st1) if st1 is not None else None
+            dom = max(ms1, key=lambda k: ms1[k]) if ms1 else max(ms, key=lambda k: ms[k])
+            launches = max(1, st["batches"])
+            launches1 = max(1, st1["batches"]) if st1 is not None else launches
+            kb1 = kernel_bytes(st1) if st1 is not None else kb
+            achieved_overlapped = kb[dom] / (ms[dom] * 1e-3) / 1e9 if ms[dom] > 0 else 0.0
+            achieved = (kb1[dom] / (ms1[dom] * 1e-3) / 1e9 if ms1[dom] > 0 else 0.0) if ms1 else achieved_overlapped
+            alone, alone_other, alone_src = alone_ms_per_step(a.pairs) if world == 1 else (None, None, None)
+            # HBM traffic by the PMC counters: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of THIS command line (tools/profile_r04.sh
+            # writes profiles/r04_traffic.json: per kernel family, bytes per step, FETCH x 2 calibrated + WRITE); not measured in this run
+            traffic = traffic_src = None
+            traffic_all = {}
+            import glob
+            tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))
+            tfiles = [f for f in tfiles if "seed_traffic" not in f]
+            if tfiles:
+                tj = json.load(open(tfiles[-1]))
+                if tj.get("pairs") == a.pairs and world == 1:
+                    traffic_all = tj.get("bytes_per_step", {})
+                    if dom in traffic_all:
+                        traffic = traffic_all[dom] / launches
+                    traffic_src = "%s: %s" % (os.path.relpath(tfiles[-1], ROOT), tj.get("note", ""))
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "frac_source": ("live: HIP-event time of the family's kernels in an untimed ONE-pipeline step of the same job behind the timed steps (kernels alone on the device)"
+                                               if ms1 else "overlapped streams of the timed steps (no one-pipeline step in this run)"),
+                               "frac_overlapped_streams": achieved_overlapped / HBM_PEAK_GBS, "achieved_overlapped_streams": achieved_overlapped,
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel_choice": "the kernel family with the most measured time (HIP events) in the one-pipeline step",
+                               "launches_per_step": launches1, "pipelines_per_gpu": int(os.environ.get("T1K_PIPELINES", "3")), "algorithmic_bytes_per_launch": kb1[dom] / launches1,
+                               "avg_launch_ms": (ms1[dom] / launches1) if ms1 else ms[dom] / launches,
+                               "one_pipeline_step": ({"ms_device_loop": st1["ms_device"], "all_kernels_ms": ms1, "sum_ms": sum(ms1.values()),
+                                                      "all_kernels_frac": {k: (kb1[k] / (ms1[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if ms1[k] > 0 else 0.0) for k in ms1}} if ms1 else None),
+                               "all_kernels_ms_per_step": ms,
+                               "all_kernels_algorithmic_GBs": {k: (kb[k] / (ms[k] * 1e-3) / 1e9 if ms[k] > 0 else 0.0) for k in ms},
+                               "all_kernels_frac_overlapped_streams": {k: (kb[k] / (ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if ms[k] > 0 else 0.0) for k in ms},
+                               "all_kernels_traffic_bytes_per_step": traffic_all or None,
+                               "bytes_model": "achieved / frac / all_kernels_*: PER-KERNEL RE-COUNT (each family's own lower bound: the allele window is counted per group in the chain family, "
+                                              "again per candidate in extension and per near-best alignment; not 8d's formula).  pipeline_frac_8d: SURVEY 8d as written, every term once",
+                               "time_model": "frac: family's HIP-event time in the one-pipeline step (no other stream on the device).  *_overlapped_streams: event time on the launch streams of the timed "
+                                             "steps; with %d pipelines the streams overlap (sum over families %.0f ms for a %.0f ms step) and stretch each other by a factor that differs from run to run.  "
+                                             "frac_alone_rocprof: the same family's kernel time in the committed rocprofv3 one-pipeline summary at this size (%s) -- must agree with frac"
+                                             % (int(os.environ.get("T1K_PIPELINES", "3")), sum(ms.values()), step_s * 1e3, alone_src or "none committed for this size"),
+                               "alone_ms_per_step": alone, "alone_source": alone_src,
+                               "frac_alone_rocprof": (kb[dom] / (alone[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if alone and alone.get(dom) else None,
+                               "all_kernels_frac_alone_rocprof": ({k: (kb[k] / (alone[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if alone[k] > 0 else 0.0) for k in ms} if alone else None),
+                               "pipeline_8d_bytes_per_step": sum(kb8.values()), "pipeline_8d_bytes_by_term": kb8,
+                               "pipeline_frac_8d": sum(kb8.values()) / step_s / 1e9 / HBM_PEAK_GBS,
+                               "pipeline_frac_8d_device_loop": sum(kb8.values()) / max(st["ms_device"] * 1e-3, 1e-9) / 1e9 / HBM_PEAK_GBS,
+                               "pipeline_recount_bytes_per_step": sum(kb.values()),
+                               "pipeline_frac_recount": sum(kb.values()) / step_s / 1e9 / HBM_PEAK_GBS,
+                               "pipeline_frac_recount_device_loop": sum(kb.values()) / max(st["ms_device"] * 1e-3, 1e-9) / 1e9 / HBM_PEAK_GBS,
+                               "dp_cell_updates_per_s": st["dp_cells"] / max(st["ms_fullalign"] * 1e-3, 1e-9) if st.get("dp_cells") else None,
+                               "em_ms": st["ms_em"], "job_ms_total": st["ms_total"]}
         if want is not None:
             big = {suf: md5_file(out_prefix + suf) == want[suf] for suf in ("_aligned_1.fa", "_aligned_2.fa", "_aligned_bc.fa") if suf in want}
             out["config"]["reference_output_check"] = {
@@ -505,7 +576,7 @@ def main():
             if not (all(hashes_ok) and all(big.values())):
                 out["config"]["reference_output_check"]["FAILED"] = True
         cold_same = None
-        if world == 1 and not a.no_executable_check:
+        if world == 1 and a.full and not a.no_executable_check:
             exe = os.path.join(ROOT, "t1k_amd", "bin", "genotyper")
             t1k_amd.pool_release()   # this process's cached device memory would otherwise be fresh (to-be-zeroed) VRAM for the other one
             walls = []
@@ -539,10 +610,8 @@ def main():
                     "reference_read_pairs_per_s": full, "reference_threads": rec["reference_run"].get("threads"),
                     "what": "the reference genotyper's own run over this WHOLE workload on a host of this pool (%s); vs_baseline stays null: BASELINE.md "
                             "holds no published number for the metric" % rec["reference_run"].get("log")}
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(ref, pfx, a.workdir, a.pairs)
-        else:
-            out["cpu_baseline"] = None
+        if a.full:
+            out["cpu_baseline"] = cpu_baseline(ref, pfx, a.workdir, a.pairs) if world == 1 and not a.no_cpu_baseline else None
         with open(os.path.join(a.workdir, "last_genotype.tsv"), "w") as f:
             f.write(text)
         if mem["free_min"] is not None:
@@ -553,7 +622,8 @@ def main():
         ok = None
         if want is not None:
             ok = not out["config"]["reference_output_check"].get("FAILED", False) and cold_same is not False
-        out["reference_md5_ok"] = ok
+        if a.full:
+            out["reference_md5_ok"] = ok
         print(json.dumps(out))
         sys.stdout.flush()
         if ok is False:

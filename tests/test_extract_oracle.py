@@ -54,9 +54,9 @@ def test_restatement_keeps_what_the_reference_kept(built, tmp_path, name):
         assert kept_ids(o + "_2.fq") == c.kept
 
 
-def test_low_complexity_rule(built):
+def test_low_complexity_rule(built, tmp_path):
     """IsLowComplexity (FastqExtractor.cpp:89-111) on hand-checked strings."""
-    orc = util.ExtractOracle(util.gunzip_to(util.CYP_RNA, "/tmp/t1k_xo_ref.fa"))
+    orc = util.ExtractOracle(util.gunzip_to(util.CYP_RNA, str(tmp_path / "ref.fa")))
     assert orc.low_complexity("A" * 50 + "CGT" * 16 + "CG")          # one base >= len / 2
     assert not orc.low_complexity("A" * 49 + "CGT" * 17)             # 49 < 50
     assert orc.low_complexity("ACGT" * 20 + "N" * 10)                # N >= len / 10 (90 / 10 = 9)

@@ -7,7 +7,7 @@ PAIRS=${2:-1000000}; STEPS=${3:-3}
 IFS='|' read -ra VARS <<< "${1:-}"
 [ ${#VARS[@]} -eq 0 ] && VARS=("")
 for v in "${VARS[@]}"; do
-  env $v python bench.py --pairs $PAIRS --steps $STEPS --warmup 1 --no-cpu-baseline --no-executable-check 2> /tmp/ab_err.log | tail -1 > /tmp/ab_line.json
+  env $v python bench.py --full --pairs $PAIRS --steps $STEPS --warmup 1 --no-cpu-baseline --no-executable-check 2> /tmp/ab_err.log | tail -1 > /tmp/ab_line.json
   python - "$v" <<'PY'
 import json, sys, hashlib
 try:

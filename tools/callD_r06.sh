@@ -27,7 +27,7 @@ say "== bench step, 10 M pairs, three pipelines"
 python -c "import bench; bench.ensure_inputs('/tmp/t1k_bench', 10000000, 24, 1.0, seed=2)"
 tools/ab_r06.sh "||" 10000000 2 2>&1 | tee -a $L
 say "== configs[4] at size: bench line (1 timed step, reference hashes checked) and the analyzer by phase"
-python bench.py --pairs 10000000 --barcodes 100000 --steps 1 --warmup 1 --no-cpu-baseline --cold-runs 2 > gpurun_out/r06_bench_barcodes_10M_100k.json 2> /tmp/bb.err; echo "bench --barcodes rc $?" | tee -a $L
+python bench.py --full --pairs 10000000 --barcodes 100000 --steps 1 --warmup 1 --no-cpu-baseline --cold-runs 2 > $(dirname $L)/r06_bench_barcodes_10M_100k.json 2> /tmp/bb.err; echo "bench --barcodes rc $?" | tee -a $L
 python - <<'PY' | tee -a $L
 import json
 d = json.loads(open("gpurun_out/r06_bench_barcodes_10M_100k.json").read().strip().splitlines()[-1])

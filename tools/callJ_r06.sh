@@ -10,7 +10,7 @@ tail -16 gpurun_out/r06_pytest_gpu.log | tee -a $L
 say "== smoke()"
 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/r06_smoke.log 2>&1; echo "rc $?" | tee -a $L; tail -3 gpurun_out/r06_smoke.log | cut -c1-300 | tee -a $L
 say "== bench.py (defaults)"
-( time python bench.py ) > gpurun_out/r06_bench.json 2> gpurun_out/r06_bench.err; echo "rc $?" | tee -a $L
+( time python bench.py --full ) > $(dirname $L)/r06_bench.json 2> $(dirname $L)/r06_bench.err; echo "rc $?" | tee -a $L
 tail -c 1500 gpurun_out/r06_bench.json | tee -a $L
 say "== profiles"
 tools/profile_r06.sh > gpurun_out/r06_profile.out 2>&1; tail -40 gpurun_out/r06_profile.out | cut -c1-300 | tee -a $L

@@ -11,6 +11,6 @@ python -c "import bench; bench.ensure_inputs('/tmp/t1k_bench', 10000000, 24, 1.0
 f="$(find /tmp/prof_f1 -name '*kernel_stats.csv' | head -1)"; [ -n "$f" ] && cp "$f" gpurun_out/r05_kernel_stats_10M_1pipeline.csv && cp "$f" profiles/r05_kernel_stats_10M_1pipeline.csv
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_f3 -o bench -- python $R/bench.py --pairs 10000000 --steps 2 --warmup 1 --no-cpu-baseline --no-executable-check > $R/gpurun_out/r05_bench_under_profiler.json 2> /dev/null )
 f="$(find /tmp/prof_f3 -name '*kernel_stats.csv' | head -1)"; [ -n "$f" ] && cp "$f" gpurun_out/r05_kernel_stats.csv
-python bench.py --steps 3 --warmup 1 > gpurun_out/r05_bench.json 2> gpurun_out/r05_bench.err
+python bench.py --full --steps 3 --warmup 1 > $(dirname $LOG)/r05_bench.json 2> $(dirname $LOG)/r05_bench.err
 cut -c1-300 gpurun_out/r05_bench.json >> $LOG
 head -12 gpurun_out/r05_kernel_stats_10M_1pipeline.csv | cut -c1-140 >> $LOG

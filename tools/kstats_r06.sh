@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 for v in $1; do
   LIB=$R/t1k_amd/lib/variants/libt1k_$v.so; [ "$v" = "main" ] && LIB=$R/t1k_amd/lib/libt1k_gpu.so
   rm -rf /tmp/ksl_$v
-  ( cd /tmp && T1K_GPU_LIB=$LIB T1K_PIPELINES=$PIPES rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ksl_$v -o p -- python $R/bench.py --pairs ${PAIRS:-1000000} --steps 1 --warmup 0 --no-cpu-baseline --no-executable-check --no-roofline-step > /tmp/ksl_$v.json 2>/dev/null )
+  ( cd /tmp && T1K_GPU_LIB=$LIB T1K_PIPELINES=$PIPES rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ksl_$v -o p -- python $R/bench.py --full --pairs ${PAIRS:-1000000} --steps 1 --warmup 0 --no-cpu-baseline --no-executable-check --no-roofline-step > /tmp/ksl_$v.json 2>/dev/null )
   f=$(find /tmp/ksl_$v -name "*kernel_stats.csv" | head -1)
   python - "$v" "$f" "$RE" /tmp/ksl_$v.json <<'PY' | tee -a $R/gpurun_out/r06_kstats_lib.log
 import csv, sys, re, json
