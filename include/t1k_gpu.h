@@ -303,6 +303,22 @@ int t1k_em_setup(t1k_ctx *ctx, const uint64_t *rowPtr, const uint32_t *ecIdx, co
                  uint32_t nEc, t1k_allreduce_fn allreduce, void *user);
 int t1k_em_update(t1k_ctx *ctx, const double *x0, double *x1, double *ecReadCount, double *diff);
 
+/* ---- per-barcode allele EM (analyzer --barcodeEM; no counterpart in the reference; estimator: DESIGN §11) ---------------------
+ * One independent EM per barcode, the whole iteration loop in one launch.  Barcode b (of the slice [0, nBarcodes)):
+ *   bcAllelePtr[b] .. [b+1]   its alleles U_b in bcAllele[], strictly ascending global ids < nAlleles (the "local" alleles)
+ *   bcGroupPtr[b] .. [b+1]    its groups, in the order the EM adds them; groupCount[g] = c_g (finite, > 0)
+ *   groupEntryPtr[g] .. [g+1] group g's list S_g in entryLocal[]: strictly ascending indices into U_b, at least one
+ * The offsets need not start at 0: a slice of a larger table is passed as the offsets of its barcodes, the other arrays whole.
+ * Start theta_a = f_a / N_b (f_a = sum over a's groups of c_g / |S_g|); an update is psum_g = sum_{a in S_g} theta_a,
+ * n_a = sum_{g ∋ a} c_g * (theta_a / psum_g), theta'_a = (n_a + alpha * rho[bcAllele]) / (N_b + alpha); it stops after the update
+ * whose sum |theta' - theta| < tol, or after maxIter updates.  nOut (laid out as bcAllele, at the same absolute positions) = the n of
+ * the last update (all 0 where N_b = 0), itersOut[b] = updates run.  rho may be NULL when alpha == 0.  kernelMs (may be NULL): the
+ * kernel's device time.  Barcodes whose state exceeds the per-wave LDS arena -- 4|U_b| + 4G + (G+1) + (|U_b|+1) + 2E four-byte words
+ * against 2048, or against T1K_BARCODE_EM_LDS if that is lower -- run the same arithmetic on global memory. */
+int t1k_barcode_em(t1k_ctx *ctx, uint32_t nBarcodes, const uint64_t *bcAllelePtr, const uint32_t *bcAllele, const uint64_t *bcGroupPtr,
+                   const double *groupCount, const uint64_t *groupEntryPtr, const uint32_t *entryLocal, const double *rho, uint32_t nAlleles,
+                   double alpha, double tol, int32_t maxIter, double *nOut, int32_t *itersOut, double *kernelMs);
+
 /* ---- profiling counters of the last t1k_assign_batch (algorithmic-traffic terms of SURVEY.md 8d) --------------- */
 typedef struct {
   uint64_t read_ends, lookups, postings, hits, groups, candidates, extended, near_best, dp_calls, rows, batches;

@@ -94,6 +94,7 @@ def lib():
     L.t1k_align_count_batch.argtypes = [vp, C.c_char_p, vp, C.c_char_p, vp, vp, C.c_uint32, vp]
     L.t1k_em_setup.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, ALLREDUCE_FN, vp]
     L.t1k_em_update.argtypes = [vp, vp, vp, vp, vp]
+    L.t1k_barcode_em.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int32, vp, vp, C.POINTER(C.c_double)]
     L.t1k_extract_batch.argtypes = [vp, C.c_uint32, vp, vp]
     L.t1k_extractor_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_stats_get.argtypes = [vp, C.POINTER(Stats)]
@@ -351,6 +352,28 @@ class Context:
         diff = C.c_double()
         self._check(lib().t1k_em_update(self.h, _ptr(x0), _ptr(x1), _ptr(n), C.byref(diff)), "t1k_em_update")
         return x1, n, diff.value
+
+    def barcode_em(self, bc_allele_ptr, bc_allele, bc_group_ptr, group_count, group_entry_ptr, entry_local, rho, n_alleles, alpha=0.0, tol=1e-7,
+                   max_iter=1000, raw=False):
+        """per-barcode allele EM (t1k_barcode_em): returns (n laid out as bc_allele, updates per barcode, kernel ms); raw=True returns the
+        status code instead of raising (argument-error tests)"""
+        ap = np.ascontiguousarray(bc_allele_ptr, np.uint64)
+        al = np.ascontiguousarray(bc_allele, np.uint32)
+        gp = np.ascontiguousarray(bc_group_ptr, np.uint64)
+        gc = np.ascontiguousarray(group_count, np.float64)
+        ep = np.ascontiguousarray(group_entry_ptr, np.uint64)
+        el = np.ascontiguousarray(entry_local, np.uint32)
+        rh = None if rho is None else np.ascontiguousarray(rho, np.float64)
+        nb = max(len(ap) - 1, 0)
+        n = np.zeros(len(al), np.float64)
+        iters = np.zeros(nb, np.int32)
+        ms = C.c_double()
+        rc = lib().t1k_barcode_em(self.h, nb, _ptr(ap), _ptr(al), _ptr(gp), _ptr(gc), _ptr(ep), _ptr(el), _ptr(rh), n_alleles, alpha, tol, max_iter,
+                                  _ptr(n), _ptr(iters), C.byref(ms))
+        if raw:
+            return rc
+        self._check(rc, "t1k_barcode_em")
+        return n, iters, ms.value
 
 
 class Readset:

@@ -30,6 +30,56 @@ struct AnalyzerVariants {
   int emIterations = 0;
 };
 
+// every fragment's raw row (the reference's list order): cnt[f] entries at rows[rowAt[f]]
+static int analyzerRows(t1k_job *job, std::vector<uint32_t> &cnt, std::vector<uint64_t> &rowAt, std::vector<t1k_row_entry> &rows) {
+  const uint32_t F = (uint32_t)job->in->nFrag();
+  int rc;
+  cnt.assign(F, 0);
+  rowAt.assign(F + 1, 0);
+  rows.clear();
+  const uint32_t step = 1u << 18;
+  std::vector<t1k_row_entry> part;
+  for (uint32_t f0 = 0; f0 < F; f0 += step) {
+    const uint32_t n = std::min(step, F - f0);
+    uint64_t total = 0;
+    if ((rc = t1k_rowset_rows_download(job->rows, f0, n, cnt.data() + f0, nullptr, 0, &total)) != T1K_OK) return jobFail(job, rc, t1k_rowset_last_error(job->rows));
+    part.resize(total);
+    if (total && (rc = t1k_rowset_rows_download(job->rows, f0, n, cnt.data() + f0, part.data(), total, &total)) != T1K_OK) return jobFail(job, rc, t1k_rowset_last_error(job->rows));
+    rows.insert(rows.end(), part.begin(), part.end());
+  }
+  for (uint32_t f = 0; f < F; ++f) rowAt[f + 1] = rowAt[f] + cnt[f];
+  if (rowAt[F] != rows.size()) return jobFail(job, T1K_ERR_INTERNAL, "analyzer: the row counts do not add up to the rows downloaded");
+  return T1K_OK;
+}
+
+// step (1): the analyzer's pooled EM over the raw rows; leaves the alleles' abundances in job->ref.al[].abundance.  Used by the variant
+// pass and, with --barcodeEM --barcodeEMPrior > 0 under --varMaxGroup 0, for the per-barcode EM's prior alone.
+static int analyzerPooledEM(t1k_job *job, const std::vector<uint32_t> &cnt, const std::vector<uint64_t> &rowAt, const std::vector<t1k_row_entry> &rows, int *iterations) {
+  const RefSet &R = job->ref;
+  const uint32_t F = (uint32_t)job->in->nFrag();
+  Genotyper &gt = job->gt;
+  const int maxAssign = job->prm.dev.max_assign_cnt;
+  std::vector<t1k_row_entry> tmp;
+  for (uint32_t f = 0; f < F; ++f) {
+    const uint32_t k = cnt[f];
+    if (!k || (maxAssign > 0 && (int)k > maxAssign)) continue;  // Genotyper.hpp:783-784
+    bool sep = false;                                            // IsFragmentSpanSeparator (796-800): an N of the allele inside the fragment's window
+    for (uint32_t j = 0; j < k && !sep; ++j) {
+      const t1k_row_entry &e = rows[rowAt[f] + j];
+      const std::string &sq = R.seqs[e.allele_idx];
+      for (int p = std::max(e.start, 0); p <= e.end && p < (int)sq.size(); ++p)
+        if (sq[p] == 'N') { sep = true; break; }
+    }
+    if (sep) continue;
+    tmp.assign(rows.begin() + rowAt[f], rows.begin() + rowAt[f] + k);
+    gt.coalesce(tmp.data(), k, f);
+  }
+  gt.finalize(std::vector<int32_t>(R.al.size(), 0));  // (missingCoverage is not read before selection, which the analyzer does not run)
+  *iterations = 0;
+  if (gt.nGroups() && (*iterations = gt.quantify(job->ctx, nullptr, job->err)) < 0) return T1K_ERR_DEVICE;
+  return T1K_OK;
+}
+
 static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants &V) {
   const double tv0 = nowMs();
   double msAssign = 0, msDetails = 0, msAlign = 0;
@@ -39,46 +89,12 @@ static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants 
   const uint32_t F = (uint32_t)in.nFrag();
   const bool paired = in.paired;
   int rc;
-  // every fragment's raw row (the reference's list order)
-  std::vector<uint32_t> cnt(F);
-  std::vector<uint64_t> rowAt(F + 1, 0);
+  std::vector<uint32_t> cnt;
+  std::vector<uint64_t> rowAt;
   std::vector<t1k_row_entry> rows;
-  {
-    const uint32_t step = 1u << 18;
-    std::vector<t1k_row_entry> part;
-    for (uint32_t f0 = 0; f0 < F; f0 += step) {
-      const uint32_t n = std::min(step, F - f0);
-      uint64_t total = 0;
-      if ((rc = t1k_rowset_rows_download(job->rows, f0, n, cnt.data() + f0, nullptr, 0, &total)) != T1K_OK) return jobFail(job, rc, t1k_rowset_last_error(job->rows));
-      part.resize(total);
-      if (total && (rc = t1k_rowset_rows_download(job->rows, f0, n, cnt.data() + f0, part.data(), total, &total)) != T1K_OK) return jobFail(job, rc, t1k_rowset_last_error(job->rows));
-      rows.insert(rows.end(), part.begin(), part.end());
-    }
-    for (uint32_t f = 0; f < F; ++f) rowAt[f + 1] = rowAt[f] + cnt[f];
-    if (rowAt[F] != rows.size()) return jobFail(job, T1K_ERR_INTERNAL, "analyzer: the row counts do not add up to the rows downloaded");
-  }
+  if ((rc = analyzerRows(job, cnt, rowAt, rows)) != T1K_OK) return rc;
   // (1) the analyzer's EM
-  {
-    Genotyper &gt = job->gt;
-    const int maxAssign = job->prm.dev.max_assign_cnt;
-    std::vector<t1k_row_entry> tmp;
-    for (uint32_t f = 0; f < F; ++f) {
-      const uint32_t k = cnt[f];
-      if (!k || (maxAssign > 0 && (int)k > maxAssign)) continue;  // Genotyper.hpp:783-784
-      bool sep = false;                                            // IsFragmentSpanSeparator (796-800): an N of the allele inside the fragment's window
-      for (uint32_t j = 0; j < k && !sep; ++j) {
-        const t1k_row_entry &e = rows[rowAt[f] + j];
-        const std::string &sq = R.seqs[e.allele_idx];
-        for (int p = std::max(e.start, 0); p <= e.end && p < (int)sq.size(); ++p)
-          if (sq[p] == 'N') { sep = true; break; }
-      }
-      if (sep) continue;
-      tmp.assign(rows.begin() + rowAt[f], rows.begin() + rowAt[f] + k);
-      gt.coalesce(tmp.data(), k, f);
-    }
-    gt.finalize(std::vector<int32_t>(R.al.size(), 0));  // (missingCoverage is not read before selection, which the analyzer does not run)
-    if (gt.nGroups() && (V.emIterations = gt.quantify(job->ctx, nullptr, job->err)) < 0) return T1K_ERR_DEVICE;
-  }
+  if ((rc = analyzerPooledEM(job, cnt, rowAt, rows, &V.emIterations)) != T1K_OK) return rc;
   std::vector<double> abundance(R.al.size());
   for (size_t a = 0; a < R.al.size(); ++a) abundance[a] = R.al[a].abundance;
   const double tv1 = nowMs();
@@ -321,6 +337,131 @@ static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants 
   return T1K_OK;
 }
 
+// --barcodeEM: the lists BarcodeSummary counts, grouped per barcode, through t1k_barcode_em.  The summary loop hands every
+// counted fragment's kept list over in file order (bc = its row of the per-barcode table); finish() groups them per barcode (identical
+// sorted lists, first appearance first, host threads over barcodes), runs the EM and writes <prefix>_barcode_em.tsv.
+struct BarcodeEM {
+  std::vector<uint32_t> fragRow;      // counted fragment -> its barcode id (the summary loop), then its row of the table (run)
+  std::vector<uint64_t> fragAt{0};    // counted fragment -> its sorted list in `lists`
+  std::vector<uint32_t> lists;
+  std::vector<uint32_t> scratch;
+
+  void add(int bc, const uint32_t *alleles, uint32_t k) {
+    scratch.assign(alleles, alleles + k);
+    std::sort(scratch.begin(), scratch.end());
+    scratch.erase(std::unique(scratch.begin(), scratch.end()), scratch.end());
+    if (scratch.empty()) return;  // nothing kept: not counted
+    fragRow.push_back((uint32_t)bc);
+    lists.insert(lists.end(), scratch.begin(), scratch.end());
+    fragAt.push_back(lists.size());
+  }
+
+  // rows x A expected counts (row-major), through the device
+  int run(t1k_job *job, uint32_t nRows, double alpha, std::vector<double> &out) {
+    const double t0 = nowMs();
+    const size_t A = job->ref.al.size();
+    const size_t nF = fragRow.size();
+    // counted fragments per row, in file order (a stable counting sort)
+    std::vector<uint64_t> rowStart(nRows + 1, 0);
+    for (uint32_t r : fragRow) ++rowStart[r + 1];
+    for (uint32_t r = 0; r < nRows; ++r) rowStart[r + 1] += rowStart[r];
+    std::vector<uint32_t> byRow(nF);
+    {
+      std::vector<uint64_t> fill(rowStart.begin(), rowStart.end() - 1);
+      for (size_t i = 0; i < nF; ++i) byRow[fill[fragRow[i]]++] = (uint32_t)i;
+    }
+    // per row: groups (distinct lists, first appearance first), their counts, U_b and the lists as indices into it
+    struct Row { std::vector<uint32_t> U, entryPtr{0}, entry; std::vector<double> count; };
+    std::vector<Row> R(nRows);
+    parallelRanges(nRows, hostThreads(job), [&](int, size_t lo, size_t hi) {
+      std::vector<uint32_t> slots, firstOf;  // open addressing over the row's groups; firstOf[g] = the fragment that opened group g
+      for (size_t r = lo; r < hi; ++r) {
+        Row &w = R[r];
+        const uint64_t b = rowStart[r], e = rowStart[r + 1];
+        size_t cap = 16;
+        slots.assign(cap, ~0u);
+        firstOf.clear();
+        auto listOf = [&](uint32_t i) { return std::make_pair(lists.data() + fragAt[i], (size_t)(fragAt[i + 1] - fragAt[i])); };
+        auto hashOf = [&](uint32_t i) {
+          auto l = listOf(i);
+          uint64_t h = 0x9E3779B97F4A7C15ull ^ l.second;
+          for (size_t j = 0; j < l.second; ++j) { h = (h ^ l.first[j]) * 0xD6E8FEB86659FD93ull; h ^= h >> 29; }
+          return h;
+        };
+        for (uint64_t q = b; q < e; ++q) {
+          const uint32_t i = byRow[q];
+          const auto l = listOf(i);
+          size_t s = (size_t)hashOf(i) & (cap - 1);
+          for (;; s = (s + 1) & (cap - 1)) {
+            if (slots[s] == ~0u) {
+              slots[s] = (uint32_t)firstOf.size();
+              firstOf.push_back(i);
+              w.count.push_back(1.0);
+              break;
+            }
+            const auto m = listOf(firstOf[slots[s]]);
+            if (m.second == l.second && std::equal(l.first, l.first + l.second, m.first)) { w.count[slots[s]] += 1.0; break; }
+          }
+          if (firstOf.size() * 2 > cap) {  // grow
+            cap *= 2;
+            slots.assign(cap, ~0u);
+            for (uint32_t g = 0; g < firstOf.size(); ++g) {
+              size_t t = (size_t)hashOf(firstOf[g]) & (cap - 1);
+              while (slots[t] != ~0u) t = (t + 1) & (cap - 1);
+              slots[t] = g;
+            }
+          }
+        }
+        for (uint32_t i : firstOf) { auto l = listOf(i); w.U.insert(w.U.end(), l.first, l.first + l.second); }
+        std::sort(w.U.begin(), w.U.end());
+        w.U.erase(std::unique(w.U.begin(), w.U.end()), w.U.end());
+        for (uint32_t i : firstOf) {
+          auto l = listOf(i);
+          for (size_t j = 0; j < l.second; ++j) w.entry.push_back((uint32_t)(std::lower_bound(w.U.begin(), w.U.end(), l.first[j]) - w.U.begin()));
+          w.entryPtr.push_back((uint32_t)w.entry.size());
+        }
+      }
+    });
+    std::vector<uint64_t> bcAllelePtr(nRows + 1, 0), bcGroupPtr(nRows + 1, 0), groupEntryPtr(1, 0);
+    std::vector<uint32_t> bcAllele, entryLocal;
+    std::vector<double> groupCount;
+    for (uint32_t r = 0; r < nRows; ++r) {
+      const Row &w = R[r];
+      bcAllele.insert(bcAllele.end(), w.U.begin(), w.U.end());
+      bcAllelePtr[r + 1] = bcAllele.size();
+      for (size_t g = 0; g < w.count.size(); ++g) groupEntryPtr.push_back(entryLocal.size() + w.entryPtr[g + 1]);
+      entryLocal.insert(entryLocal.end(), w.entry.begin(), w.entry.end());
+      groupCount.insert(groupCount.end(), w.count.begin(), w.count.end());
+      bcGroupPtr[r + 1] = groupCount.size();
+    }
+    R.clear();
+    // the prior: the pooled EM's allele shares (uniform if it has nothing)
+    std::vector<double> rho(A);
+    double tot = 0;
+    for (size_t a = 0; a < A; ++a) tot += job->ref.al[a].abundance;
+    for (size_t a = 0; a < A; ++a) rho[a] = tot > 0 ? job->ref.al[a].abundance / tot : 1.0 / (double)A;
+    const double t1 = nowMs();
+    std::vector<double> n(bcAllele.size());
+    std::vector<int32_t> iters(nRows);
+    double kernelMs = 0;
+    int rc = t1k_barcode_em(job->ctx, nRows, bcAllelePtr.data(), bcAllele.data(), bcGroupPtr.data(), groupCount.data(), groupEntryPtr.data(), entryLocal.data(),
+                            rho.data(), (uint32_t)A, alpha, 1e-7, 1000, n.data(), iters.data(), &kernelMs);
+    if (rc != T1K_OK) return jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(job->ctx));
+    const double t2 = nowMs();
+    out.assign((size_t)nRows * A, 0.0);
+    for (uint32_t r = 0; r < nRows; ++r)
+      for (uint64_t i = bcAllelePtr[r]; i < bcAllelePtr[r + 1]; ++i) out[(size_t)r * A + bcAllele[i]] = n[i];
+    if (getenv("T1K_DEBUG_PHASES")) {
+      int32_t mx = 0;
+      double sum = 0;
+      for (int32_t v : iters) { mx = std::max(mx, v); sum += v; }
+      fprintf(stderr, "[t1k analyzer] barcode EM: groups built in %.1f ms, t1k_barcode_em %.1f ms (kernel %.1f ms); %u barcodes, %zu groups, %zu entries; iterations max %d mean %.1f\n",
+              t1 - t0, t2 - t1, kernelMs, nRows, groupCount.size(), entryLocal.size(), mx, nRows ? sum / nRows : 0.0);
+    }
+    return T1K_OK;
+  }
+};
+
 static const char *kAnalyzerUsage =
     "./analyzer [OPTIONS]:   (MI355X build of the T1K post-analysis stage: re-assignment, novel variants, per-barcode summary)\n"
     "Required:\n"
@@ -334,6 +475,8 @@ static const char *kAnalyzerUsage =
     "\t-n INT: maximal number of alleles per read (default: 2000)\n"
     "\t-s FLOAT: minimum alignment similarity (default: 0.8)\n"
     "\t--barcode STRING: barcode file\n"
+    "\t--barcodeEM: also write prefix_barcode_em.tsv, the alleles' expected fragment counts of an EM run per barcode (needs --barcode; or $T1K_BARCODE_EM=1 with --barcode)\n"
+    "\t--barcodeEMPrior FLOAT: weight of the pooled allele abundances as a prior of the per-barcode EM (default: 0)\n"
     "\t--relaxIntronAlign: allow one more mismatch in intronic alignment\n"
     "\t--alleleDigitUnits INT, --alleleDelimiter CHR: as in genotyper\n"
     "\t--varMaxGroup INT: the maximum variant group size to call novel variant. -1 for no limitation, 0 for no variant calling (default: 8)\n"
@@ -343,13 +486,16 @@ int t1k_analyzer_main(int argc, char **argv) {
   if (argc <= 1) { fprintf(stderr, "%s", kAnalyzerUsage); return 0; }  // Analyzer.cpp:241-245
   static struct option longOpts[] = {{"barcode", required_argument, 0, 10000}, {"relaxIntronAlign", no_argument, 0, 10004}, {"alleleDigitUnits", required_argument, 0, 10005},
                                      {"alleleDelimiter", required_argument, 0, 10006}, {"varMaxGroup", required_argument, 0, 10007}, {"device", required_argument, 0, 10010},
-                                     {0, 0, 0, 0}};
+                                     {"barcodeEM", no_argument, 0, 10011}, {"barcodeEMPrior", required_argument, 0, 10012}, {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
   std::string refFile, alleleFile, prefix = "t1k", barcode;
   std::vector<const char *> f1, f2, single;
   int varMaxGroup = 8;  // Analyzer.cpp:251
+  bool barcodeEM = false;
+  double emPrior = 0;
+  const char *emPriorText = nullptr;
   optind = 1;
   int c, idx = 0;
   while ((c = getopt_long(argc, argv, "f:a:u:1:2:o:t:n:s:", longOpts, &idx)) != -1) {
@@ -369,11 +515,21 @@ int t1k_analyzer_main(int argc, char **argv) {
       case 10006: p.allele_delimiter = optarg[0]; break;
       case 10007: varMaxGroup = atoi(optarg); break;
       case 10010: p.device = atoi(optarg); break;
+      case 10011: barcodeEM = true; break;
+      case 10012: emPriorText = optarg; break;
       default: fprintf(stderr, "%s", kAnalyzerUsage); return EXIT_FAILURE;
     }
   }
   if (refFile.empty()) { fprintf(stderr, "Need to use -f to specify the reference sequences.\n"); return EXIT_FAILURE; }
   if (alleleFile.empty()) { fprintf(stderr, "Need to use -a to specify selected allele ids.\n"); return EXIT_FAILURE; }
+  if (barcodeEM && barcode.empty()) { fprintf(stderr, "--barcodeEM needs --barcode.\n"); return EXIT_FAILURE; }
+  if (const char *e = getenv("T1K_BARCODE_EM"))  // (for run-t1k, which passes the analyzer only the flags it knows)
+    if (!strcmp(e, "1") && !barcode.empty()) barcodeEM = true;
+  if (emPriorText) {
+    char *end = nullptr;
+    emPrior = strtod(emPriorText, &end);
+    if (end == emPriorText || *end || !(emPrior >= 0) || !std::isfinite(emPrior)) { fprintf(stderr, "--barcodeEMPrior needs a number >= 0.\n"); return EXIT_FAILURE; }
+  }
   if (p.dev.max_assign_cnt == 0) p.dev.max_assign_cnt = -1;
   std::set<std::string> selected;
   {
@@ -395,6 +551,12 @@ int t1k_analyzer_main(int argc, char **argv) {
       if (!fb) { fprintf(stderr, "analyzer: cannot write %s_barcode_expr.tsv\n", prefix.c_str()); return EXIT_FAILURE; }
       fprintf(fb, "#barcode\n");
       fclose(fb);
+    }
+    if (barcodeEM) {
+      FILE *fe = fopen((prefix + "_barcode_em.tsv").c_str(), "w");
+      if (!fe) { fprintf(stderr, "analyzer: cannot write %s_barcode_em.tsv\n", prefix.c_str()); return EXIT_FAILURE; }
+      fprintf(fe, "#barcode\n");
+      fclose(fe);
     }
     logLine("Post analysis finishes.");
     return 0;
@@ -426,6 +588,15 @@ int t1k_analyzer_main(int argc, char **argv) {
     rc = analyzerCallVariants(job, varMaxGroup, V);
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
     logLine("Finish allele quantification in %d EM iterations.", V.emIterations);
+  } else if (barcodeEM && emPrior > 0) {
+    // the per-barcode EM's prior is the pooled EM's abundances: step (1) of the variant pass on its own (its outputs are not written)
+    std::vector<uint32_t> cnt;
+    std::vector<uint64_t> rowAt;
+    std::vector<t1k_row_entry> rows;
+    int it = 0;
+    rc = analyzerRows(job, cnt, rowAt, rows);
+    if (rc == T1K_OK) rc = analyzerPooledEM(job, cnt, rowAt, rows, &it);
+    if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
   }
   {
     FILE *fp = fopen((prefix + "_allele.vcf").c_str(), "w");  // VariantCaller::OutputAlleleVCF (1202-1227)
@@ -451,6 +622,8 @@ int t1k_analyzer_main(int argc, char **argv) {
     std::vector<uint32_t> cnt;
     std::vector<t1k_row_entry> rows;
     std::vector<uint8_t> keepFlag;
+    std::unique_ptr<BarcodeEM> em(barcodeEM ? new BarcodeEM : nullptr);
+    std::vector<uint32_t> emList;
     for (uint32_t f0 = 0; f0 < F; f0 += step) {
       const uint32_t n = std::min(step, F - f0);
       cnt.resize(n);
@@ -476,12 +649,22 @@ int t1k_analyzer_main(int argc, char **argv) {
           if (fr.n == k) V.vc->adjust(fr, V.ops.data(), keepFlag.data());
           uint32_t kept = 0;
           for (uint32_t j = 0; j < k; ++j) kept += keepFlag[j];
+          if (em) {
+            emList.clear();
+            for (uint32_t j = 0; j < k; ++j) if (keepFlag[j]) emList.push_back((uint32_t)rows[q + j].allele_idx);
+            em->add(bcOf[f], emList.data(), (uint32_t)emList.size());
+          }
           for (uint32_t j = 0; j < k; ++j, ++q) {
             if (!keepFlag[j]) continue;
             slot.first[rows[q].allele_idx] += 1.0 / kept;
             if (kept == 1) ++slot.second[rows[q].allele_idx];
           }
           continue;
+        }
+        if (em) {
+          emList.clear();
+          for (uint32_t j = 0; j < k; ++j) emList.push_back((uint32_t)rows[q + j].allele_idx);
+          em->add(bcOf[f0 + i], emList.data(), k);
         }
         for (uint32_t j = 0; j < k; ++j, ++q) {
           slot.first[rows[q].allele_idx] += 1.0 / k;
@@ -502,6 +685,27 @@ int t1k_analyzer_main(int argc, char **argv) {
       fprintf(fp, "\n");
     }
     fclose(fp);
+    if (em) {
+      // the table's rows, in its order: every counted fragment's barcode id becomes its row
+      std::unordered_map<int, uint32_t> rowOf;
+      for (auto &kv : table) rowOf.emplace(kv.first, (uint32_t)rowOf.size());
+      for (uint32_t &r : em->fragRow) r = rowOf.at((int)r);
+      std::vector<double> est;
+      if (em->run(job, (uint32_t)table.size(), emPrior, est) != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
+      FILE *fe = fopen((prefix + "_barcode_em.tsv").c_str(), "w");
+      if (!fe) { fprintf(stderr, "analyzer: cannot write %s_barcode_em.tsv\n", prefix.c_str()); t1k_job_destroy(job); return EXIT_FAILURE; }
+      fprintf(fe, "#barcode");
+      for (size_t a = 0; a < A; ++a) fprintf(fe, "\t%s", job->ref.al[a].name.c_str());
+      fprintf(fe, "\n");
+      size_t r = 0;
+      for (auto &kv : table) {
+        fprintf(fe, "%s", names[kv.first].c_str());
+        for (size_t a = 0; a < A; ++a) fprintf(fe, "\t%lf", est[r * A + a]);
+        fprintf(fe, "\n");
+        ++r;
+      }
+      fclose(fe);
+    }
   }
   logLine("Post analysis finishes.");
   t1k_job_destroy(job);
