@@ -1164,10 +1164,6 @@ void t1k_launch_extend(t1k_ctx *ctx, const ExtendArgs &a) {
   if (!a.nCand) return;
   hipLaunchKernelGGL(k_extend, dim3((unsigned)((a.nCand + WG - 1) / WG)), dim3(WG), 0, ctx->stream, a);
 }
-void t1k_launch_extend_retry(t1k_ctx *ctx, const ExtendArgs &a, const uint32_t *list, uint32_t n) {
-  if (!n) return;
-  hipLaunchKernelGGL(k_extend_retry, dim3((n + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, list, n, (const unsigned long long *)nullptr);
-}
 void t1k_launch_extend_retry_dev(t1k_ctx *ctx, const ExtendArgs &a, const uint32_t *list, int arena, uint64_t est) {
   const unsigned long long *nDev = (const unsigned long long *)ctx->bCounters.p + T1K_TOTAL_BASE + arena;
   hipLaunchKernelGGL(k_extend_retry, dim3((unsigned)std::max<uint64_t>(1, (est + WG - 1) / WG)), dim3(WG), 0, ctx->stream, a, list, 0u, nDev);

@@ -311,7 +311,7 @@ void t1k_ctx_destroy(t1k_ctx *ctx) {
   for (auto &b : ctx->refBufs) freeBuf(b);
   T1kDevBuf *all[] = {&ctx->bReadAscii, &ctx->bReadOffs, &ctx->bReadBases, &ctx->bReadN, &ctx->bReadLen, &ctx->bReadWeight, &ctx->bWgHits, &ctx->bWgGroups,
                       &ctx->bWgStage, &ctx->bWgBig, &ctx->bWgCache, &ctx->bLists, &ctx->bCand, &ctx->bExt, &ctx->bCandStart, &ctx->bCandCount, &ctx->bListPtr, &ctx->bListCount,
-                      &ctx->bOvlWork, &ctx->bDedupScratch, &ctx->bDedupBases, &ctx->bDedupN, &ctx->bDedupLen, &ctx->bDedupWeight, &ctx->bOvlStart, &ctx->bOvlCount, &ctx->bCounters, &ctx->bSlowQueue, &ctx->bSlowScratch, &ctx->bSortScratch, &ctx->bEqTrace, &ctx->bSortTmp, &ctx->bSlowKeys, &ctx->bJobSort, &ctx->bEnd1, &ctx->bEnd2,
+                      &ctx->bOvlWork, &ctx->bDedupScratch, &ctx->bDedupBases, &ctx->bDedupN, &ctx->bDedupLen, &ctx->bDedupWeight, &ctx->bOvlStart, &ctx->bOvlCount, &ctx->bCounters, &ctx->bSlowQueue, &ctx->bSlowScratch, &ctx->bSortScratch, &ctx->bEqTrace, &ctx->bSortTmp, &ctx->bJobSort, &ctx->bEnd1, &ctx->bEnd2,
                       &ctx->bHasN, &ctx->bRows, &ctx->bRowStart, &ctx->bRowCount, &ctx->bFragAssigned, &ctx->bPairScratch, &ctx->bPairOverflow, &ctx->bPairBig, &ctx->bExtractHuge, &ctx->bEmRowPtr, &ctx->bEmEc,
                       &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bExtract};
   for (auto *b : all) freeBuf(*b);
@@ -332,7 +332,7 @@ uint64_t t1k_ctx_mem_report(t1k_ctx *ctx, const char *tag, int print) {
 #define B(x) {#x, &ctx->x}
   const struct { const char *name; T1kDevBuf *b; } all[] = {B(bReadAscii), B(bReadOffs), B(bReadBases), B(bReadN), B(bReadLen), B(bReadWeight), B(bWgHits), B(bWgGroups),
     B(bWgStage), B(bWgBig), B(bWgCache), B(bLists), B(bCand), B(bExt), B(bCandStart), B(bCandCount), B(bListPtr), B(bListCount), B(bOvlWork), B(bDedupScratch), B(bDedupBases), B(bDedupN),
-    B(bDedupLen), B(bDedupWeight), B(bOvlStart), B(bOvlCount), B(bCounters), B(bSlowQueue), B(bSlowScratch), B(bSortScratch), B(bEqTrace), B(bSortTmp), B(bSlowKeys), B(bJobSort), B(bEnd1),
+    B(bDedupLen), B(bDedupWeight), B(bOvlStart), B(bOvlCount), B(bCounters), B(bSlowQueue), B(bSlowScratch), B(bSortScratch), B(bEqTrace), B(bSortTmp), B(bJobSort), B(bEnd1),
     B(bEnd2), B(bHasN), B(bRows), B(bRowStart), B(bRowCount), B(bFragAssigned), B(bPairScratch), B(bPairOverflow), B(bPairBig), B(bExtractHuge), B(bEmRowPtr), B(bEmEc), B(bEmCount),
     B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract)};
 #undef B
@@ -648,7 +648,6 @@ extern "C++" int t1k_fetch_counters(t1k_ctx *ctx, unsigned long long *h) {
   memcpy(h, raw.data(), 64 * 8);
   h[6] = 0;  // group records: sum of the arena's segment cursors
   for (int s = 0; s < T1K_NSTRIPE; ++s) h[6] += raw[T1K_ARENA_BASE + ((size_t)T1K_AR_GROUPS * T1K_NSTRIPE + s) * T1K_STRIPE_WORDS];
-  for (int s = 56; s < 64; ++s) h[6] += raw[s];  // ... + the groups the fused seeding kernel ended without a record
   static const int slot[8] = {7, 11, 12, 14, 10, 3, 4, 5};
   for (int s = 0; s < T1K_STAT_STRIPES; ++s)
     for (int k = 0; k < 8; ++k) h[slot[k]] += raw[64 + s * 8 + k];
@@ -917,7 +916,7 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   const uint32_t listSegCap = (uint32_t)std::max<uint64_t>(ctx->wList / T1K_NSTRIPE, 1024u), rareSegCap = (uint32_t)std::max<uint64_t>(ctx->wRare / T1K_NSTRIPE, 1024u);
   const uint32_t jobSegCap = jobCap / T1K_NSTRIPE, genCandSegCap = genCandCap / T1K_NSTRIPE;
   const size_t listWords = (size_t)listSegCap * T1K_NSTRIPE, rareWords = (size_t)rareSegCap * T1K_NSTRIPE;
-  if ((rc = t1k_ensure(ctx, ctx->bLists, ((size_t)jobCap * 2 + listWords * 6 + rareWords * 6 + (size_t)genCandCap * 6 + genHitCap + (size_t)genJobCap * 2) * 4 + 64))) return rc;
+  if ((rc = t1k_ensure(ctx, ctx->bLists, ((size_t)jobCap * 2 + listWords * 5 + rareWords * 6 + (size_t)genCandCap * 6 + genHitCap + (size_t)genJobCap * 2) * 4 + 64))) return rc;
   if ((rc = t1k_ensure(ctx, ctx->bCand, (size_t)ctx->wCand * sizeof(T1kCand)))) return rc;
   if ((rc = t1k_ensure(ctx, ctx->bExt, (size_t)ctx->wCand * sizeof(T1kExt)))) return rc;
   // this range's lists go to the end of the overlap store: the current chunk if the working overlap capacity still fits, else the next one
@@ -972,7 +971,7 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   a.memo = (unsigned long long *)ctx->bWgCache.p;
   a.jobList = (uint32_t *)ctx->bLists.p; a.jobCap = jobCap;
   a.jobStr = a.jobList + jobCap;
-  a.retryList = a.jobStr + jobCap; a.finishList = a.retryList + listWords; a.slowList = a.finishList + listWords;
+  a.retryList = a.jobStr + jobCap; a.slowList = a.retryList + listWords;
   a.retryStr = a.slowList + listWords; a.finishStr = a.retryStr + listWords; a.slowStr = a.finishStr + listWords;
   a.generalList = a.slowStr + listWords; a.bigList = a.generalList + rareWords; a.waveList = a.bigList + rareWords;
   a.generalStr = a.waveList + rareWords; a.bigStr = a.generalStr + rareWords; a.waveStr = a.bigStr + rareWords;
@@ -982,7 +981,6 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   a.groupSegCap = groupSegCap; a.jobSegCap = jobSegCap; a.listSegCap = listSegCap; a.rareSegCap = rareSegCap; a.genCandSegCap = genCandSegCap;
   a.bigScratch = (uint32_t *)ctx->bWgBig.p;
   { static const int ns = getenv("T1K_NO_SIMPLE_CHAIN") ? 0 : 1; a.nearSimple = ns; }
-  { static const int fz = getenv("T1K_FUSE_SEED") ? atoi(getenv("T1K_FUSE_SEED")) : 0; a.fuse = fz; }  // measured in round 5: 20 % MORE kernel time than the two launches; opt-in
   { static const int ep = getenv("T1K_NO_EARLY_PRUNE") ? 0 : getenv("T1K_WALK_IN_CLOSED") ? atoi(getenv("T1K_WALK_IN_CLOSED")) + 1 : 2; a.earlyPrune = ep; }  // 0: none, 1: the closed-form pass prunes with the gap-count bound, 2: ... and runs the gap walk's first pass
   a.cand = (T1kCand *)ctx->bCand.p; a.candCap = ctx->wCand;
   a.candStart = (uint32_t *)ctx->bCandStart.p; a.candCount = (uint32_t *)ctx->bCandCount.p;
@@ -997,18 +995,9 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   // the extension alignments go through the memo like the chain's (the chain's work lists are dead by now: reuse their memory)
   e.memo = a.memo; e.jobStr = a.jobStr; e.jobSegCap = a.jobSegCap; e.retryStr = a.retryStr; e.retrySegCap = a.listSegCap;
   t1k_launch_extend(ctx, e);
-  const bool hostDriven = t1k_chain_host_driven();
-  if (hostDriven) {
-    if ((rc = fetchCounters(ctx, hc))) return rc;
-    const T1kArenaCounts ej = t1k_arena_counts(ctx, T1K_AR_EXTJOBS, e.jobSegCap), er = t1k_arena_counts(ctx, T1K_AR_EXTRETRY, e.retrySegCap);
-    if (er.overflow || ej.overflow) return capacityError(ctx, 256);
-    t1k_arena_compact(ctx, T1K_AR_EXTJOBS, e.jobStr, e.jobSegCap, a.jobList, ej.maxSeg);
-    t1k_arena_compact(ctx, T1K_AR_EXTRETRY, e.retryStr, e.retrySegCap, a.retryList, er.maxSeg);
-    t1k_launch_dp_dense(ctx, a, a.jobList, (uint32_t)ej.total);
-    t1k_launch_extend_retry(ctx, e, a.retryList, (uint32_t)er.total);
-  } else if (ctx->nCand) {
-    // the same launches without the counter fetch: item counts read on the device, grids from the previous range's counts; a full stripe
-    // raises the group-capacity flag on the device and shows in the fetch behind the selection (nothing of the range is committed before it)
+  if (ctx->nCand) {
+    // no counter fetch between the extension and its alignments: item counts read on the device, grids from the previous range's counts; a full
+    // stripe raises the group-capacity flag on the device and shows in the fetch behind the selection (nothing of the range is committed before it)
     const uint64_t jobCapAll = (uint64_t)e.jobSegCap * T1K_NSTRIPE, retryCapAll = (uint64_t)e.retrySegCap * T1K_NSTRIPE;
     const uint64_t eJ = t1k_arena_estimate(ctx, T1K_AR_EXTJOBS, jobCapAll, n), eR = t1k_arena_estimate(ctx, T1K_AR_EXTRETRY, retryCapAll, n);
     t1k_arena_compact_dev(ctx, T1K_AR_EXTJOBS, e.jobStr, e.jobSegCap, a.jobList, eJ);
@@ -1017,7 +1006,6 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
     t1k_launch_extend_retry_dev(ctx, e, a.retryList, T1K_AR_EXTRETRY, eR);
   }
   T1K_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-  if (hostDriven) T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));
   double t2 = nowMs();
   SelectArgs s{};
   s.reads = rd; s.cand = a.cand; s.ext = e.ext; s.candStart = a.candStart; s.candCount = a.candCount;
@@ -1031,10 +1019,8 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   if ((rc = fetchCounters(ctx, hc))) return rc;
   double t3 = nowMs();
   if (hc[2]) return capacityError(ctx, hc[2]);
-  if (!hostDriven) {
-    t1k_arena_estimate_set(ctx, T1K_AR_EXTJOBS, t1k_arena_counts(ctx, T1K_AR_EXTJOBS, e.jobSegCap).total, n);
-    t1k_arena_estimate_set(ctx, T1K_AR_EXTRETRY, t1k_arena_counts(ctx, T1K_AR_EXTRETRY, e.retrySegCap).total, n);
-  }
+  t1k_arena_estimate_set(ctx, T1K_AR_EXTJOBS, t1k_arena_counts(ctx, T1K_AR_EXTJOBS, e.jobSegCap).total, n);
+  t1k_arena_estimate_set(ctx, T1K_AR_EXTRETRY, t1k_arena_counts(ctx, T1K_AR_EXTRETRY, e.retrySegCap).total, n);
   ctx->nOvl = hc[1];
   // Near-best full alignments (SeqSet.hpp:2188-2285).  Without --relaxIntronAlign they only feed the per-base coverage, so a context
   // whose coverage is deferred (t1k_ctx_set_coverage_mode) skips them here altogether: k_select has written the relaxed counts, and

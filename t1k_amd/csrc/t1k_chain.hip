@@ -1,32 +1,29 @@
-// t1k_amd/csrc/t1k_chain.hip -- seeding, hit grouping and chaining of SeqSet::AssignRead on gfx950, as a sequence of flat,
-// batch-wide kernels (all integer, HBM/LDS-bound; no MFMA):
+// t1k_amd/csrc/t1k_chain.hip -- chaining of SeqSet::AssignRead on gfx950: the group records that seeding leaves (t1k_seed.hip; record layout in
+// t1k_chain_rec.h) -> candidate overlaps per read-end, as a sequence of flat, batch-wide kernels (all integer, HBM/LDS-bound; no MFMA):
 //
-//   k_seed_groups   one 256-thread workgroup per read-end: rolling 11-mers + direct-address look-up with the >=100 skip
-//                   rule (GetHitsFromRead, SeqSet.hpp:1071-1229); per (strand, 1024-allele chunk) the hits are folded into
-//                   per-allele LDS accumulators (reference diagonal, bitmask of hit offsets, stray counts), i.e. grouped by
-//                   (strand, allele) as SortHits 1558-1590 does, and one record per group leaves the chip; groups with fewer
-//                   than 3 hits are never written (refMinHitRequired, 1253/1314)
-//   k_chain_fast    one lane per (read-end, strand, allele) group over the whole batch: single-diagonal fast path
-//                   (GetOverlapsFromHits 1232-1556 + seed-chain match count 1697-1848); alignments that need a DP are
-//                   registered in the read-end's memo table and the group is parked
-//   k_dp_dense      one lane per distinct registered alignment (banded forward sweep, band in registers)
-//   k_chain_retry   parked groups finish from the memo
-//   k_chain_general groups with hits on several nearby diagonals: the reference's diagonal-run / LIS logic verbatim
-//   k_collect       one workgroup per read-end: strand vote (1619-1648) and copy-out of the winning strand's candidates
+//   k_chain_fast<*, 0>  one lane per (read-end, strand, allele) group over the whole batch: single-diagonal closed form
+//                       (GetOverlapsFromHits 1232-1556 + seed-chain match count 1697-1848); groups that need the gap walk go to the
+//                       slow list, groups with hits on several diagonals to the general list
+//   k_chain_fast<*, 1>  the gap walk over the slow list: alignments that need a DP are registered in the read-end's memo
+//   k_dp_dense          one lane per distinct registered alignment (banded forward sweep, band in registers)
+//   k_chain_fast<*, 2>  groups whose memo slot was taken run again behind k_dp_dense (retry list)
+//   k_near_hits, k_gather_general, k_chain_general, k_chain_wave, k_general_finish, k_chain_big
+//                       groups with hits on several nearby diagonals: their hit lists, then the reference's diagonal-run / LIS logic verbatim
+//   k_collect           one workgroup per read-end: strand vote (1619-1648), match counts of candidates that waited for the memo, copy-out
+//                       of the winning strand's candidates
+//   k_arena_compact, k_csort_*   striped work list -> dense list; counting sort of a dense list by a small key
 #include <algorithm>
 #include "t1k_dev.h"
 #include "t1k_launch.h"
 #include "t1k_memo.h"
 #include "t1k_group.h"
+#include "t1k_chain_rec.h"
 
-#define WG 256
 #define GROUP_FAST_MAXLEN 320
 #define GENERAL_CAP 128             // hits per group handled by k_chain_general in private memory; larger groups: k_chain_big
 #define BIG_CAP 16384
 #define GA_BIG_MAX 2048
 #define GA_SCRATCH_INTS (6 * (GA_BIG_MAX + 4))
-
-enum { ERR_HITCAP = 1, ERR_STAGECAP = 2, ERR_CANDCAP = 4, ERR_BIGGROUP = 8, ERR_OVLCAP = 16, ERR_SORTCAP = 32, ERR_SLOWCAP = 64, ERR_ROWCAP = 128, ERR_GROUPCAP = 256, ERR_MEMO = 512 };
 
 // ------------------------------------------------------------------------------------------------------------------
 // group -> candidate overlaps
@@ -93,8 +90,10 @@ __device__ __forceinline__ void shlOr(uint64_t *C, int sft) {
 
 // return value: 5 = needs the gap walk (CLOSED only), 1 = finished (out holds 0 or 1 candidate), 2 = run again after the dense DP phase, 3 = candidate pushed with a
 // partial matchCnt, refs[] name the memo slots whose match counts are still to be added (DEFER only)
-#define GROUP_MAX_REFS 4   // two 32-bit words of 16-bit memo slots in a group record
-template <int NW, bool DEFER, bool CLOSED, bool ONDEMAND = false>
+#ifndef GROUP_MAX_REFS     // (t1k_chain_rec.h defines it; tests/test_closed_form_cpu.py compiles this stretch of the file on its own, without the header)
+#define GROUP_MAX_REFS 4
+#endif
+template <int NW, bool DEFER, bool CLOSED>
 __device__ inline int groupFastPath(const uint32_t *Mw, int diag, const ReadCtx &c, bool hasN, int k, int hitLenRequired, double simThreshold, CandOut &out,
                                     unsigned int *dpCounter, int strandBit, const GapSink &sink, uint32_t *refs, int *nRefs, int earlyPrune = 1) {
   constexpr int MW = (NW + 1) / 2;  // 64-bit words of the read-offset bitmask
@@ -141,34 +140,6 @@ __device__ inline int groupFastPath(const uint32_t *Mw, int diag, const ReadCtx 
     const int rw = first >> 5;
     const int nWin = (span + 31) >> 5;
     constexpr int NP = (NW + 2) / 2;  // 16-byte pieces covering NW + 1 words
-    if (ONDEMAND) {
-      // (the seeding kernel's call: the read's words are in LDS -- c.rb / c.rn point there -- and are fetched where they are used; only the
-      // allele's words come as one burst; the allele's N-mask words, rarely needed, are loaded where they are used as well.  Half the
-      // registers of the form below, the same words)
-      uint64_t G[2 * NP];
-#pragma unroll
-      for (int j = 0; j < NP; ++j) {
-        t1k_u64x2 g = {0ull, 0ull};
-        if (2 * j <= nWin) g = *(const t1k_u64x2 *)(c.gb + gw + 2 * j);
-        G[2 * j] = g.x; G[2 * j + 1] = g.y;
-      }
-#pragma unroll
-      for (int i = 0; i < NW; ++i) {
-        mmw[i] = 0;
-        if (i < nWin) {
-          const uint64_t r0 = c.rb[rw + i], r1 = c.rb[rw + i + 1], n0 = c.rn[rw + i], n1 = c.rn[rw + i + 1];
-          const uint64_t g = (G[i] >> gsh) | ((G[i + 1] << 1) << (63 - gsh)), r = (r0 >> rsh) | ((r1 << 1) << (63 - rsh));
-          uint64_t nn = (n0 >> rsh) | ((n1 << 1) << (63 - rsh));
-          if (hasN) { const uint64_t q0 = c.gn[gw + i], q1 = c.gn[gw + i + 1]; nn |= (q0 >> gsh) | ((q1 << 1) << (63 - gsh)); }
-          const uint64_t xo = g ^ r;
-          uint64_t mm = (xo | (xo >> 1)) & T1K_EVEN & ~nn;
-          const int rem = span - 32 * i;
-          if (rem < 32) mm &= t1k_lowmask(rem);
-          mmw[i] = mm;
-          mmT += __popcll(mm);
-        }
-      }
-    } else {
     uint64_t G[2 * NP], R[2 * NP], GN[2 * NP], RN[2 * NP];
     // (the allele's words from the transposed copy where there is one: lanes = consecutive alleles, the same word of each, one row -- see T1kRefDev::basesT)
     const uint64_t *gt = c.gT ? c.gT + (gw - (c.goff >> 5)) * 64 : nullptr;
@@ -202,7 +173,6 @@ __device__ inline int groupFastPath(const uint32_t *Mw, int diag, const ReadCtx 
         mmw[i] = mm;
         mmT += __popcll(mm);
       }
-    }
     }
   }
   int matchCnt;
@@ -487,742 +457,12 @@ __device__ __forceinline__ VoteKey voteKey(int matchCnt0, int rs, int re, uint32
 }
 
 
-// ------------------------------------------------------------------------------------------------------------------
-// K1: seeds -> one record per (strand, allele) group, built in LDS in a single pass over the posting lists
-//
-// Alleles are processed in chunks of CHUNK_A; each allele of the chunk owns an accumulator in LDS:
-//   diag  reference diagonal = diagonal of the first hit that arrived (any choice is valid, see groupFastPath)
-//   M     bitmask of the read offsets whose k-mer hits the allele on that diagonal
-//   meta  number of hits on other diagonals (low 16 bits) and how many of those lie within `radius` (high 16 bits)
-// Posting lists are sorted by allele, so the chunk's slice of every used list is found by binary search from a cursor.
-// A group record leaves the chip once, coalesced; no hit list is ever written.
-// ------------------------------------------------------------------------------------------------------------------
-#define CHUNK_A T1K_SEED_CHUNK
-// record word 2 before chaining: reference diagonal (22 bits, biased; alleles are shorter than 2^20 bases) and the counts of hits off
-// it: FAR = beyond `radius` diagonals (bits 22..24, saturating at 7) and NEAR = within `radius` (bits 25..29, saturating at 31) -- the
-// chain asks "near > 0" and "far > 2" (several diagonals: the general path), k_near_hits asks for "far == 0" and the exact near count
-// (31 = unknown).  Bits 30 and 31 stay clear: after chaining the word holds the state, whose REC_DONE is bit 31.
-__device__ __forceinline__ uint32_t packDiagMeta(int diag, uint32_t meta) {
-  const uint32_t strays = meta & 0xFFFFu, nearCnt = meta >> 16;  // (strays counts every hit off the reference diagonal, near ones included)
-  return (uint32_t)(diag + (1 << 21)) | (min(strays - nearCnt, 7u) << 22) | (min(nearCnt, 31u) << 25);
-}
-__device__ __forceinline__ int recDiag(uint32_t w2) { return (int)(w2 & 0x3FFFFFu) - (1 << 21); }
-__device__ __forceinline__ uint32_t recFar(uint32_t w2) { return (w2 >> 22) & 7u; }
-__device__ __forceinline__ uint32_t recNear(uint32_t w2) { return (w2 >> 25) & 31u; }
-__device__ __forceinline__ bool recIsGeneral(uint32_t w2) { return recNear(w2) > 0 || recFar(w2) > 2; }
-#define REC_NEAR_DONE 0x4E454152u  // record word 5 of a multi-diagonal group whose hit list k_near_hits wrote (k_gather_general leaves it alone)
-enum { REC_DONE = 0x80000000u };  // word 3 after chaining: REC_DONE | number of candidates (general groups: candidates in the side arena)
-
 __device__ __forceinline__ ReadCtx makeCtx(const ChainArgs &P, uint32_t re, int pass, uint32_t allele) {
   const int S = P.reads.S;
   ReadCtx c{P.reads.bases + ((uint64_t)re * 2 + pass) * S, P.reads.nmask + ((uint64_t)re * 2 + pass) * S, (int)P.reads.len[re], P.ref.bases, P.ref.nmask,
             (int64_t)P.ref.alleleOff[allele], (int)P.ref.alleleLen[allele], P.ref.anyN != 0};
   if (P.ref.basesT) c.gT = P.ref.basesT + (uint64_t)P.ref.blockT[allele >> 6] + (allele & 63u);
   return c;
-}
-
-#define DIAG_EMPTY 0x7FFFFFFF
-
-// the closed-form pass on one accumulator (fused seeding): `a` = the accumulator row in LDS (diag, meta, M[NW]); returns groupFastPath's verdict, 6 instead of
-// 1 when the group ended WITH a candidate, which is left in a[2..4]
-template <int NW>
-__device__ __forceinline__ uint32_t closedFormGroup(uint32_t *a, const uint64_t *rb, const uint64_t *rn, const uint64_t *gb, const uint64_t *gn, int64_t goff, bool anyN, bool hasN, int k,
-                                                    int hitLenRequired, double sim, int pass, int earlyPrune) {
-  uint32_t Mw[NW];
-#pragma unroll
-  for (int w = 0; w < NW; ++w) Mw[w] = a[2 + w];
-  const ReadCtx c{rb, rn, 0, gb, gn, goff, 0, anyN};
-  uint32_t cbuf[3];
-  CandOut out{cbuf, 0};
-  const GapSink sink{nullptr, nullptr, nullptr, 0u, 0u, T1K_AR_JOBS};  // (the closed-form pass registers nothing)
-  uint32_t refs[2] = {0, 0};
-  int nRefs = 0;
-  const uint32_t kind = (uint32_t)groupFastPath<NW, true, true, true>(Mw, (int)a[0], c, hasN, k, hitLenRequired, sim, out, nullptr, pass, sink, refs, &nRefs, earlyPrune);
-  if (kind == 1u && out.n) { a[2] = cbuf[0]; a[3] = cbuf[1]; a[4] = cbuf[2]; return 6u; }
-  return kind;
-}
-
-#ifndef T1K_SEED_WAVES
-#define T1K_SEED_WAVES 7   // round 6: the kernel's 20.7 KB of LDS admit SEVEN workgroups a compute unit; held to 64 VGPRs for eight it spilled 41 registers for an occupancy it never had (72 VGPRs: 24 spilled; 3.11 -> 2.87 ms per range alone, profiles/r06_callE_seed_waves_suite.log)
-#endif
-#ifndef T1K_SEED_PACK_Q
-#define T1K_SEED_PACK_Q 0
-#endif
-#ifndef T1K_FUSE_WAVES
-#define T1K_FUSE_WAVES 5
-#endif
-// FUSE: the closed-form pass of the chain (groupFastPath<NW, true, true>, what k_chain_fast<NW, 0> does per record) runs here, on the
-// accumulators while they are in LDS: a group that ends there leaves as a finished record (state + candidate) or -- no candidate -- not
-// at all, a group for the gap walk / the multi-diagonal path leaves as before AND is put on its work list.  No launch reads the
-// records back just to classify them.
-template <int NW, bool FUSE>
-__device__ __forceinline__ void seedGroupsBody(const ChainArgs &P) {
-  constexpr int AW = NW == 5 ? 7 : 13;  // u32 per accumulator: diag, meta, M[NW]; odd stride = no LDS bank conflicts
-  extern __shared__ uint32_t lds[];
-  const int k = P.k;
-  const int maxK = (int)P.maxKFast;                 // >= k-mers of a read-end this kernel seeds, both strands (LDS layout; the used-list table's stride is P.maxK)
-  uint32_t *acc = lds;                              // [CHUNK_A][AW] per-allele accumulators of the current chunk
-  // look-up phase only (overlaid on the accumulators, which are re-initialised afterwards):
-  uint32_t *ukCode = acc;                           // [maxK]  code | valid << 31
-  uint32_t *ukStart = ukCode + maxK;                // [maxK]
-  uint32_t *ukLen = ukStart + maxK;                 // [maxK]
-  uint32_t *ukDir = ukLen + maxK;                   // [maxK]  chunk-directory row of the list
-  uint16_t *usedQ = (uint16_t *)(ukDir + maxK);     // [maxK]  k-mers whose lists are used, + strand first
-  // chunk loop:
-  uint32_t *sLo = acc + CHUNK_A * AW;               // [maxK]  slice of the current chunk
-  uint32_t *pre = sLo + maxK;                       // [maxK + 1] exclusive prefix of the slice lengths
-  uint32_t *lstStart = pre + maxK + 1;              // [maxK]  posting-list start / length of the used lists (both strands)
-  uint32_t *lstLen = lstStart + maxK;               // [maxK]
-  uint32_t *lstDir = lstLen + maxK;                 // [maxK]
-  // read offset of the used lists: T1K_SEED_PACK_Q (round 6) keeps it in the upper nine bits of lstLen -- a list's length is only asked for "is it
-  // empty" (lists with a directory row) or is below T1K_DIR_MINLEN (the others), so 23 bits hold all that is read -- and the 560 bytes of its own array
-  // go: 20 756 -> 20 196 bytes of LDS per workgroup for 2 x 150 bp reads, under the 20 480 at which EIGHT workgroups fit a compute unit's 160 KB
-  // (the register allocation has been held to 64 VGPRs for eight wavefronts per SIMD all along; the LDS admitted seven)
-#if T1K_SEED_PACK_Q
-  uint16_t *qOf = (uint16_t *)(lstDir + maxK);      // (no array: the pointer only marks where the bitmaps may start)
-#define LST_LEN(x) ((x) & 0x7FFFFFu)
-#else
-  uint16_t *qOf = (uint16_t *)(lstDir + maxK);      // [maxK]  read offset of the used lists
-#define LST_LEN(x) (x)
-#endif
-  // two bitmaps over all alleles (chunk selection, before the chunk loop of each strand): over the accumulators when they fit there
-  // (references of up to 57 344 / 106 496 sequences), else behind the list arrays (the launcher sizes the dynamic LDS for it)
-  const uint32_t A = P.ref.nAlleles;
-  const uint32_t nChunks = P.ref.kDirStride - 1;    // (the launcher refuses more than 256 chunks: sHot)
-  uint32_t *bitmaps = 2 * ((A + 31) >> 5) <= (uint32_t)(CHUNK_A * AW) ? acc : (uint32_t *)(qOf + (T1K_SEED_PACK_Q ? 0 : ((maxK + 1) & ~1)));
-  __shared__ uint32_t warpSums[4];
-  __shared__ uint32_t sHot[8];                      // bit c: chunk c can hold an allele with three hits (this strand)
-  __shared__ uint32_t sUsed[2], sGroupBase, sFallback, sPost;
-  __shared__ int sWaveMax[4];
-  const int tid = threadIdx.x;
-  const uint32_t kmask = (1u << (2 * k)) - 1;
-  const uint32_t stride = P.recStride;
-  for (uint32_t i = tid; i < CHUNK_A * AW; i += WG) acc[i] = (i % AW) == 0 ? (uint32_t)DIAG_EMPTY : 0u;
-  __syncthreads();
-#ifdef T1K_SEED_PROFILE
-  uint64_t tp_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = __builtin_amdgcn_s_memtime();
-#endif
-  __shared__ uint32_t sUMask[2 * T1K_USED_MASK_WORDS];  // read offsets whose lists are used, per strand
-  constexpr int RDW = 14;                             // >= S + 2 (S <= 11: reads of at most T1K_MAX_READ_LEN bases)
-  __shared__ uint64_t sRd[2][2][FUSE ? RDW : 1];      // [strand][bases | N mask][word] of the read-end (FUSE)
-  __shared__ unsigned long long sStat[3];             // lookups, postings, hits: thread 0 tallies them in LDS (three 64-bit counters in registers would be held by every lane), flushed once per workgroup
-  if (tid == 0) { sStat[0] = 0; sStat[1] = 0; sStat[2] = 0; }
-  unsigned int fastLocal = 0, groupsLocal = 0, recsLocal = 0;  // (FUSE)
-  for (uint32_t re = blockIdx.x; re < P.reads.nReadEnds; re += gridDim.x) {
-    const int len = P.reads.len[re];
-    const int S = P.reads.S;
-    const uint64_t *rbase = P.reads.bases + (uint64_t)re * 2 * S;
-    const uint64_t *rnm = P.reads.nmask + (uint64_t)re * 2 * S;
-    for (int c = tid; c < P.maxChunks; c += WG) P.chunkCount[(uint64_t)re * P.maxChunks + c] = 0;
-    if (tid == 0) { P.usedCount[2 * re] = 0; P.usedCount[2 * re + 1] = 0; }
-    // (a read-end beyond the hit masks' span is seeded by k_seed_long, launched behind this kernel)
-    // (... and one whose lists an earlier window of the job holds is not seeded at all: t1k_xwin_link)
-    if (len < k || len > T1K_MAX_READ_LEN || (P.reads.skip && P.reads.skip[re])) { __syncthreads(); continue; }  // GetOverlapsFromRead returns -1 (SeqSet.hpp:1598-1599)
-    const int nk = len - k + 1;
-    if (tid < 2 * T1K_USED_MASK_WORDS) sUMask[tid] = 0;  // (read by the previous read-end before its chunk loop's barriers)
-    if (FUSE && tid >= 64 && tid < 64 + 2 * 2 * RDW) {  // the read's packed words for the closed-form pass (used behind the barriers of the look-up phase)
-      const int x = tid - 64, strand = x / (2 * RDW), kind = (x / RDW) & 1, w = x % RDW;
-      sRd[strand][kind][w] = w < S ? (kind ? rnm : rbase)[strand * S + w] : 0ull;
-    }
-    for (int q = tid; q < 2 * nk; q += WG) {
-      int pass = q / nk, p = q - pass * nk;
-      const uint64_t *b = rbase + pass * S, *nm = rnm + pass * S;
-      uint32_t code = (uint32_t)t1k_get32(b, p) & kmask;
-      bool valid = ((uint32_t)t1k_get32(nm, p) & kmask) == 0;
-      uint32_t st = 0, ln = 0, dr = T1K_NO_DIR;
-      if (valid) { st = P.ref.kStart[code]; ln = P.ref.kStart[code + 1] - st; dr = P.ref.kDirIdx[code]; }
-      ukCode[q] = code | (valid ? 0x80000000u : 0);
-      ukStart[q] = st; ukLen[q] = ln; ukDir[q] = dr;
-    }
-    __syncthreads();
-
-#ifdef T1K_SEED_PROFILE
-    { const uint64_t tn_ = __builtin_amdgcn_s_memtime(); tp_[0] += tn_ - tl_; tl_ = tn_; }
-#endif
-    // The look-up rule (SeqSet.hpp:1098-1153, 1165-1226) is a sequential state machine (prevKmerCode, skipCnt).
-    // Parallel form: if no two k-mers within k/2 + 1 consecutive positions of a strand are equal, `code != prev` holds at every
-    // position (prev is the code of one of the previous k/2 + 1 positions), every position is a look-up, and only skipCnt is
-    // left: in a maximal run of "big" positions (list >= 100, not the first / last k-mer) exactly every (k/2 + 1)-th one is
-    // used, any other position resets the count.  Reads with such short repeats take the sequential replay below.
-    const int W1 = k / 2 + 1;
-    if (tid == 0) { sFallback = 0; sUsed[0] = 0; sUsed[1] = 0; sPost = 0; }
-    __syncthreads();
-    int qv[3], lastNonBig[3];
-    uint32_t szv[3];
-    bool bigv[3];
-    {
-      int localMax = -1;
-#pragma unroll
-      for (int x = 0; x < 3; ++x) {
-        const int q = 3 * tid + x;
-        qv[x] = q; szv[x] = 0; bigv[x] = false; lastNonBig[x] = -1;
-        if (q < 2 * nk) {
-          const int pass = q >= nk ? 1 : 0, p = q - pass * nk;
-          const uint32_t code = ukCode[q] & 0x7FFFFFFFu;
-          for (int d = 1; d <= W1 && d <= p; ++d)
-            if ((ukCode[q - d] & 0x7FFFFFFFu) == code) sFallback = 1;
-          szv[x] = ukLen[q];
-          bigv[x] = szv[x] >= 100 && p != 0 && p != nk - 1;
-          if (!bigv[x]) localMax = q;
-        }
-        lastNonBig[x] = localMax;  // within this lane so far; the lanes before are merged in below
-      }
-      // inclusive max-scan of localMax over the lanes (three consecutive positions per lane, lanes in position order)
-      int incl = localMax;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl = max(incl, y); }
-      if ((tid & 63) == 63) sWaveMax[tid >> 6] = incl;
-      __syncthreads();
-      int before = __shfl_up(incl, 1, 64);
-      if ((tid & 63) == 0) before = -1;
-      for (int w = 0; w < (tid >> 6); ++w) before = max(before, sWaveMax[w]);
-#pragma unroll
-      for (int x = 0; x < 3; ++x) lastNonBig[x] = max(lastNonBig[x], before);
-    }
-    const bool fallback = sFallback != 0;  // (sWaveMax's barrier also published sFallback)
-    if (!fallback) {
-      uint32_t mine = 0, minePlus = 0, minePost = 0;
-      bool usedv[3];
-#pragma unroll
-      for (int x = 0; x < 3; ++x) {
-        usedv[x] = false;
-        if (qv[x] < 2 * nk && szv[x]) usedv[x] = !bigv[x] || ((qv[x] - lastNonBig[x]) % W1 == 0);
-        if (usedv[x]) { ++mine; minePost += szv[x]; if (qv[x] < nk) ++minePlus; }
-      }
-      uint32_t tot;
-      uint32_t slot = t1k_block_scan_exclusive(mine, warpSums, &tot);
-#pragma unroll
-      for (int x = 0; x < 3; ++x)
-        if (usedv[x]) usedQ[slot++] = (uint16_t)qv[x];
-      for (int o = 32; o > 0; o >>= 1) { minePlus += __shfl_xor(minePlus, o, 64); minePost += __shfl_xor(minePost, o, 64); }
-      if ((tid & 63) == 0) { atomicAdd(&sUsed[0], minePlus); atomicAdd(&sPost, minePost); }
-      __syncthreads();
-      if (tid == 0) {
-        sUsed[1] = tot - sUsed[0];
-        sStat[0] += 2 * nk; sStat[1] += sPost;
-        P.usedCount[2 * re] = sUsed[0]; P.usedCount[2 * re + 1] = sUsed[1];
-      }
-    }
-    // sequential replay (reads with short repeats): the first wavefront runs it as uniform (scalar) code: each lane holds one
-    // k-mer's code and list length, the loop reads them with v_readlane.
-    if (fallback && tid < 64) {
-      uint32_t prev = 0;  // prevKmerCode starts at code 0 and is carried from the + strand into the - strand
-      uint32_t nUsed = 0;
-      uint32_t lookups = 0, postings = 0;
-      for (int pass = 0; pass < 2; ++pass) {
-        int skipCnt = 0;
-        const uint32_t begin = nUsed;
-        for (int seg = 0; seg < nk; seg += 64) {
-          const int pl = seg + tid;
-          const uint32_t vc = pl < nk ? (ukCode[pass * nk + pl] & 0x7FFFFFFFu) : 0u;
-          const uint32_t vl = pl < nk ? ukLen[pass * nk + pl] : 0u;
-          const int cnt = min(64, nk - seg);
-          for (int j = 0; j < cnt; ++j) {
-            const uint32_t code = (uint32_t)__builtin_amdgcn_readlane((int)vc, j);
-            const uint32_t size = (uint32_t)__builtin_amdgcn_readlane((int)vl, j);
-            const int p = seg + j;
-            if (p == 0 || code != prev) {
-              ++lookups;
-              if (size >= 100 && p != 0 && p != nk - 1 && skipCnt < k / 2) { ++skipCnt; continue; }
-              skipCnt = 0;
-              if (size) {
-                if (tid == 0) usedQ[nUsed] = (uint16_t)(pass * nk + p);
-                ++nUsed;
-                postings += size;
-              }
-            }
-            prev = code;
-          }
-        }
-        if (tid == 0) sUsed[pass] = nUsed - begin;
-      }
-      if (tid == 0) {
-        sStat[0] += lookups; sStat[1] += postings;
-        P.usedCount[2 * re] = sUsed[0]; P.usedCount[2 * re + 1] = sUsed[1];
-      }
-    }
-    __syncthreads();
-    const uint32_t nUsedPlus = sUsed[0], nUsedMinus = sUsed[1];
-#ifdef T1K_SEED_PROFILE
-    { const uint64_t tn_ = __builtin_amdgcn_s_memtime(); tp_[1] += tn_ - tl_; tl_ = tn_; }
-#endif
-
-    // the used lists are kept for k_chain_general, which re-derives the hits of the few multi-diagonal groups; which read offsets have
-    // their lists used goes out per strand as bit masks as well (k_near_hits rebuilds the hits on near diagonals from them; sUMask was
-    // cleared at the top of this read-end, before the barriers of the look-up phase)
-    {
-      uint32_t *uo = P.usedOut + (uint64_t)re * P.maxK * 4;
-      for (uint32_t u = tid; u < nUsedPlus + nUsedMinus; u += WG) {
-        int q = usedQ[u];
-        int pass = u < nUsedPlus ? 0 : 1;
-        uo[4 * u] = (uint32_t)(q - pass * nk); uo[4 * u + 1] = ukStart[q]; uo[4 * u + 2] = ukLen[q]; uo[4 * u + 3] = ukDir[q];
-        atomicOr(&sUMask[pass * T1K_USED_MASK_WORDS + ((q - pass * nk) >> 5)], 1u << ((q - pass * nk) & 31));
-      }
-    }
-    // what the chunk loop needs of the used lists moves out of the overlay, then the accumulators under it are made clean again
-    __syncthreads();
-    if (tid < 2 * T1K_USED_MASK_WORDS) P.usedMask[(uint64_t)re * 2 * T1K_USED_MASK_WORDS + tid] = sUMask[tid];
-    for (uint32_t u = tid; u < nUsedPlus + nUsedMinus; u += WG) {
-      const int q = usedQ[u];
-      const int pass = u < nUsedPlus ? 0 : 1;
-      const uint32_t st = ukStart[q], ln = ukLen[q];
-#if T1K_SEED_PACK_Q
-      lstStart[u] = st; lstLen[u] = min(ln, 0x7FFFFFu) | ((uint32_t)(q - pass * nk) << 23); lstDir[u] = ukDir[q];
-#else
-      lstStart[u] = st; lstLen[u] = ln; lstDir[u] = ukDir[q]; qOf[u] = (uint16_t)(q - pass * nk);
-#endif
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < (uint32_t)((9 * maxK + 1) / 2); i += WG) acc[i] = (i % AW) == 0 ? (uint32_t)DIAG_EMPTY : 0u;
-    __syncthreads();
-
-#ifdef T1K_SEED_PROFILE
-    { const uint64_t tn_ = __builtin_amdgcn_s_memtime(); tp_[2] += tn_ - tl_; tl_ = tn_; }
-#endif
-    int chunk = 0;
-    for (int sp = 0; sp < 2; ++sp) {  // '-' strand first (SortHits 1577-1583)
-      const int pass = sp == 0 ? 1 : 0;
-      const uint32_t uBegin = pass == 0 ? 0 : nUsedPlus;
-      const uint32_t uCount = pass == 0 ? nUsedPlus : nUsedMinus;
-      if (uCount == 0) continue;
-      // thread t owns the lists t and t + WG (uCount <= 2 * WG: reads are at most 320 bp)
-      const bool has0 = (uint32_t)tid < uCount, has1 = (uint32_t)tid + WG < uCount;
-      uint32_t cur0 = 0, cur1 = 0;
-      // ---- which chunks can hold a group at all.  A group needs >= 3 hits on its allele.  The k-mers of a read that are not part of
-      // a gene's conserved sequence have short lists (a handful of chance postings anywhere in the reference), and there are enough of
-      // them to put a posting or two into EVERY chunk: stepping through all chunks for them was most of this kernel's time.  So: a
-      // chunk is visited if a long list (one with a directory row: its per-chunk occupancy mask is part of the index) has a posting
-      // in it, or if some allele of it collects three postings from the short lists alone -- counted exactly with two bitmaps over
-      // all alleles (seen once / seen twice; the third sighting marks the chunk).  Every other chunk holds no allele with three hits
-      // and cannot emit a record.  mk0 / mk1: chunk occupancy of this lane's own lists (chunks < 64; beyond that: "maybe").
-      unsigned long long mk0 = 0, mk1 = 0;
-      {
-        const uint32_t BW = (A + 31) >> 5;
-        uint32_t *b1 = bitmaps, *b2 = bitmaps + BW;
-        for (uint32_t i = tid; i < 2 * BW; i += WG) bitmaps[i] = 0;
-        if (tid < 8) sHot[tid] = 0;
-        __syncthreads();
-        auto mark = [&](bool has, uint32_t st, uint32_t ln, uint32_t row, unsigned long long &mk) {
-          if (!has || !ln) return;
-          if (row != T1K_NO_DIR) {
-            const unsigned long long *m = P.ref.kDirMask + (uint64_t)row * P.ref.kDirMaskWords;
-            for (uint32_t w = 0; w < P.ref.kDirMaskWords; ++w) {
-              const unsigned long long v = m[w];
-              if (w == 0) mk = v;
-              if ((uint32_t)v) atomicOr(&sHot[2 * w], (uint32_t)v);
-              if ((uint32_t)(v >> 32)) atomicOr(&sHot[2 * w + 1], (uint32_t)(v >> 32));
-            }
-            if (P.ref.kDirMaskWords > 1) mk = ~0ull;  // (more than 64 chunks: the directory itself answers)
-          } else {
-            for (uint32_t j0 = 0; j0 < ln; j0 += 8) {  // <= T1K_DIR_MINLEN postings; eight loads in flight
-              uint32_t al[8];
-#pragma unroll
-              for (int x = 0; x < 8; ++x) al[x] = j0 + x < ln ? P.ref.kPostAllele[st + j0 + x] : 0xFFFFFFFFu;
-#pragma unroll
-              for (int x = 0; x < 8; ++x) {
-                if (al[x] == 0xFFFFFFFFu) continue;
-                const uint32_t ci = al[x] / CHUNK_A, bit = 1u << (al[x] & 31);
-                mk |= ci < 64 ? 1ull << ci : 0ull;
-                if (atomicOr(&b1[al[x] >> 5], bit) & bit)
-                  if (atomicOr(&b2[al[x] >> 5], bit) & bit) atomicOr(&sHot[ci >> 5], 1u << (ci & 31));
-              }
-            }
-            if (nChunks > 64) mk = ~0ull;
-          }
-        };
-        mark(has0, has0 ? lstStart[uBegin + tid] : 0u, has0 ? LST_LEN(lstLen[uBegin + tid]) : 0u, has0 ? lstDir[uBegin + tid] : T1K_NO_DIR, mk0);
-        mark(has1, has1 ? lstStart[uBegin + tid + WG] : 0u, has1 ? LST_LEN(lstLen[uBegin + tid + WG]) : 0u, has1 ? lstDir[uBegin + tid + WG] : T1K_NO_DIR, mk1);
-        __syncthreads();
-        if (bitmaps == acc) {  // the bitmaps lay over the accumulators: make those clean again
-          for (uint32_t i = tid; i < 2 * BW; i += WG) acc[i] = (i % AW) == 0 ? (uint32_t)DIAG_EMPTY : 0u;
-          __syncthreads();
-        }
-      }
-      // first posting with allele >= bound in [lo, ln) of a short list (bisection over the allele column)
-      auto lowerBound = [&](uint32_t st, uint32_t lo, uint32_t ln, uint32_t bound) -> uint32_t {
-        uint32_t hi = ln;
-        while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (P.ref.kPostAllele[st + m] < bound) lo = m + 1; else hi = m; }
-        return lo;
-      };
-      for (uint32_t hw = 0; hw < 8; ++hw) {
-       uint32_t hotBits = sHot[hw];
-       while (hotBits) {
-        const uint32_t ci = hw * 32 + (uint32_t)__ffs((int)hotBits) - 1;
-        hotBits &= hotBits - 1;
-        const uint32_t c0 = ci * CHUNK_A;
-        const uint32_t c1 = min(c0 + CHUNK_A, A);
-#ifdef T1K_SEED_PROFILE
-        tp_[3] += 1;  // chunks visited (not a clock)
-#endif
-        // slice of every used list inside [c0, c1): long lists from their directory row, short ones by bisection from their cursor
-        // (the chunks come in ascending order, so the cursor only moves forward); lists without a posting here are not touched
-        // (a lane's list start / length / directory row are read back from LDS where they are needed: held in registers across the
-        // chunk loop they were spilled to scratch under the 64-VGPR budget)
-        uint32_t n0 = 0, n1 = 0;
-        const bool may = ci >= 64;
-        if (has0) {
-          uint32_t lo = cur0, hi = cur0;
-          if (may || ((mk0 >> ci) & 1ull)) {
-            const uint32_t row = lstDir[uBegin + tid];
-            if (row != T1K_NO_DIR) { const uint32_t *dir = P.ref.kDir + (uint64_t)row * P.ref.kDirStride; lo = dir[ci]; hi = dir[ci + 1]; }
-            else { const uint32_t st = lstStart[uBegin + tid], ln = LST_LEN(lstLen[uBegin + tid]); lo = lowerBound(st, cur0, ln, c0); hi = lowerBound(st, lo, ln, c1); }
-          }
-          n0 = hi - lo; sLo[tid] = lo; cur0 = hi;
-        }
-        if (has1) {
-          uint32_t lo = cur1, hi = cur1;
-          if (may || ((mk1 >> ci) & 1ull)) {
-            const uint32_t row = lstDir[uBegin + tid + WG];
-            if (row != T1K_NO_DIR) { const uint32_t *dir = P.ref.kDir + (uint64_t)row * P.ref.kDirStride; lo = dir[ci]; hi = dir[ci + 1]; }
-            else { const uint32_t st = lstStart[uBegin + tid + WG], ln = LST_LEN(lstLen[uBegin + tid + WG]); lo = lowerBound(st, cur1, ln, c0); hi = lowerBound(st, lo, ln, c1); }
-          }
-          n1 = hi - lo; sLo[tid + WG] = lo; cur1 = hi;
-        }
-
-#ifdef T1K_SEED_PROFILE
-    { const uint64_t tn_ = __builtin_amdgcn_s_memtime(); tp_[4] += tn_ - tl_; tl_ = tn_; }
-#endif
-        uint32_t tot0, tot1 = 0;
-        const uint32_t e0 = t1k_block_scan_exclusive(n0, warpSums, &tot0);
-        if (has0) pre[tid] = e0;
-        if (uCount > WG) {
-          const uint32_t e1 = t1k_block_scan_exclusive(n1, warpSums, &tot1);
-          if (has1) pre[tid + WG] = tot0 + e1;
-        }
-        const uint32_t T = tot0 + tot1;
-        if (tid == 0) { pre[uCount] = T; sStat[2] += T; }
-        __syncthreads();
-
-#ifdef T1K_SEED_PROFILE
-    { const uint64_t tn_ = __builtin_amdgcn_s_memtime(); tp_[5] += tn_ - tl_; tl_ = tn_; }
-#endif
-        // walk the chunk's postings.  The flat posting index [0, T) is cut into one contiguous range per wavefront; a lane finds the
-        // list of its first posting by bisection over the prefix ONCE, and from there its list index only moves forward (its
-        // positions grow by 64 a step), so the later postings cost a look at one or two prefix entries instead of a bisection each.
-        // Four postings in flight per lane; 64 consecutive postings per wavefront load.
-        {
-          const uint32_t wv = (uint32_t)tid >> 6, ln = (uint32_t)tid & 63u;
-          const uint32_t Rw = (((T + 3) >> 2) + 63u) & ~63u;
-          const uint32_t jBeg = wv * Rw, jEnd = min(T, jBeg + Rw);
-          uint32_t lo = 0;
-          if (jBeg + ln < jEnd) {
-            const uint32_t j = jBeg + ln;
-            uint32_t hi = uCount;
-            while (hi - lo > 1) { uint32_t m = (lo + hi) >> 1; if (pre[m] <= j) lo = m; else hi = m; }
-          }
-#ifndef T1K_SEED_INFLIGHT
-#define T1K_SEED_INFLIGHT 4
-#endif
-          for (uint32_t j0 = jBeg + ln; j0 < jEnd; j0 += T1K_SEED_INFLIGHT * 64) {
-            T1kPosting pst[T1K_SEED_INFLIGHT];
-            int rr[T1K_SEED_INFLIGHT];
-#pragma unroll
-            for (int x = 0; x < T1K_SEED_INFLIGHT; ++x) {
-              const uint32_t j = j0 + x * 64;
-              if (j < jEnd) {
-                while (pre[lo + 1] <= j) ++lo;  // pre[uCount] = T > j ends it
-                pst[x] = P.ref.kPost[lstStart[uBegin + lo] + sLo[lo] + (j - pre[lo])];
-                rr[x] = T1K_SEED_PACK_Q ? (int)(lstLen[uBegin + lo] >> 23) : (int)qOf[uBegin + lo];
-              }
-            }
-#pragma unroll
-            for (int x = 0; x < T1K_SEED_INFLIGHT; ++x) {
-              const uint32_t j = j0 + x * 64;
-              if (j < jEnd) {
-                const int r = rr[x];
-                const int d = r - (int)pst[x].offset;
-                uint32_t *a = acc + (pst[x].allele - c0) * AW;
-                const uint32_t old = atomicCAS(&a[0], (uint32_t)DIAG_EMPTY, (uint32_t)d);
-                if (old == (uint32_t)DIAG_EMPTY || old == (uint32_t)d) atomicOr(&a[2 + (r >> 5)], 1u << (r & 31));
-                else {
-                  int dd = d - (int)old; if (dd < 0) dd = -dd;
-                  atomicAdd(&a[1], dd <= P.radius ? 0x10001u : 1u);
-                }
-              }
-            }
-          }
-        }
-        __syncthreads();
-
-#ifdef T1K_SEED_PROFILE
-    { const uint64_t tn_ = __builtin_amdgcn_s_memtime(); tp_[6] += tn_ - tl_; tl_ = tn_; }
-#endif
-        // emit the groups that can still produce a candidate: >= 3 hits in total, and either >= 3 on the reference diagonal
-        // or some hit close enough to chain with it, or > 2 strays (which could form their own run).  Lane t looks at the
-        // accumulators t, t + WG, ... (conflict-free with the odd accumulator stride); the records leave in allele order.
-        constexpr int EPT = CHUNK_A / WG;
-        uint32_t flags = 0, kinds = 0;  // kinds (FUSE): 4 bits per accumulator row, groupFastPath's verdict (1 finished with a candidate, 5 gap walk) or 4 = several diagonals
-        uint64_t packed = 0;  // EPT counters of 16 bits
-        if (FUSE) {
-#pragma unroll 1
-          for (int i = 0; i < EPT; ++i) {
-            uint32_t *a = acc + (i * WG + tid) * AW;
-            if (a[0] == (uint32_t)DIAG_EMPTY) continue;
-            int onDiag = 0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) onDiag += __popc(a[2 + w]);
-            const uint32_t strays = a[1] & 0xFFFFu, nearCnt = a[1] >> 16;
-            const bool general = nearCnt > 0 || strays > 2;
-            flags |= 2u << (2 * i);  // occupied
-            if (!(onDiag + (int)strays >= 3 && (general || onDiag >= 3))) continue;
-            ++groupsLocal;
-            uint32_t kind = 4;
-            if (!general) {
-              // the closed-form pass (what k_chain_fast<NW, 0> does with the record): the candidate of a group that ends here waits in the
-              // accumulator's mask words (dead now) for the record write below; a group without a candidate leaves no record
-              const uint32_t allele = c0 + i * WG + tid;
-              kind = closedFormGroup<NW>(a, &sRd[pass][0][0], &sRd[pass][1][0], P.ref.bases, P.ref.nmask, (int64_t)P.ref.alleleOff[allele], P.ref.anyN != 0, P.ref.alleleHasN[allele] != 0, k,
-                                         P.hitLenRequired, P.sim, pass, P.earlyPrune);
-              if (kind == 1u) { ++fastLocal; continue; }  // no candidate
-              if (kind == 6u) { ++fastLocal; kind = 1u; }
-            }
-            flags |= 1u << (2 * i); packed += 1ull << (16 * i); kinds |= kind << (4 * i); ++recsLocal;
-          }
-        } else {
-#pragma unroll
-        for (int i = 0; i < EPT; ++i) {
-          const uint32_t *a = acc + (i * WG + tid) * AW;
-          if (a[0] == (uint32_t)DIAG_EMPTY) continue;
-          int onDiag = 0;
-#pragma unroll
-          for (int w = 0; w < NW; ++w) onDiag += __popc(a[2 + w]);
-          const uint32_t strays = a[1] & 0xFFFFu, nearCnt = a[1] >> 16;
-          const bool general = nearCnt > 0 || strays > 2;
-          flags |= 2u << (2 * i);  // occupied
-          if (onDiag + (int)strays >= 3 && (general || onDiag >= 3)) { flags |= 1u << (2 * i); packed += 1ull << (16 * i); }
-        }
-        }
-        uint32_t totLo, totHi = 0, exHi = 0;
-        const uint32_t exLo = t1k_block_scan_exclusive((uint32_t)packed, warpSums, &totLo);
-        exHi = t1k_block_scan_exclusive((uint32_t)(packed >> 32), warpSums, &totHi);  // (skipping it when CHUNK_A <= 512 -- the high word is empty then -- measured 4 % SLOWER)
-        const uint64_t ex = (uint64_t)exLo | ((uint64_t)exHi << 32), tt = (uint64_t)totLo | ((uint64_t)totHi << 32);
-        const uint32_t gTot = (uint32_t)((tt & 0xFFFF) + ((tt >> 16) & 0xFFFF) + ((tt >> 32) & 0xFFFF) + (tt >> 48));
-        if (tid == 0) {
-          const uint32_t gb = gTot ? t1k_arena_alloc(P.counters, T1K_AR_GROUPS, gTot, P.groupSegCap) : 0u;
-          const bool ok = gb != T1K_ARENA_FULL && chunk < P.maxChunks;
-          if (!ok) atomicOr(&P.counters[2], (unsigned long long)ERR_GROUPCAP);
-          sGroupBase = ok ? gb : 0xFFFFFFFFu;
-          if (ok && gTot) { P.chunkStart[(uint64_t)re * P.maxChunks + chunk] = gb; P.chunkCount[(uint64_t)re * P.maxChunks + chunk] = gTot; }
-        }
-        __syncthreads();
-        const uint32_t groupBase = sGroupBase;
-
-#ifdef T1K_SEED_PROFILE
-    { const uint64_t tn_ = __builtin_amdgcn_s_memtime(); tp_[7] += tn_ - tl_; tl_ = tn_; }
-#endif
-        if (gTot) ++chunk;
-        uint32_t before = 0;  // records of the lower accumulator rows
-#pragma unroll
-        for (int i = 0; i < EPT; ++i) {
-          if ((flags >> (2 * i)) & 2u) {
-            uint32_t *a = acc + (i * WG + tid) * AW;
-            if (((flags >> (2 * i)) & 1u) && groupBase != 0xFFFFFFFFu) {
-              const uint32_t slot = before + (uint32_t)((ex >> (16 * i)) & 0xFFFF);
-              uint4 *rec = (uint4 *)(P.recs + (uint64_t)(groupBase + slot) * stride);
-              constexpr int RW = NW == 5 ? 8 : 16;  // record words: re|strand, allele, diagonal + stray counts, M[NW]
-              uint32_t v[RW];
-              const uint32_t kind = FUSE ? (kinds >> (4 * i)) & 15u : 0u;
-              v[0] = re | (pass == 0 ? 0x80000000u : 0);  // bit31: '+' strand
-              v[1] = c0 + i * WG + tid;
-              if (FUSE && kind == 1u) {  // finished: state, candidate (the record k_chain_fast<NW, 0> leaves behind)
-                v[2] = REC_DONE | 1u; v[3] = a[2]; v[4] = a[3]; v[5] = a[4];
-#pragma unroll
-                for (int w = 6; w < RW; ++w) v[w] = 0;
-              } else {
-                v[2] = packDiagMeta((int)a[0], a[1]);
-#pragma unroll
-                for (int w = 0; w < NW; ++w) v[3 + w] = a[2 + w];
-#pragma unroll
-                for (int w = 3 + NW; w < RW; ++w) v[w] = 0;
-              }
-#pragma unroll
-              for (int w = 0; w < RW / 4; ++w) rec[w] = make_uint4(v[4 * w], v[4 * w + 1], v[4 * w + 2], v[4 * w + 3]);
-              if (FUSE) {  // the work lists k_chain_fast<NW, 0> used to fill
-                if (kind == 5u) { const uint32_t q = t1k_arena_append(P.counters, T1K_AR_SLOW, P.listSegCap); if (q != T1K_ARENA_FULL) P.slowStr[q] = groupBase + slot; }
-                else if (kind == 4u) { const uint32_t q = t1k_arena_append(P.counters, T1K_AR_GENERAL, P.rareSegCap); if (q != T1K_ARENA_FULL) P.generalStr[q] = groupBase + slot; }
-              }
-            }
-            a[0] = (uint32_t)DIAG_EMPTY; a[1] = 0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) a[2 + w] = 0;
-          }
-          before += (uint32_t)((tt >> (16 * i)) & 0xFFFF);
-        }
-        __syncthreads();
-       }
-      }
-    }
-  }
-#ifdef T1K_SEED_PROFILE
-  if (tid == 0) for (int i = 0; i < 8; ++i) atomicAdd(&P.counters[48 + i], (unsigned long long)tp_[i]);
-#endif
-  if (tid == 0) {  // statistics: one striped atomic per workgroup and counter
-    unsigned long long *st = P.counters + 64 + (blockIdx.x & (T1K_STAT_STRIPES - 1)) * 8;
-    atomicAdd(&st[T1K_STAT_LOOKUPS], sStat[0]); atomicAdd(&st[T1K_STAT_POSTINGS], sStat[1]); atomicAdd(&st[T1K_STAT_HITS], sStat[2]);
-  }
-  if (FUSE) {
-    t1k_stat_add(P.counters, T1K_STAT_FAST, fastLocal);
-    // groups seeded = records written + groups that ended without a candidate: the latter are counted here (control counters 56..63, striped)
-    unsigned int noRec = groupsLocal - recsLocal;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) noRec += __shfl_down(noRec, o, 64);
-    if ((tid & 63) == 0 && noRec) atomicAdd(&P.counters[56 + ((blockIdx.x * 4 + (tid >> 6)) & 7)], (unsigned long long)noRec);
-  }
-}
-template <int NW>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_SEED_WAVES, T1K_SEED_WAVES))) void k_seed_groups(ChainArgs P) { seedGroupsBody<NW, false>(P); }
-template <int NW>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_FUSE_WAVES, T1K_FUSE_WAVES))) void k_seed_chain(ChainArgs P) { seedGroupsBody<NW, true>(P); }
-
-// ------------------------------------------------------------------------------------------------------------------
-// K1L: seeding of the read-ends beyond the hit masks' span (T1K_MAX_READ_LEN < len <= T1K_LONG_READ_LEN), one workgroup per such
-// read-end; the others are k_seed_groups' and are skipped here.  No masks, no diagonals: the look-up rule (GetHitsFromRead,
-// SeqSet.hpp:1071-1229) is replayed sequentially by the first wavefront, the used lists are kept for gatherHits as usual, and a
-// (strand, allele) pair that collects >= 3 postings (minHitRequired, 1253 / 1314) becomes a group record flagged "several diagonals":
-// k_chain_fast<*, 0> hands such records to k_gather_general -> k_chain_general / k_chain_wave / k_chain_big, which rebuild the hit
-// list and run the reference's diagonal-run / LIS logic on it whatever the read's length.  Counts live in LDS for LONG_CH alleles at
-// a time; a pass emits its records in allele order as one entry of the read-end's chunk table ('-' strand first, as SortHits
-// 1577-1583 orders the groups).  Slow by design: such reads are the odd ones among millions.
-// ------------------------------------------------------------------------------------------------------------------
-#define LONG_CH 16384
-__global__ __launch_bounds__(WG) void k_seed_long(ChainArgs P) {
-  extern __shared__ uint32_t lds[];
-  const int k = P.k;
-  const int maxK = (int)P.maxK;
-  uint32_t *ukCode = lds;                           // [maxK]  code | valid << 31
-  uint32_t *ukStart = ukCode + maxK;                // [maxK]
-  uint32_t *ukLen = ukStart + maxK;                 // [maxK]
-  uint32_t *ukDir = ukLen + maxK;                   // [maxK]
-  uint16_t *usedQ = (uint16_t *)(ukDir + maxK);     // [maxK]  used k-mers, + strand first
-  uint32_t *cnt = (uint32_t *)(usedQ + ((maxK + 1) & ~1));  // [LONG_CH] postings per allele of the current pass
-  __shared__ uint32_t warpSums[4];
-  __shared__ uint32_t sUsed[2], sGroupBase;
-  const int tid = threadIdx.x;
-  const uint32_t kmask = (1u << (2 * k)) - 1;
-  const uint32_t stride = P.recStride;
-  const uint32_t A = P.ref.nAlleles;
-  unsigned int hitsLocal = 0;
-  for (uint32_t re = blockIdx.x; re < P.reads.nReadEnds; re += gridDim.x) {
-    const int len = P.reads.len[re];
-    if (len <= T1K_MAX_READ_LEN || (P.reads.skip && P.reads.skip[re])) continue;  // (uniform over the workgroup)
-    const int S = P.reads.S;
-    const uint64_t *rbase = P.reads.bases + (uint64_t)re * 2 * S;
-    const uint64_t *rnm = P.reads.nmask + (uint64_t)re * 2 * S;
-    const int nk = len - k + 1;
-    __syncthreads();  // the previous read-end's tables are dead
-    for (int q = tid; q < 2 * nk; q += WG) {
-      const int pass = q / nk, p = q - pass * nk;
-      const uint64_t *b = rbase + pass * S, *nm = rnm + pass * S;
-      const uint32_t code = (uint32_t)t1k_get32(b, p) & kmask;
-      const bool valid = ((uint32_t)t1k_get32(nm, p) & kmask) == 0;
-      uint32_t st = 0, ln = 0, dr = T1K_NO_DIR;
-      if (valid) { st = P.ref.kStart[code]; ln = P.ref.kStart[code + 1] - st; dr = P.ref.kDirIdx[code]; }
-      ukCode[q] = code | (valid ? 0x80000000u : 0);
-      ukStart[q] = st; ukLen[q] = ln; ukDir[q] = dr;
-    }
-    __syncthreads();
-    // the look-up rule, sequentially (SeqSet.hpp:1098-1153, 1165-1226): lane j of the first wavefront holds one k-mer's code
-    // and list length, the loop reads them with v_readlane (the same replay k_seed_groups runs for reads with short repeats)
-    if (tid < 64) {
-      uint32_t prev = 0, nUsed = 0, lookups = 0, postings = 0;
-      for (int pass = 0; pass < 2; ++pass) {
-        int skipCnt = 0;
-        const uint32_t begin = nUsed;
-        for (int seg = 0; seg < nk; seg += 64) {
-          const int pl = seg + tid;
-          const uint32_t vc = pl < nk ? (ukCode[pass * nk + pl] & 0x7FFFFFFFu) : 0u;
-          const uint32_t vl = pl < nk ? ukLen[pass * nk + pl] : 0u;
-          const int cntj = min(64, nk - seg);
-          for (int j = 0; j < cntj; ++j) {
-            const uint32_t code = (uint32_t)__builtin_amdgcn_readlane((int)vc, j);
-            const uint32_t size = (uint32_t)__builtin_amdgcn_readlane((int)vl, j);
-            const int p = seg + j;
-            if (p == 0 || code != prev) {
-              ++lookups;
-              if (size >= 100 && p != 0 && p != nk - 1 && skipCnt < k / 2) { ++skipCnt; continue; }
-              skipCnt = 0;
-              if (size) {
-                if (tid == 0) usedQ[nUsed] = (uint16_t)(pass * nk + p);
-                ++nUsed;
-                postings += size;
-              }
-            }
-            prev = code;
-          }
-        }
-        if (tid == 0) sUsed[pass] = nUsed - begin;
-      }
-      if (tid == 0) {
-        P.usedCount[2 * re] = sUsed[0]; P.usedCount[2 * re + 1] = sUsed[1];
-        unsigned long long *st = P.counters + 64 + (blockIdx.x & (T1K_STAT_STRIPES - 1)) * 8;
-        atomicAdd(&st[T1K_STAT_LOOKUPS], (unsigned long long)lookups); atomicAdd(&st[T1K_STAT_POSTINGS], (unsigned long long)postings);
-      }
-    }
-    __syncthreads();
-    const uint32_t nUsedPlus = sUsed[0], nUsedMinus = sUsed[1];
-    {
-      uint32_t *uo = P.usedOut + (uint64_t)re * maxK * 4;
-      for (uint32_t u = tid; u < nUsedPlus + nUsedMinus; u += WG) {
-        const int q = usedQ[u];
-        const int pass = u < nUsedPlus ? 0 : 1;
-        uo[4 * u] = (uint32_t)(q - pass * nk); uo[4 * u + 1] = ukStart[q]; uo[4 * u + 2] = ukLen[q]; uo[4 * u + 3] = ukDir[q];
-      }
-    }
-    int chunk = 0;
-    for (int sp = 0; sp < 2; ++sp) {  // '-' strand first
-      const int pass = sp == 0 ? 1 : 0;
-      const uint32_t uBegin = pass == 0 ? 0 : nUsedPlus;
-      const uint32_t uCount = pass == 0 ? nUsedPlus : nUsedMinus;
-      if (uCount == 0) continue;
-      for (uint32_t c0 = 0; c0 < A; c0 += LONG_CH) {
-        const uint32_t c1 = min(c0 + (uint32_t)LONG_CH, A);
-        for (uint32_t i = tid; i < LONG_CH; i += WG) cnt[i] = 0;
-        __syncthreads();
-        for (uint32_t u = tid; u < uCount; u += WG) {
-          const int q = usedQ[uBegin + u];
-          const uint32_t st = ukStart[q], ln = ukLen[q];
-          uint32_t lo = 0, hi = ln;  // first posting with allele >= c0
-          while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (P.ref.kPostAllele[st + m] < c0) lo = m + 1; else hi = m; }
-          for (uint32_t j = lo; j < ln; ++j) {
-            const uint32_t al = P.ref.kPostAllele[st + j];
-            if (al >= c1) break;
-            atomicAdd(&cnt[al - c0], 1u);
-            ++hitsLocal;
-          }
-        }
-        __syncthreads();
-        constexpr uint32_t PER = LONG_CH / WG;  // thread t looks at the alleles [c0 + t * PER, + PER): the records leave in allele order
-        uint32_t mine = 0;
-        for (uint32_t i = 0; i < PER; ++i) mine += cnt[tid * PER + i] >= 3u ? 1u : 0u;
-        uint32_t gTot;
-        const uint32_t ex = t1k_block_scan_exclusive(mine, warpSums, &gTot);
-        if (tid == 0) {
-          const uint32_t gb = gTot ? t1k_arena_alloc(P.counters, T1K_AR_GROUPS, gTot, P.groupSegCap) : 0u;
-          const bool ok = gb != T1K_ARENA_FULL && chunk < P.maxChunks;
-          if (!ok) atomicOr(&P.counters[2], (unsigned long long)ERR_GROUPCAP);
-          sGroupBase = ok ? gb : 0xFFFFFFFFu;
-          if (ok && gTot) { P.chunkStart[(uint64_t)re * P.maxChunks + chunk] = gb; P.chunkCount[(uint64_t)re * P.maxChunks + chunk] = gTot; }
-        }
-        __syncthreads();
-        const uint32_t groupBase = sGroupBase;
-        if (gTot) ++chunk;
-        if (mine && groupBase != 0xFFFFFFFFu) {
-          uint32_t slot = ex;
-          for (uint32_t i = 0; i < PER; ++i) {
-            if (cnt[tid * PER + i] < 3u) continue;
-            uint4 *rec = (uint4 *)(P.recs + (uint64_t)(groupBase + slot) * stride);
-            // words 0..2: read-end | '+' strand, allele, "several diagonals" (recIsGeneral: near count 1, diagonal 0); the rest is the chain's
-            rec[0] = make_uint4(re | (pass == 0 ? 0x80000000u : 0u), c0 + tid * PER + i, (1u << 21) | (31u << 25), 0u);  // near = 31: "count unknown", the hits come from the used lists
-            for (uint32_t w = 1; w < stride / 4; ++w) rec[w] = make_uint4(0u, 0u, 0u, 0u);
-            if (P.fuse) { const uint32_t gq = t1k_arena_append(P.counters, T1K_AR_GENERAL, P.rareSegCap); if (gq != T1K_ARENA_FULL) P.generalStr[gq] = groupBase + slot; }  // (no k_chain_fast<*, 0> lists it)
-            ++slot;
-          }
-        }
-        __syncthreads();
-      }
-    }
-  }
-  t1k_stat_add(P.counters, T1K_STAT_HITS, hitsLocal);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1233,18 +473,14 @@ __global__ __launch_bounds__(WG) void k_seed_long(ChainArgs P) {
 // MODE 0: all records, closed form only (the rest -> slow list; multi-diagonal groups -> general list)
 // MODE 1: slow list: gap walk, alignments registered in the memo (-> finish list / retry list)
 // MODE 2: retry list after k_dp_dense: alignments from the memo or inline
-// nDev != nullptr: the list's length is read there (the total word k_arena_compact left), nItems is ignored.  The workgroups stride over the
-// items, so a grid sized from an estimate (t1k_run_chain) covers whatever the device counted.
-// LOOP = false (the host-driven launches: one item per thread, the grid covers the list) keeps the straight-line kernel: the loop costs the
-// closed-form pass 16 VGPRs and a wavefront per SIMD (78 -> 94).
-#if T1K_CF0_WAVES > 0
-#define T1K_CF_ATTR __attribute__((amdgpu_waves_per_eu(MODE == 0 && NW == 5 ? T1K_CF0_WAVES : 1)))
-#else
-#define T1K_CF_ATTR
-#endif
-template <int NW, int MODE, bool LOOP>
-__global__ __launch_bounds__(WG) T1K_CF_ATTR void k_chain_fast(ChainArgs P, const uint32_t *list, uint32_t nItems, const unsigned long long *nDev) {
+// MODE 1 and 2 read their list's length at nDev (the total word k_arena_compact left) and stride over the list, so a grid sized from an
+// estimate (t1k_run_chain) covers whatever the device counted; nItems is ignored.  MODE 0 (no list: blockIdx.y = arena stripe, its length
+// from the stripe's cursor) is the straight-line form, one record per thread over a grid that covers what a stripe CAN hold: the striding
+// loop costs the closed-form pass 16 VGPRs and with them a wavefront per SIMD (78 -> 94), and workgroups beyond the cursor end at once.
+template <int NW, int MODE>
+__global__ __launch_bounds__(WG) void k_chain_fast(ChainArgs P, const uint32_t *list, uint32_t nItems, const unsigned long long *nDev) {
   constexpr bool DEFER = MODE != 2;
+  constexpr bool LOOP = MODE != 0;
   unsigned int dpLocal = 0, fastLocal = 0;
   if (nDev && P.counters[2]) return;  // an arena overflowed earlier in this submission: the range runs again, nothing of this pass is kept
   // list mode: 1-D grid over a dense list of record indices; all records: blockIdx.y = arena segment, blockIdx.x strides over the segment
@@ -1328,30 +564,6 @@ __global__ __launch_bounds__(WG) void k_dp_dense(ChainArgs P, const uint32_t *jo
     __hip_atomic_store(slot, (e & ~(GAP_PENDING << 25)) | ((unsigned long long)m << 25), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   t1k_stat_add(P.counters, T1K_STAT_DP, dpLocal);
-}
-
-// K3b: groups whose candidate waits for registered alignments: add the memo's match counts (SeqSet.hpp:1736-1741)
-__global__ __launch_bounds__(WG) void k_chain_finish(ChainArgs P, uint32_t nItems) {
-  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned int fastLocal = 0;
-  if (q < nItems) {
-    uint32_t *rec = P.recs + (uint64_t)P.finishList[q] * P.recStride;
-    const uint32_t re = rec[0] & 0x7FFFFFFFu;
-    const int nRefs = (int)rec[2];
-    const unsigned long long *memo = P.memo + (uint64_t)re * GAP_CACHE;
-    uint32_t sum = 0;
-    for (int i = 0; i < nRefs; ++i) {
-      const uint32_t slot = (rec[6 + (i >> 1)] >> (16 * (i & 1))) & 0xFFFFu;
-      const unsigned long long e = __hip_atomic_load(&memo[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t v = GAP_VAL(e);
-      if (v == GAP_PENDING) atomicOr(&P.counters[2], (unsigned long long)ERR_MEMO);  // cannot happen: every registered job is run by k_dp_dense
-      sum += v;
-    }
-    rec[5] += (2u * sum) << 20;
-    rec[2] = REC_DONE | 1u;
-    ++fastLocal;
-  }
-  t1k_stat_add(P.counters, T1K_STAT_FAST, fastLocal);
 }
 
 // re-derive the hit list of one (read-end, strand, allele) group from the used posting lists kept by k_seed_groups:
@@ -1875,8 +1087,8 @@ __device__ __forceinline__ bool keepCandidate(const ChainArgs &P, const uint16_t
 }
 
 // A single-diagonal group whose candidate still waits for registered alignments (record word 2 = their number, words 6..7 their memo
-// slots; k_dp_dense has run them): the match counts are added here, where the record is read anyway -- k_chain_finish used to fetch and
-// rewrite those records in a launch of its own (1.9 GB fetched per range for scattered 32-byte records).  Returns the candidate's word 2.
+// slots; k_dp_dense has run them): the match counts are added here, where the record is read anyway -- rounds 1-3 fetched and
+// rewrote those records in a launch of its own (1.9 GB fetched per range for scattered 32-byte records).  Returns the candidate's word 2.
 __device__ __forceinline__ uint32_t pendingMatchWord(const ChainArgs &P, uint32_t re, uint32_t nRefs, uint32_t w2, uint32_t s0, uint32_t s1) {
   const unsigned long long *memo = P.memo + (uint64_t)re * GAP_CACHE;
   uint32_t sum = 0;
@@ -1889,7 +1101,6 @@ __device__ __forceinline__ uint32_t pendingMatchWord(const ChainArgs &P, uint32_
   }
   return w2 + ((2u * sum) << 20);
 }
-__device__ __forceinline__ bool recPending(uint32_t state) { return !(state & REC_DONE) && state >= 1u && state <= (uint32_t)GROUP_MAX_REFS; }
 
 // MAXLEN: longest read of the launch (T1K_MAX_READ_LEN, or T1K_LONG_READ_LEN for a window with longer reads: 16 KB of prefix counts)
 #if T1K_COLLECT_WAVES > 0
@@ -2111,8 +1322,6 @@ int t1k_chain_rec_stride(int maxLen) { return maxLen <= 160 ? 8 : 16; }  // u32 
 int t1k_chain_max_kmers(int maxLen, int k) { return (2 * std::max(1, maxLen - k + 1) + 3) / 4 * 4; }
 int t1k_chain_used_u32(int maxK) { return maxK * 4; }  // per used list: read offset, list start, list length, directory row
 
-static int readCounters(t1k_ctx *ctx, unsigned long long *h) { return t1k_fetch_counters(ctx, h); }
-
 // striped list -> dense list; grid (blocks, T1K_NSTRIPE)
 // The first workgroup also leaves the dense list's length in the arena's total word (T1K_TOTAL_BASE) for the consumers that take their item
 // count from the device, and raises `overflowFlag` in the control word when a stripe is full (the range then runs again with larger lists).
@@ -2161,21 +1370,6 @@ void t1k_arena_compact_dev(t1k_ctx *ctx, int arena, const uint32_t *src, uint32_
                      (unsigned long long *)ctx->bCounters.p, arena, dst, (unsigned long long)ERR_GROUPCAP);
 }
 
-// sort key of a registered alignment: its read-window length, so that the lanes of a wavefront sweep DPs of equal height
-__global__ __launch_bounds__(WG) void k_job_keys(const unsigned long long *memo, const uint32_t *jobs, unsigned long long *keys, uint32_t n) {
-  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q < n) keys[q] = (memo[jobs[q]] >> 5) & 0x1FF;
-}
-// sort key of a multi-diagonal group: its hit count (record word 4 after k_gather_general), so that the lanes of k_chain_general's
-// wavefronts work on groups of similar size
-__global__ __launch_bounds__(WG) void k_group_size_keys(const uint32_t *recs, uint32_t stride, const uint32_t *list, unsigned long long *keys, uint32_t n, int useSimple) {
-  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q < n) {
-    const uint32_t *r = recs + (uint64_t)list[q] * stride;
-    const bool simple = useSimple && r[5] == REC_NEAR_DONE && r[6] == 1u;  // chains first (they skip the sorts: their own wavefronts), each kind by size
-    keys[q] = simple ? min(r[4], 127u) : 128u + min(r[4], 63u);
-  }
-}
 // ------------------------------------------------------------------------------------------------------------------
 // Counting sort of a dense work list by a small key (<= CS_BINS values), fused with the key's computation: the two in-loop orderings --
 // registered alignments by read-window length (wavefronts of k_dp_dense sweep DPs of equal height: mixed lengths ran at 40 % lane
@@ -2269,19 +1463,6 @@ static const uint32_t *countingSort(t1k_ctx *ctx, const uint32_t *list, uint32_t
   hipLaunchKernelGGL(k_csort_scatter<KeyFn>, dim3(grid), dim3(WG), 0, ctx->stream, list, n, scratch, sorted, key, nDev);
   return sorted;
 }
-void t1k_launch_dp_dense(t1k_ctx *ctx, const ChainArgs &a, const uint32_t *jobs, uint32_t n) {
-  if (!n) return;
-  // order the jobs by length first: wavefronts of mixed lengths ran at 40 % lane utilisation (T1K_RADIX_SORTS=1: the rocPRIM radix sort of rounds 2-4)
-  static const bool radix = getenv("T1K_RADIX_SORTS") != nullptr;
-  if (n >= 4096 && !radix) jobs = countingSort(ctx, jobs, n, JobLenKey{(const unsigned long long *)a.memo});
-  else if (n >= 4096 && t1k_ensure(ctx, ctx->bSlowKeys, (size_t)n * 20 + 64) == T1K_OK) {
-    unsigned long long *k0 = (unsigned long long *)ctx->bSlowKeys.p, *k1 = k0 + n;
-    uint32_t *sorted = (uint32_t *)(k1 + n);
-    hipLaunchKernelGGL(k_job_keys, dim3((n + WG - 1) / WG), dim3(WG), 0, ctx->stream, (const unsigned long long *)a.memo, jobs, k0, n);
-    if (t1k_sort_pairs(ctx, k0, k1, jobs, sorted, n, 9) == T1K_OK) jobs = sorted;
-  }
-  hipLaunchKernelGGL(k_dp_dense, dim3((n + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, jobs, n, (const unsigned long long *)nullptr);
-}
 // the same with the number of jobs read on the device (arena's total word); cap = the most there can be, est sizes the grids
 void t1k_launch_dp_dense_dev(t1k_ctx *ctx, const ChainArgs &a, const uint32_t *jobs, int arena, uint32_t cap, uint64_t est) {
   const unsigned long long *nDev = (const unsigned long long *)ctx->bCounters.p + T1K_TOTAL_BASE + arena;
@@ -2289,6 +1470,13 @@ void t1k_launch_dp_dense_dev(t1k_ctx *ctx, const ChainArgs &a, const uint32_t *j
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, (std::min<uint64_t>(cap, est) + WG - 1) / WG);
   hipLaunchKernelGGL(k_dp_dense, dim3(grid), dim3(WG), 0, ctx->stream, a, jobs, cap, nDev);
 }
+
+// expected entries of an arena in a range of nRe read-ends (a quarter to spare), never more than it can hold
+uint64_t t1k_arena_estimate(const t1k_ctx *ctx, int arena, uint64_t cap, uint32_t nRe) {
+  if (!ctx->estValid || !ctx->estTotal[arena]) return cap;
+  return std::min<uint64_t>(cap, (ctx->estTotal[arena] * std::max(1u, nRe) >> 16) * 5 / 4 + 4096);
+}
+void t1k_arena_estimate_set(t1k_ctx *ctx, int arena, uint64_t total, uint32_t nRe) { ctx->estTotal[arena] = (total << 16) / std::max(1u, nRe) + 1; }
 
 // ------------------------------------------------------------------------------------------------------------------
 // The chain of one range as ONE submission (round 5).  Rounds 1-4 fetched the counter block six times per range -- after seeding, after
@@ -2299,35 +1487,32 @@ void t1k_launch_dp_dense_dev(t1k_ctx *ctx, const ChainArgs &a, const uint32_t *j
 // stripe raises ERR_GROUPCAP on the device; the kernels behind it work on the clamped lists (their results are thrown away: the caller
 // runs the range again with the capacities the cursors ask for, as before).  One counter fetch is left, at the end.
 // ------------------------------------------------------------------------------------------------------------------
-// expected entries of an arena in a range of nRe read-ends (a quarter to spare), never more than it can hold
-uint64_t t1k_arena_estimate(const t1k_ctx *ctx, int arena, uint64_t cap, uint32_t nRe) {
-  if (!ctx->estValid || !ctx->estTotal[arena]) return cap;
-  return std::min<uint64_t>(cap, (ctx->estTotal[arena] * std::max(1u, nRe) >> 16) * 5 / 4 + 4096);
-}
-void t1k_arena_estimate_set(t1k_ctx *ctx, int arena, uint64_t total, uint32_t nRe) { ctx->estTotal[arena] = (total << 16) / std::max(1u, nRe) + 1; }
-bool t1k_chain_host_driven() { static const bool h = getenv("T1K_HOST_CHAIN") != nullptr; return h; }
-static int runChainDevice(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBlocks, bool longReads, bool xlong, unsigned long long *hc) {
+// runs K1..K6; on return counters[0] = number of candidates, counters[2] = error flags
+int t1k_run_chain(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBlocks, bool longReads, unsigned long long *hc) {
   ChainArgs a = aIn;
   a.devDriven = 1;
+  const bool xlong = a.maxK > a.maxKFast;  // the window holds read-ends beyond T1K_MAX_READ_LEN: k_seed_long takes those
+  T1K_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+  if (const int rc = t1k_launch_seed(ctx, a, longReads, xlong)) return rc;
+  T1K_HIP(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
   const unsigned long long *tot = (const unsigned long long *)ctx->bCounters.p + T1K_TOTAL_BASE;
   const uint32_t nRe = std::max<uint32_t>(1u, a.reads.nReadEnds);
   auto est = [&](int arena, uint64_t cap) -> uint64_t { return t1k_arena_estimate(ctx, arena, cap, nRe); };
   auto blocks = [](uint64_t items, uint32_t per) { return (uint32_t)std::max<uint64_t>(1, (items + per - 1) / per); };
   const uint64_t listCap = (uint64_t)a.listSegCap * T1K_NSTRIPE, rareCap = (uint64_t)a.rareSegCap * T1K_NSTRIPE, jobCap = (uint64_t)a.jobSegCap * T1K_NSTRIPE,
-                 genJobCap = (uint64_t)a.genJobSegCap * T1K_NSTRIPE, groupCap = (uint64_t)a.groupSegCap * T1K_NSTRIPE;
+                 genJobCap = (uint64_t)a.genJobSegCap * T1K_NSTRIPE;
   {  // closed-form pass over all records: blockIdx.y = stripe.  The straight-line kernel (the striding form costs it a wavefront per SIMD) over a
      // grid that covers what a stripe CAN hold: the workgroups beyond the stripe's cursor end at once (a few hundred thousand empty
      // workgroups are tens of microseconds of dispatch)
     const dim3 grid(blocks(a.groupSegCap, WG), T1K_NSTRIPE);
-    (void)groupCap;
-    if (longReads) hipLaunchKernelGGL((k_chain_fast<10, 0, false>), grid, dim3(WG), 0, ctx->stream, a, (const uint32_t *)nullptr, 0u, tot);
-    else hipLaunchKernelGGL((k_chain_fast<5, 0, false>), grid, dim3(WG), 0, ctx->stream, a, (const uint32_t *)nullptr, 0u, tot);
+    if (longReads) hipLaunchKernelGGL((k_chain_fast<10, 0>), grid, dim3(WG), 0, ctx->stream, a, (const uint32_t *)nullptr, 0u, tot);
+    else hipLaunchKernelGGL((k_chain_fast<5, 0>), grid, dim3(WG), 0, ctx->stream, a, (const uint32_t *)nullptr, 0u, tot);
   }
   {  // gap walk over the groups the closed form left
     const uint64_t e = est(T1K_AR_SLOW, listCap);
     t1k_arena_compact_dev(ctx, T1K_AR_SLOW, a.slowStr, a.listSegCap, a.slowList, e);
-    if (longReads) hipLaunchKernelGGL((k_chain_fast<10, 1, true>), dim3(blocks(e, WG)), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.slowList, 0u, tot + T1K_AR_SLOW);
-    else hipLaunchKernelGGL((k_chain_fast<5, 1, true>), dim3(blocks(e, WG)), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.slowList, 0u, tot + T1K_AR_SLOW);
+    if (longReads) hipLaunchKernelGGL((k_chain_fast<10, 1>), dim3(blocks(e, WG)), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.slowList, 0u, tot + T1K_AR_SLOW);
+    else hipLaunchKernelGGL((k_chain_fast<5, 1>), dim3(blocks(e, WG)), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.slowList, 0u, tot + T1K_AR_SLOW);
   }
   const uint64_t eJobs = est(T1K_AR_JOBS, jobCap), eRetry = est(T1K_AR_RETRY, listCap), eGen = est(T1K_AR_GENERAL, rareCap);
   t1k_arena_compact_dev(ctx, T1K_AR_JOBS, a.jobStr, a.jobSegCap, a.jobList, eJobs);
@@ -2336,11 +1521,10 @@ static int runChainDevice(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBl
   // (the finish list -- groups whose candidate waits for registered alignments -- is only a count here: k_collect adds the match counts itself;
   // a full stripe of it loses nothing, its entries are never read)
   t1k_launch_dp_dense_dev(ctx, a, a.jobList, T1K_AR_JOBS, (uint32_t)jobCap, eJobs);
-  if (longReads) hipLaunchKernelGGL((k_chain_fast<10, 2, true>), dim3(blocks(eRetry, WG)), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.retryList, 0u, tot + T1K_AR_RETRY);
-  else hipLaunchKernelGGL((k_chain_fast<5, 2, true>), dim3(blocks(eRetry, WG)), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.retryList, 0u, tot + T1K_AR_RETRY);
+  if (longReads) hipLaunchKernelGGL((k_chain_fast<10, 2>), dim3(blocks(eRetry, WG)), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.retryList, 0u, tot + T1K_AR_RETRY);
+  else hipLaunchKernelGGL((k_chain_fast<5, 2>), dim3(blocks(eRetry, WG)), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.retryList, 0u, tot + T1K_AR_RETRY);
   {  // groups with hits on several diagonals
-    static const bool nearHits = getenv("T1K_NO_NEAR_HITS") == nullptr;
-    const int skipDone = nearHits && !xlong ? 1 : 0;
+    const int skipDone = !xlong;  // k_near_hits writes the hit lists it can (its masks span T1K_MAX_READ_LEN), k_gather_general the rest
     const unsigned long long *nGen = tot + T1K_AR_GENERAL;
     if (skipDone) {
       if (longReads) hipLaunchKernelGGL(k_near_hits<10>, dim3(blocks(eGen, WG)), dim3(WG), 0, ctx->stream, a, 0u, nGen);
@@ -2357,8 +1541,8 @@ static int runChainDevice(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBl
     T1K_HIP(ctx, hipFuncSetAttribute((const void *)k_chain_wave, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * WAVE_CAP * 4));
     {
       const uint32_t wgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(eWave, 2048u));
-      static const uint32_t smallCap = getenv("T1K_WAVE_SMALL") ? (uint32_t)atoi(getenv("T1K_WAVE_SMALL")) : 512u;  // 0: one launch as in rounds 2-4
-      if (smallCap) hipLaunchKernelGGL(k_chain_wave, dim3(wgrid), dim3(64), 3 * smallCap * 4, ctx->stream, a, 0u, tot + T1K_AR_WAVE, smallCap, 0u);
+      const uint32_t smallCap = 512;  // the list is run twice: the small LDS size class first, the groups beyond it with the full arrays
+      hipLaunchKernelGGL(k_chain_wave, dim3(wgrid), dim3(64), 3 * smallCap * 4, ctx->stream, a, 0u, tot + T1K_AR_WAVE, smallCap, 0u);
       hipLaunchKernelGGL(k_chain_wave, dim3(wgrid), dim3(64), 3 * WAVE_CAP * 4, ctx->stream, a, 0u, tot + T1K_AR_WAVE, (uint32_t)WAVE_CAP, smallCap);
     }
     const uint64_t eGenJobs = est(T1K_AR_GENJOBS, genJobCap);
@@ -2371,8 +1555,7 @@ static int runChainDevice(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBl
   if (xlong) hipLaunchKernelGGL(k_collect<T1K_LONG_READ_LEN>, dim3(nWg), dim3(WG), 0, ctx->stream, a);
   else hipLaunchKernelGGL(k_collect<T1K_MAX_READ_LEN>, dim3(nWg), dim3(WG), 0, ctx->stream, a);
   T1K_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-  const int rc = readCounters(ctx, hc);
-  if (rc) return rc;
+  if (const int rc = t1k_fetch_counters(ctx, hc)) return rc;
   // what the cursors say: overflow of a list whose compaction is the only place that could have seen it, the statistics, the next range's estimates
   const T1kArenaCounts groups = t1k_arena_counts(ctx, T1K_AR_GROUPS, a.groupSegCap), slow = t1k_arena_counts(ctx, T1K_AR_SLOW, a.listSegCap), jobs = t1k_arena_counts(ctx, T1K_AR_JOBS, a.jobSegCap),
                        retry = t1k_arena_counts(ctx, T1K_AR_RETRY, a.listSegCap), fin = t1k_arena_counts(ctx, T1K_AR_FINISH, a.listSegCap), gen = t1k_arena_counts(ctx, T1K_AR_GENERAL, a.rareSegCap),
@@ -2391,134 +1574,4 @@ static int runChainDevice(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBl
     ctx->estValid = true;
   }
   return 0;
-}
-
-// runs K1..K6; on return counters[0] = number of candidates, counters[2] = error flags
-int t1k_run_chain(t1k_ctx *ctx, const ChainArgs &a, int nWg, int bigBlocks, bool longReads, unsigned long long *hc) {
-  const int AW = longReads ? 13 : 7;
-  const size_t maxK = a.maxKFast;
-  const bool xlong = a.maxK > a.maxKFast;  // the window holds read-ends beyond T1K_MAX_READ_LEN: k_seed_long takes those
-  size_t lds = (size_t)CHUNK_A * AW * 4 + maxK * (5 * 4 + (T1K_SEED_PACK_Q ? 0 : 2)) + 4 + (T1K_SEED_PACK_Q ? 8 : 64);  // accumulators | sLo, pre, lstStart, lstLen, lstDir, qOf
-  const size_t bitmapWords = 2 * (((size_t)a.ref.nAlleles + 31) / 32);        // chunk selection: two bitmaps over all alleles ...
-  if (bitmapWords > (size_t)CHUNK_A * AW) lds += bitmapWords * 4 + 8;         // ... behind the list arrays when the accumulators cannot hold them
-  if (a.ref.kDirStride - 1 > 256) return t1k_fail(ctx, T1K_ERR_ARG, "the reference holds more than 131 072 distinct sequences (256 seeding chunks)");
-  if (lds > 160 * 1024) return t1k_fail(ctx, T1K_ERR_ARG, "the reference holds too many sequences for the seeding kernel's LDS bitmaps");
-  // the seeding kernel keeps no per-workgroup HBM scratch: one workgroup per read-end (up to 32768) balances their uneven cost best
-  const char *esw = getenv("T1K_SEED_WG");
-  const int seedWg = (int)std::min<uint32_t>(a.reads.nReadEnds, esw ? (uint32_t)atoi(esw) : 32768u);
-  T1K_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-  if (a.fuse) {
-    if (longReads) {
-      T1K_HIP(ctx, hipFuncSetAttribute((const void *)k_seed_chain<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_seed_chain<10>, dim3(seedWg), dim3(WG), lds, ctx->stream, a);
-    } else {
-      T1K_HIP(ctx, hipFuncSetAttribute((const void *)k_seed_chain<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_seed_chain<5>, dim3(seedWg), dim3(WG), lds, ctx->stream, a);
-    }
-  } else if (longReads) {
-    T1K_HIP(ctx, hipFuncSetAttribute((const void *)k_seed_groups<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_seed_groups<10>, dim3(seedWg), dim3(WG), lds, ctx->stream, a);
-  } else {
-    T1K_HIP(ctx, hipFuncSetAttribute((const void *)k_seed_groups<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_seed_groups<5>, dim3(seedWg), dim3(WG), lds, ctx->stream, a);
-  }
-  if (xlong) {
-    const size_t ldsLong = (size_t)a.maxK * (4 * 4 + 2) + 8 + (size_t)LONG_CH * 4;
-    T1K_HIP(ctx, hipFuncSetAttribute((const void *)k_seed_long, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsLong));
-    hipLaunchKernelGGL(k_seed_long, dim3(std::min<uint32_t>(a.reads.nReadEnds, 32768u)), dim3(WG), ldsLong, ctx->stream, a);
-  }
-  T1K_HIP(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
-  // T1K_HOST_CHAIN: the launch sequence of rounds 1-4 -- the host fetches the counters between a producer and its consumers (A/B, fallback)
-  if (!t1k_chain_host_driven() && !a.fuse) return runChainDevice(ctx, a, nWg, bigBlocks, longReads, xlong, hc);
-  const unsigned long long *NODEV = nullptr;
-  int rc = readCounters(ctx, hc);
-  if (rc) return rc;
-  if (hc[2]) return 0;
-  const T1kArenaCounts groups = t1k_arena_counts(ctx, T1K_AR_GROUPS, a.groupSegCap);
-  const unsigned long long groupsSeeded = hc[6];  // records + (fused seeding) the groups that ended without one
-  if (!a.fuse) {  // the closed-form pass as a launch of its own over all records (T1K_FUSE_SEED=0)
-    if (groups.maxSeg) {
-      const dim3 grid((groups.maxSeg + WG - 1) / WG, T1K_NSTRIPE);
-      if (longReads) hipLaunchKernelGGL((k_chain_fast<10, 0, false>), grid, dim3(WG), 0, ctx->stream, a, (const uint32_t *)nullptr, 0u, NODEV);
-      else hipLaunchKernelGGL((k_chain_fast<5, 0, false>), grid, dim3(WG), 0, ctx->stream, a, (const uint32_t *)nullptr, 0u, NODEV);
-    }
-    if ((rc = readCounters(ctx, hc))) return rc;
-  }
-  const T1kArenaCounts slow = t1k_arena_counts(ctx, T1K_AR_SLOW, a.listSegCap);
-  if (slow.overflow) { hc[2] |= ERR_GROUPCAP; return 0; }
-  ctx->lastSlowGroups = slow.total;
-  if (slow.total) {
-    t1k_arena_compact(ctx, T1K_AR_SLOW, a.slowStr, a.listSegCap, a.slowList, slow.maxSeg);
-    const uint32_t nSlowGroups = (uint32_t)slow.total;
-    if (longReads) hipLaunchKernelGGL((k_chain_fast<10, 1, false>), dim3((nSlowGroups + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.slowList, nSlowGroups, NODEV);
-    else hipLaunchKernelGGL((k_chain_fast<5, 1, false>), dim3((nSlowGroups + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.slowList, nSlowGroups, NODEV);
-  }
-  if ((rc = readCounters(ctx, hc))) return rc;
-  hc[6] = groupsSeeded;
-  const T1kArenaCounts jobs = t1k_arena_counts(ctx, T1K_AR_JOBS, a.jobSegCap), retry = t1k_arena_counts(ctx, T1K_AR_RETRY, a.listSegCap),
-                       fin = t1k_arena_counts(ctx, T1K_AR_FINISH, a.listSegCap), gen = t1k_arena_counts(ctx, T1K_AR_GENERAL, a.rareSegCap);
-  // A full job segment is NOT benign: the lane that could not list its job released the memo claim, but another lane may already be
-  // waiting on that slot (it saw the claim) and would find it empty or re-claimed at finish time.  The range runs again with a larger list.
-  if (retry.overflow || fin.overflow || gen.overflow || jobs.overflow) { hc[2] |= ERR_GROUPCAP; return 0; }
-  hc[16] = jobs.total; hc[17] = retry.total; hc[18] = gen.total; hc[22] = fin.total;
-  t1k_arena_compact(ctx, T1K_AR_JOBS, a.jobStr, a.jobSegCap, a.jobList, jobs.maxSeg);
-  t1k_arena_compact(ctx, T1K_AR_FINISH, a.finishStr, a.listSegCap, a.finishList, fin.maxSeg);
-  t1k_arena_compact(ctx, T1K_AR_RETRY, a.retryStr, a.listSegCap, a.retryList, retry.maxSeg);
-  t1k_arena_compact(ctx, T1K_AR_GENERAL, a.generalStr, a.rareSegCap, a.generalList, gen.maxSeg);
-  const uint32_t nJobs = (uint32_t)jobs.total, nRetry = (uint32_t)retry.total, nGen = (uint32_t)gen.total, nFinish = (uint32_t)fin.total;
-  t1k_launch_dp_dense(ctx, a, a.jobList, nJobs);
-  // (k_collect adds the registered alignments' match counts itself; T1K_FINISH_KERNEL=1 runs the separate pass of rounds 1-3 first)
-  static const bool finishKernel = getenv("T1K_FINISH_KERNEL") != nullptr;
-  if (nFinish && finishKernel) hipLaunchKernelGGL(k_chain_finish, dim3((nFinish + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, nFinish);
-  if (nRetry) {
-    if (longReads) hipLaunchKernelGGL((k_chain_fast<10, 2, false>), dim3((nRetry + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.retryList, nRetry, NODEV);
-    else hipLaunchKernelGGL((k_chain_fast<5, 2, false>), dim3((nRetry + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, (const uint32_t *)a.retryList, nRetry, NODEV);
-  }
-  uint32_t nBig = 0;
-  if (nGen) {
-    static const bool nearHits = getenv("T1K_NO_NEAR_HITS") == nullptr;
-    const int skipDone = nearHits && !xlong ? 1 : 0;
-    if (skipDone) {
-      if (longReads) hipLaunchKernelGGL(k_near_hits<10>, dim3((nGen + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, nGen, NODEV);
-      else hipLaunchKernelGGL(k_near_hits<5>, dim3((nGen + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, nGen, NODEV);
-    }
-    if (xlong) hipLaunchKernelGGL(k_gather_general<(T1K_LONG_READ_LEN + 63) / 64>, dim3(std::min<uint32_t>((nGen + 3) / 4, 8192u)), dim3(WG), 0, ctx->stream, a, nGen, skipDone, NODEV);
-    else hipLaunchKernelGGL(k_gather_general<GROUP_FAST_MAXLEN / 64>, dim3(std::min<uint32_t>((nGen + 3) / 4, 8192u)), dim3(WG), 0, ctx->stream, a, nGen, skipDone, NODEV);
-    ChainArgs g = a;
-    static const bool radix = getenv("T1K_RADIX_SORTS") != nullptr;
-    if (nGen >= 4096 && !radix)  // groups of similar size side by side
-      g.generalList = (uint32_t *)countingSort(ctx, a.generalList, nGen, GroupSizeKey{(const uint32_t *)a.recs, a.recStride, skipDone});
-    else if (nGen >= 4096 && t1k_ensure(ctx, ctx->bSlowKeys, (size_t)nGen * 20 + 64) == T1K_OK) {
-      unsigned long long *k0 = (unsigned long long *)ctx->bSlowKeys.p, *k1 = k0 + nGen;
-      uint32_t *sorted = (uint32_t *)(k1 + nGen);
-      hipLaunchKernelGGL(k_group_size_keys, dim3((nGen + WG - 1) / WG), dim3(WG), 0, ctx->stream, (const uint32_t *)a.recs, a.recStride, (const uint32_t *)a.generalList, k0, nGen, skipDone);
-      if (t1k_sort_pairs(ctx, k0, k1, a.generalList, sorted, nGen, 8) == T1K_OK) g.generalList = sorted;
-    }
-    hipLaunchKernelGGL(k_chain_general, dim3((nGen + 63) / 64), dim3(64), 0, ctx->stream, g, nGen, skipDone, NODEV);
-    if ((rc = readCounters(ctx, hc))) return rc;
-    const T1kArenaCounts wv = t1k_arena_counts(ctx, T1K_AR_WAVE, a.rareSegCap);
-    if (wv.overflow) { hc[2] |= ERR_GROUPCAP; return 0; }
-    if (wv.total) {
-      t1k_arena_compact(ctx, T1K_AR_WAVE, a.waveStr, a.rareSegCap, a.waveList, wv.maxSeg);
-      T1K_HIP(ctx, hipFuncSetAttribute((const void *)k_chain_wave, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * WAVE_CAP * 4));
-      hipLaunchKernelGGL(k_chain_wave, dim3(std::min<uint32_t>((uint32_t)wv.total, 2048u)), dim3(64), 3 * WAVE_CAP * 4, ctx->stream, a, (uint32_t)wv.total, NODEV, (uint32_t)WAVE_CAP, 0u);
-    }
-    if ((rc = readCounters(ctx, hc))) return rc;  // the general kernels register alignments and may hand groups over to the big-scratch kernel
-    const T1kArenaCounts gj = t1k_arena_counts(ctx, T1K_AR_GENJOBS, a.genJobSegCap);
-    if (gj.overflow) { hc[2] |= ERR_GROUPCAP; return 0; }
-    t1k_arena_compact(ctx, T1K_AR_GENJOBS, a.genJobStr, a.genJobSegCap, a.genJobList, gj.maxSeg);
-    t1k_launch_dp_dense(ctx, a, a.genJobList, (uint32_t)gj.total);
-    hipLaunchKernelGGL(k_general_finish, dim3((nGen + WG - 1) / WG), dim3(WG), 0, ctx->stream, a, nGen, NODEV);
-    const T1kArenaCounts big = t1k_arena_counts(ctx, T1K_AR_BIG, a.rareSegCap);
-    if (big.overflow) { hc[2] |= ERR_GROUPCAP; return 0; }
-    t1k_arena_compact(ctx, T1K_AR_BIG, a.bigStr, a.rareSegCap, a.bigList, big.maxSeg);
-    nBig = (uint32_t)big.total;
-  }
-  if (nBig) hipLaunchKernelGGL(k_chain_big, dim3(bigBlocks * 64), dim3(64), 0, ctx->stream, a, nBig, NODEV);
-  if (xlong) hipLaunchKernelGGL(k_collect<T1K_LONG_READ_LEN>, dim3(nWg), dim3(WG), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_collect<T1K_MAX_READ_LEN>, dim3(nWg), dim3(WG), 0, ctx->stream, a);
-  T1K_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-  rc = readCounters(ctx, hc);
-  hc[6] = groupsSeeded; hc[16] = jobs.total; hc[17] = retry.total; hc[18] = gen.total; hc[19] = nBig; hc[22] = fin.total;
-  return rc;
 }

@@ -628,12 +628,13 @@ enum { T1K_STAT_DP = 0, T1K_STAT_FAST = 1, T1K_STAT_GENERAL = 2, T1K_STAT_EXTEND
 #endif
 // (round 6) T1K_<KERNEL>_WAVES: the wavefronts per SIMD the register allocation of a kernel aims for; 0 = the compiler's own choice, which is what
 // ships for these four.  Measured (profiles/r06_callG_occupancy_variants.log, one pipeline, per range): k_collect at 7: 0.98 -> 0.94 ms, k_extend at 7:
-// 0.85 -> 0.79 ms, k_truncate small at 6 / 7: no change, large at 8: 0.61 -> 0.65 ms -- and k_chain_fast<5, 0> at 7 (72 VGPRs, 32 of its registers
-// spilled): 1.90 -> 2.42 ms AND WRONG, VARYING RESULTS in every configuration (one pipeline, host-driven chain, kernels serialised:
-// profiles/r06_callH_occupancy_bisect.log, r06_callI_closed_form_spill_variant.log).  The kernel was re-read for values used before they are set
-// and for out-of-range local indices without a finding; the build that ships keeps it in registers (78 VGPRs, no scratch) and is the one every test
-// and reference hash covers.  Budgets are therefore only ever RAISED towards what a kernel's LDS admits (k_seed_groups, k_select's small shape:
-// fewer spills than before), never lowered.
+// 0.85 -> 0.79 ms, k_truncate small at 6 / 7: no change, large at 8: 0.61 -> 0.65 ms.  k_chain_fast<5, 0> had such a switch too (T1K_CF0_WAVES, since
+// removed): held to 7 (72 VGPRs, 32 of its registers spilled) it took 2.42 ms instead of 1.90 AND GAVE WRONG, VARYING RESULTS in every configuration
+// that was tried (one pipeline, host-driven chain, kernels serialised: profiles/r06_callH_occupancy_bisect.log,
+// r06_callI_closed_form_spill_variant.log).  The kernel was re-read for values used before they are set and for out-of-range local indices without a
+// finding; the build that ships keeps it in registers (78 VGPRs, no scratch), is the one every test and reference hash covers, and
+// tests/test_kernel_resources_cpu.py fails a build that spills it.  Budgets are therefore only ever RAISED towards what a kernel's LDS admits
+// (k_seed_groups, k_select's small shape: fewer spills than before), never lowered.
 #define T1K_WAVES_ATTR_(n) __attribute__((amdgpu_waves_per_eu(n)))
 // read-ends a workgroup takes per atomic on its kernel's hand-out word (round 6, profiles/r06_callL_hot_word_atomics.log, one pipeline, per range of 32 768
 // read-ends).  A returning atomic on one word saturates near 88 M/s on this part: 32 768 hand-outs are 0.37 ms, which is what a kernel that SKIPS most read-ends
@@ -660,9 +661,6 @@ enum { T1K_STAT_DP = 0, T1K_STAT_FAST = 1, T1K_STAT_GENERAL = 2, T1K_STAT_EXTEND
 #endif
 #ifndef T1K_EXTEND_WAVES
 #define T1K_EXTEND_WAVES 0
-#endif
-#ifndef T1K_CF0_WAVES
-#define T1K_CF0_WAVES 0
 #endif
 #ifndef T1K_TRUNC_SMALL_WAVES
 #define T1K_TRUNC_SMALL_WAVES 0
@@ -801,7 +799,7 @@ struct t1k_ctx {
                                  // t1k_coverage_selected over the kept lists, or not wanted at all)
   double msAlloc = 0;            // wall time spent in hipMalloc (fresh VRAM is zeroed by the driver: ~35 ms per GB)
   uint64_t bytesAlloc = 0;
-  T1kDevBuf bCand, bExt, bCandStart, bCandCount, bOvlStart, bOvlCount, bCounters, bSlowQueue, bSlowScratch, bSortScratch, bEqTrace, bSortTmp, bSlowKeys, bJobSort;
+  T1kDevBuf bCand, bExt, bCandStart, bCandCount, bOvlStart, bOvlCount, bCounters, bSlowQueue, bSlowScratch, bSortScratch, bEqTrace, bSortTmp, bJobSort;
   uint64_t nCand = 0, nOvl = 0;
   // pairing
   T1kDevBuf bEnd1, bEnd2, bHasN, bRows, bRowStart, bRowCount, bFragAssigned, bPairScratch, bPairOverflow, bPairBig, bExtractHuge;

@@ -15,17 +15,16 @@ struct ChainArgs {
   uint32_t *usedOut, *usedCount;                           // [re][maxK][4] used k-mers (readOff, listStart, listLen, directory row); [re][2] counts per strand
   unsigned long long *memo;                                // [re][GAP_CACHE] memo of gap alignments
   uint32_t *jobList; uint32_t jobCap;
-  uint32_t *retryList, *generalList, *bigList, *finishList;  // dense lists (filled by k_arena_compact)
+  uint32_t *retryList, *generalList, *bigList;  // dense lists (filled by k_arena_compact)
   uint32_t *jobStr, *retryStr, *generalStr, *bigStr, *finishStr, *waveStr, *waveList, *slowStr, *slowList;  // striped arenas the kernels append to
-  uint32_t groupSegCap, jobSegCap, listSegCap, rareSegCap, genCandSegCap, genHitSegCap;  // listSegCap: slow / retry / finish lists; rareSegCap: general / wave / big
+  uint32_t groupSegCap, jobSegCap, listSegCap, rareSegCap, genCandSegCap, genHitSegCap;  // listSegCap: slow / retry / finish arenas; rareSegCap: general / wave / big
   uint32_t maxK;  // upper bound of the k-mers of a read-end (both strands): stride of the used-list table
   uint32_t maxKFast;  // the same for the read-ends k_seed_groups takes (<= T1K_MAX_READ_LEN bases): its LDS layout; < maxK in a window with longer reads
   uint32_t *genJobStr, *genJobList; uint32_t genJobSegCap;  // alignments registered by the multi-diagonal groups
   uint32_t *genHits;  // hit lists of the multi-diagonal groups (k_gather_general)
   uint32_t *genCand; uint32_t genCandCap;                  // packed candidates of multi-diagonal groups (3 u32 each)
   uint32_t *bigScratch;
-  int fuse;                // the seeding kernel runs the closed-form pass itself (k_seed_chain) and fills the gap-walk / multi-diagonal lists; 0 (T1K_FUSE_SEED=0): k_seed_groups + k_chain_fast<*, 0>
-  int devDriven;             // this submission holds no counter fetch between its launches (runChainDevice): a launch behind an overflow ends at once
+  int devDriven;           // this submission holds no counter fetch between its launches (t1k_run_chain: always 1): a launch behind an overflow ends at once
   int nearSimple;          // k_near_hits marks the two-diagonal groups whose hit list is its chain (T1K_NO_SIMPLE_CHAIN=1: leaves them to the general path)
   int earlyPrune;          // k_chain_fast<*, 0>: 0 = closed form only (T1K_NO_EARLY_PRUNE=1), 1 = + the groups that cannot pass the similarity filter by the gap-count bound
                            // (T1K_WALK_IN_CLOSED=0), 2 = + the gap walk's first pass: groups without a gap of more than three mismatches and groups its bound prunes (default)
@@ -149,6 +148,7 @@ int t1k_chain_memo_entries();
 int t1k_chain_rec_stride(int maxLen);
 int t1k_chain_max_kmers(int maxLen, int k);
 int t1k_chain_used_u32(int maxK);
+int t1k_launch_seed(t1k_ctx *ctx, const ChainArgs &a, bool longReads, bool xlong);  // t1k_seed.hip: k_seed_groups (+ k_seed_long when xlong)
 int t1k_run_chain(t1k_ctx *ctx, const ChainArgs &a, int nWg, int bigBlocks, bool longReads, unsigned long long *hc);
 void t1k_launch_extend(t1k_ctx *ctx, const ExtendArgs &a);
 void t1k_launch_select(t1k_ctx *ctx, const SelectArgs &a, int nWg);
@@ -168,14 +168,11 @@ T1kArenaCounts t1k_arena_counts(const t1k_ctx *ctx, int arena, uint32_t segCap);
 void t1k_launch_coverage_add(t1k_ctx *ctx, int32_t *dst, int32_t *src, uint64_t n);
 int t1k_coverage_fold(t1k_ctx *ctx);  // covFull -> covDiff (on the context's stream, not synchronised)
 void t1k_launch_missing_coverage(t1k_ctx *ctx, const T1kRefDev &ref, int32_t *scratch, int32_t *missing);
-void t1k_launch_extend_retry(t1k_ctx *ctx, const ExtendArgs &a, const uint32_t *list, uint32_t n);
-void t1k_launch_dp_dense(t1k_ctx *ctx, const ChainArgs &a, const uint32_t *jobs, uint32_t n);
-// device-driven forms (t1k_chain.hip, runChainDevice): item counts read on the device from the arena's total word, grids from estimates
+// device-driven launches (t1k_run_chain, t1k_assign_range): item counts read on the device from the arena's total word, grids from estimates
 void t1k_arena_compact_dev(t1k_ctx *ctx, int arena, const uint32_t *src, uint32_t segCap, uint32_t *dst, uint64_t estTotal);
 void t1k_launch_dp_dense_dev(t1k_ctx *ctx, const ChainArgs &a, const uint32_t *jobs, int arena, uint32_t cap, uint64_t est);
 uint64_t t1k_arena_estimate(const t1k_ctx *ctx, int arena, uint64_t cap, uint32_t nRe);
 void t1k_arena_estimate_set(t1k_ctx *ctx, int arena, uint64_t total, uint32_t nRe);
-bool t1k_chain_host_driven();
 void t1k_launch_extend_retry_dev(t1k_ctx *ctx, const ExtendArgs &a, const uint32_t *list, int arena, uint64_t est);
 void t1k_arena_compact64(t1k_ctx *ctx, int arena, const unsigned long long *src, uint32_t segCap, unsigned long long *dst, uint32_t maxSeg);
 int t1k_sort_pairs(t1k_ctx *ctx, const unsigned long long *keysIn, unsigned long long *keysOut, const uint32_t *valsIn, uint32_t *valsOut, uint32_t n, int endBit = 64);

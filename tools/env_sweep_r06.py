@@ -20,7 +20,6 @@ for i in range(runs):
     if rng.random() < 0.2: env["T1K_COVERAGE"] = "eager"
     if rng.random() < 0.2: env["T1K_CROSS_WINDOW"] = "0"
     if rng.random() < 0.15: env["T1K_ARCHIVE_GB"] = "0.001"
-    if rng.random() < 0.15: env["T1K_HOST_CHAIN"] = "1"
     out = os.path.join(tmp, "o")
     r = subprocess.run([exe] + c.args() + ["-o", out, "--outputReadAssignment"], stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True, env=dict(os.environ, **env))
     ok = r.returncode == 0
