@@ -319,6 +319,33 @@ int t1k_barcode_em(t1k_ctx *ctx, uint32_t nBarcodes, const uint64_t *bcAllelePtr
                    const double *groupCount, const uint64_t *groupEntryPtr, const uint32_t *entryLocal, const double *rho, uint32_t nAlleles,
                    double alpha, double tol, int32_t maxIter, double *nOut, int32_t *itersOut, double *kernelMs);
 
+/* ---- UMI collapse of the per-barcode allele lists (analyzer --umi) ------------------------------------------
+ * Fragment f: row fragRow[f] < nRows of the per-barcode table, the strictly ascending allele list listAllele[listPtr[f] .. listPtr[f+1])
+ * (not empty, ids < nAlleles; listPtr may start anywhere: a slice of a larger table) and the UMI word fragUmi[f]: the code in bits 0-31
+ * (2 bits per base, A 0 C 1 G 2 T 3, first base most significant), the length 1 - 16 in bits 32-36, or all ones for "no UMI".
+ * Its gene is alleleGene[its smallest allele] < nGenes, its bucket (row, gene, length).  With mismatch = 1 a UMI u joins the neighbour v
+ * (same bucket, Hamming distance 1) with c(v) >= 2 c(u) - 1 and (c(v) > c(u), or c(v) == c(u) and v < u) that has the largest count,
+ * ties to the smallest code; root(u) follows these parents to the end.  mismatch = 0: root(u) = u.  A key = (bucket, root): one molecule
+ * with the intersection of its fragments' lists or, when that is empty, one molecule per distinct list among them; a fragment without a
+ * UMI is a molecule of its own.
+ * Outputs, sized by the caller: fragMol[nFrag]; *nMol <= nFrag molecules in no particular order with molRow, molFrags (fragments
+ * behind each), molListPtr[*nMol + 1] (starting at 0) into molList (at most listPtr[nFrag] - listPtr[0] entries); the dense tables
+ * frac[nRows * nAlleles] = sum over ascending n of (double)K(r, a, n) / (double)n and uniq = K(r, a, 1), K(r, a, n) = the row's molecules
+ * of n alleles that hold a.  stats may be NULL.  Negative codes: mismatch not 0 / 1, a row, allele, gene, UMI word or offset out of
+ * range, a list not ascending, nRows * nGenes >= 2^28 (the 64-bit sort key holds 28 bits of row and gene, 4 of length, 32 of code),
+ * nRows * nAlleles >= 2^40 or not fitting 64 bits beside the longest list's length (the table's sort key), 2^31 fragments, 2^32 entries. */
+typedef struct {
+  uint64_t distinct;   /* distinct (bucket, UMI) */
+  uint64_t keys;       /* distinct (bucket, root) */
+  uint64_t corrected;  /* distinct UMIs that joined a neighbour */
+  uint64_t split;      /* keys with an empty intersection */
+  uint64_t no_umi;     /* fragments without a UMI */
+  double kernel_ms;    /* device time from the first kernel to the last (the sizes read back in between included) */
+} t1k_umi_stats;
+int t1k_umi_collapse(t1k_ctx *ctx, uint32_t nFrag, const uint32_t *fragRow, const uint64_t *fragUmi, const uint64_t *listPtr, const uint32_t *listAllele,
+                     uint32_t nRows, const uint32_t *alleleGene, uint32_t nAlleles, uint32_t nGenes, int32_t mismatch, uint32_t *fragMol, uint32_t *nMol,
+                     uint32_t *molRow, uint32_t *molFrags, uint64_t *molListPtr, uint32_t *molList, double *frac, int32_t *uniq, t1k_umi_stats *stats);
+
 /* ---- profiling counters of the last t1k_assign_batch (algorithmic-traffic terms of SURVEY.md 8d) --------------- */
 typedef struct {
   uint64_t read_ends, lookups, postings, hits, groups, candidates, extended, near_best, dp_calls, rows, batches;

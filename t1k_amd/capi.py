@@ -45,6 +45,10 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class UmiStats(C.Structure):  # t1k_umi_stats
+    _fields_ = [(n, C.c_uint64) for n in ("distinct", "keys", "corrected", "split", "no_umi")] + [("kernel_ms", C.c_double)]
+
+
 OVERLAP_DTYPE = np.dtype([("seq_idx", "<i4"), ("read_start", "<i4"), ("read_end", "<i4"), ("seq_start", "<i4"),
                           ("seq_end", "<i4"), ("strand", "<i4"), ("match_cnt", "<i4"), ("left_clip", "<i4"),
                           ("right_clip", "<i4"), ("relaxed_match_cnt", "<i4"), ("similarity", "<f8")])
@@ -95,6 +99,8 @@ def lib():
     L.t1k_em_setup.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, ALLREDUCE_FN, vp]
     L.t1k_em_update.argtypes = [vp, vp, vp, vp, vp]
     L.t1k_barcode_em.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int32, vp, vp, C.POINTER(C.c_double)]
+    L.t1k_umi_collapse.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int32, vp, C.POINTER(C.c_uint32), vp, vp, vp, vp, vp, vp,
+                                   C.POINTER(UmiStats)]
     L.t1k_extract_batch.argtypes = [vp, C.c_uint32, vp, vp]
     L.t1k_extractor_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_stats_get.argtypes = [vp, C.POINTER(Stats)]
@@ -374,6 +380,51 @@ class Context:
             return rc
         self._check(rc, "t1k_barcode_em")
         return n, iters, ms.value
+
+    def umi_collapse(self, frag_row, frag_umi, list_ptr, list_allele, n_rows, allele_gene, n_genes, mismatch=1, raw=False):
+        """UMI collapse of per-barcode allele lists (t1k_umi_collapse).  frag_umi: code in bits 0-31, length in bits 32-36, all ones for
+        none; list_ptr may be a slice of a larger table's offsets (list_allele whole).  Returns a dict with the molecule table
+        canonicalised -- molecules sorted by (row, smallest fragment index), frag_mol renumbered to match: frag_mol, mol_row, mol_frags,
+        mol_list_ptr, mol_list, frac and uniq [n_rows, n_alleles], stats.  raw=True returns the status code instead of raising."""
+        fr = np.ascontiguousarray(frag_row, np.uint32)
+        fu = np.ascontiguousarray(frag_umi, np.uint64)
+        lp = np.ascontiguousarray(list_ptr, np.uint64)
+        la = np.ascontiguousarray(list_allele, np.uint32)
+        ag = np.ascontiguousarray(allele_gene, np.uint32)
+        nf, na = len(fr), len(ag)
+        if len(fu) != nf or len(lp) != nf + 1:
+            raise ValueError("umi_collapse: frag_row, frag_umi and list_ptr do not describe the same fragments")
+        # output room by the upper bounds: molecules <= fragments, their list entries <= the fragments' (an offset array that lies is the
+        # library's to reject: the room only has to be there when the offsets are sound)
+        ne = int(lp[-1]) - int(lp[0]) if nf and int(lp[-1]) >= int(lp[0]) else 0
+        ne = min(ne, len(la))
+        frag_mol = np.zeros(nf, np.uint32)
+        mol_row = np.zeros(nf, np.uint32)
+        mol_frags = np.zeros(nf, np.uint32)
+        mol_ptr = np.zeros(nf + 1, np.uint64)
+        mol_list = np.zeros(max(ne, 1), np.uint32)
+        frac = np.zeros((int(n_rows), na), np.float64)
+        uniq = np.zeros((int(n_rows), na), np.int32)
+        n_mol = C.c_uint32()
+        st = UmiStats()
+        rc = lib().t1k_umi_collapse(self.h, nf, _ptr(fr), _ptr(fu), _ptr(lp), _ptr(la), int(n_rows), _ptr(ag), na, int(n_genes), int(mismatch), _ptr(frag_mol), C.byref(n_mol),
+                                    _ptr(mol_row), _ptr(mol_frags), _ptr(mol_ptr), _ptr(mol_list), _ptr(frac), _ptr(uniq), C.byref(st))
+        if raw:
+            return rc
+        self._check(rc, "t1k_umi_collapse")
+        m = n_mol.value
+        mol_row, mol_frags, mol_ptr = mol_row[:m], mol_frags[:m], mol_ptr[:m + 1].astype(np.int64)
+        first = np.full(m, nf, np.int64)
+        np.minimum.at(first, frag_mol, np.arange(nf))
+        order = np.lexsort((first, mol_row))
+        rank = np.empty(m, np.uint32)
+        rank[order] = np.arange(m, dtype=np.uint32)
+        lens = np.diff(mol_ptr)[order]
+        new_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+        take = np.repeat(mol_ptr[:-1][order] - new_ptr[:-1].astype(np.int64), lens) + np.arange(int(lens.sum()))
+        return dict(frag_mol=rank[frag_mol], mol_row=mol_row[order], mol_frags=mol_frags[order], mol_list_ptr=new_ptr, mol_list=mol_list[take] if m else mol_list[:0],
+                    frac=frac, uniq=uniq,
+                    stats=dict(distinct=int(st.distinct), keys=int(st.keys), corrected=int(st.corrected), split=int(st.split), no_umi=int(st.no_umi), kernel_ms=float(st.kernel_ms)))
 
 
 class Readset:

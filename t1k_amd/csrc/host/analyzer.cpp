@@ -1,5 +1,6 @@
 // t1k_amd/csrc/host/analyzer.cpp -- t1k_analyzer_main(): the post-analysis stage (Analyzer.cpp:236-733 as run-t1k:438-449 starts it)
 // on top of the job layer: re-assignment to the selected alleles, novel variants, per-barcode summary.
+#include <numeric>
 #include "job_internal.h"
 
 extern "C" {
@@ -337,27 +338,31 @@ static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants 
   return T1K_OK;
 }
 
-// --barcodeEM: the lists BarcodeSummary counts, grouped per barcode, through t1k_barcode_em.  The summary loop hands every
-// counted fragment's kept list over in file order (bc = its row of the per-barcode table); finish() groups them per barcode (identical
-// sorted lists, first appearance first, host threads over barcodes), runs the EM and writes <prefix>_barcode_em.tsv.
-struct BarcodeEM {
-  std::vector<uint32_t> fragRow;      // counted fragment -> its barcode id (the summary loop), then its row of the table (run)
+// --barcodeEM and --umi (§11.2): the lists BarcodeSummary counts.  The summary loop hands every counted fragment's kept
+// list over in file order (bc = its row of the per-barcode table) and, under --umi, its UMI word.  runEM() groups the lists per barcode
+// (identical sorted lists, first appearance first, host threads over barcodes) and runs t1k_barcode_em; --umi sends the same lists
+// through t1k_umi_collapse and, with --barcodeEM, the molecules that come back through runEM() once more.
+struct BarcodeLists {
+  std::vector<uint32_t> fragRow;      // counted fragment -> its barcode id (the summary loop), then its row of the table
   std::vector<uint64_t> fragAt{0};    // counted fragment -> its sorted list in `lists`
   std::vector<uint32_t> lists;
+  std::vector<uint64_t> fragUmi;      // --umi: counted fragment -> its UMI word (t1k_umi_collapse)
   std::vector<uint32_t> scratch;
 
-  void add(int bc, const uint32_t *alleles, uint32_t k) {
+  bool add(int bc, const uint32_t *alleles, uint32_t k) {
     scratch.assign(alleles, alleles + k);
     std::sort(scratch.begin(), scratch.end());
     scratch.erase(std::unique(scratch.begin(), scratch.end()), scratch.end());
-    if (scratch.empty()) return;  // nothing kept: not counted
+    if (scratch.empty()) return false;  // nothing kept: not counted
     fragRow.push_back((uint32_t)bc);
     lists.insert(lists.end(), scratch.begin(), scratch.end());
     fragAt.push_back(lists.size());
+    return true;
   }
 
-  // rows x A expected counts (row-major), through the device
-  int run(t1k_job *job, uint32_t nRows, double alpha, std::vector<double> &out) {
+  // rows x A expected counts (row-major), through the device.  sortGroups: a row's groups in ascending lexicographic order of their lists
+  // instead of first appearance (molecules come in no particular order)
+  int runEM(t1k_job *job, uint32_t nRows, double alpha, std::vector<double> &out, bool sortGroups = false, const char *what = "barcode EM") {
     const double t0 = nowMs();
     const size_t A = job->ref.al.size();
     const size_t nF = fragRow.size();
@@ -412,6 +417,19 @@ struct BarcodeEM {
             }
           }
         }
+        if (sortGroups) {
+          std::vector<uint32_t> ord(firstOf.size());
+          std::iota(ord.begin(), ord.end(), 0u);
+          std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
+            const auto a = listOf(firstOf[x]), b = listOf(firstOf[y]);
+            return std::lexicographical_compare(a.first, a.first + a.second, b.first, b.first + b.second);
+          });
+          std::vector<uint32_t> fo(ord.size());
+          std::vector<double> ct(ord.size());
+          for (size_t g = 0; g < ord.size(); ++g) { fo[g] = firstOf[ord[g]]; ct[g] = w.count[ord[g]]; }
+          firstOf.swap(fo);
+          w.count.swap(ct);
+        }
         for (uint32_t i : firstOf) { auto l = listOf(i); w.U.insert(w.U.end(), l.first, l.first + l.second); }
         std::sort(w.U.begin(), w.U.end());
         w.U.erase(std::unique(w.U.begin(), w.U.end()), w.U.end());
@@ -455,12 +473,96 @@ struct BarcodeEM {
       int32_t mx = 0;
       double sum = 0;
       for (int32_t v : iters) { mx = std::max(mx, v); sum += v; }
-      fprintf(stderr, "[t1k analyzer] barcode EM: groups built in %.1f ms, t1k_barcode_em %.1f ms (kernel %.1f ms); %u barcodes, %zu groups, %zu entries; iterations max %d mean %.1f\n",
-              t1 - t0, t2 - t1, kernelMs, nRows, groupCount.size(), entryLocal.size(), mx, nRows ? sum / nRows : 0.0);
+      fprintf(stderr, "[t1k analyzer] %s: groups built in %.1f ms, t1k_barcode_em %.1f ms (kernel %.1f ms); %u barcodes, %zu groups, %zu entries; iterations max %d mean %.1f\n",
+              what, t1 - t0, t2 - t1, kernelMs, nRows, groupCount.size(), entryLocal.size(), mx, nRows ? sum / nRows : 0.0);
     }
     return T1K_OK;
   }
 };
+
+// --umi FILE: one record per candidate read, >name\nUMI as the extractors write it, read by the project's reader (names as the read
+// loader normalises them).  The analyzer's fragments are a subset of the records in the same relative order: take() is one forward merge.
+struct UmiFile {
+  ReadInput in;
+  size_t cursor = 0;
+
+  bool open(const std::string &path, int threads, std::string &err) {
+    if (!in.open({path}, {}, "", hostThreadsFor(threads), err)) return false;
+    const ReadInput::Side &s = in.side[0];
+    for (size_t i = 0; i < s.seqL.size(); ++i)
+      if (s.seqL[i] > 16) {
+        err = "--umi takes UMIs of up to 16 bases: record " + std::string(s.idP[i], s.idL[i]) + " of " + path + " has " + std::to_string(s.seqL[i]);
+        return false;
+      }
+    return true;
+  }
+  // 2 bits per base, first base most significant, the length above bit 32; all ones for a record that is not 1 - 16 of ACGT (an N, the
+  // extractors' missing_barcode)
+  static uint64_t word(const char *p, uint32_t n) {
+    if (n < 1 || n > 16) return ~0ull;
+    uint64_t code = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const char c = p[i];
+      const int b = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
+      if (b < 0) return ~0ull;
+      code = (code << 2) | (uint64_t)b;
+    }
+    return code | ((uint64_t)n << 32);
+  }
+  bool take(const char *id, size_t idLen, uint64_t &w) {
+    const ReadInput::Side &s = in.side[0];
+    for (; cursor < s.seqL.size(); ++cursor)
+      if (s.idL[cursor] == idLen && !memcmp(s.idP[cursor], id, idLen)) {
+        w = word(s.seqP[cursor], s.seqL[cursor]);
+        ++cursor;
+        return true;
+      }
+    return false;
+  }
+};
+
+struct UmiTables {
+  std::vector<double> frac;
+  std::vector<int32_t> uniq;
+  BarcodeLists molecules;  // the molecules as lists of their rows, for runEM()
+};
+
+// the counted fragments through t1k_umi_collapse: the molecule tables of nRows x A
+static int analyzerUmiCollapse(t1k_job *job, const BarcodeLists &L, uint32_t nRows, int mismatch, double msFile, double msMerge, UmiTables &T) {
+  const double t0 = nowMs();
+  const size_t A = job->ref.al.size(), nF = L.fragRow.size();
+  std::vector<uint32_t> alleleGene(A);
+  uint32_t nGenes = 0;
+  for (size_t a = 0; a < A; ++a) {
+    if (job->ref.al[a].gene < 0) return jobFail(job, T1K_ERR_INTERNAL, "analyzer: allele " + job->ref.al[a].name + " has no gene");
+    alleleGene[a] = (uint32_t)job->ref.al[a].gene;
+    nGenes = std::max(nGenes, alleleGene[a] + 1);
+  }
+  if (nF >= (1ull << 31)) return jobFail(job, T1K_ERR_CAPACITY, "analyzer: --umi takes up to 2^31 counted fragments");
+  // upper bounds: molecules <= fragments, their list entries <= the fragments'
+  std::vector<uint32_t> fragMol(nF), molRow(nF), molFrags(nF);
+  uint32_t nMol = 0;
+  BarcodeLists &M = T.molecules;
+  M.fragAt.assign(nF + 1, 0);
+  M.lists.resize(L.lists.size());
+  T.frac.assign((size_t)nRows * A, 0.0);
+  T.uniq.assign((size_t)nRows * A, 0);
+  t1k_umi_stats st;
+  const double t1 = nowMs();
+  const int rc = t1k_umi_collapse(job->ctx, (uint32_t)nF, L.fragRow.data(), L.fragUmi.data(), L.fragAt.data(), L.lists.data(), nRows, alleleGene.data(), (uint32_t)A, nGenes, mismatch,
+                                  fragMol.data(), &nMol, molRow.data(), molFrags.data(), M.fragAt.data(), M.lists.data(), T.frac.data(), T.uniq.data(), &st);
+  if (rc != T1K_OK) return jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(job->ctx));
+  const double t2 = nowMs();
+  M.fragAt.resize((size_t)nMol + 1);
+  M.lists.resize(M.fragAt[nMol]);
+  M.fragRow.assign(molRow.begin(), molRow.begin() + nMol);
+  const double t3 = nowMs();
+  if (getenv("T1K_DEBUG_PHASES"))
+    fprintf(stderr, "umi: %zu fragments, %llu distinct keys, %llu corrected UMIs, %u molecules, %llu split keys, %llu fragments without a UMI; host %.1f ms (UMI file %.1f, name merge %.1f, hand-over %.1f), t1k_umi_collapse %.1f ms, kernels %.1f ms\n",
+            nF, (unsigned long long)st.keys, (unsigned long long)st.corrected, nMol, (unsigned long long)st.split, (unsigned long long)st.no_umi,
+            msFile + msMerge + (t1 - t0) + (t3 - t2), msFile, msMerge, (t1 - t0) + (t3 - t2), t2 - t1, st.kernel_ms);
+  return T1K_OK;
+}
 
 static const char *kAnalyzerUsage =
     "./analyzer [OPTIONS]:   (MI355X build of the T1K post-analysis stage: re-assignment, novel variants, per-barcode summary)\n"
@@ -477,6 +579,9 @@ static const char *kAnalyzerUsage =
     "\t--barcode STRING: barcode file\n"
     "\t--barcodeEM: also write prefix_barcode_em.tsv, the alleles' expected fragment counts of an EM run per barcode (needs --barcode; or $T1K_BARCODE_EM=1 with --barcode)\n"
     "\t--barcodeEMPrior FLOAT: weight of the pooled allele abundances as a prior of the per-barcode EM (default: 0)\n"
+    "\t--umi FILE: UMI file (prefix_umi.fa of bam-extractor --UMI): also write prefix_barcode_umi.tsv, the table of prefix_barcode_expr.tsv counted in molecules\n"
+    "\t\tinstead of fragments, and with --barcodeEM prefix_barcode_umi_em.tsv (needs --barcode)\n"
+    "\t--umiMismatch INT: 1 joins a UMI to a neighbour at one mismatch that is at least twice as frequent, 0 keeps every UMI (default: 1)\n"
     "\t--relaxIntronAlign: allow one more mismatch in intronic alignment\n"
     "\t--alleleDigitUnits INT, --alleleDelimiter CHR: as in genotyper\n"
     "\t--varMaxGroup INT: the maximum variant group size to call novel variant. -1 for no limitation, 0 for no variant calling (default: 8)\n"
@@ -486,7 +591,8 @@ int t1k_analyzer_main(int argc, char **argv) {
   if (argc <= 1) { fprintf(stderr, "%s", kAnalyzerUsage); return 0; }  // Analyzer.cpp:241-245
   static struct option longOpts[] = {{"barcode", required_argument, 0, 10000}, {"relaxIntronAlign", no_argument, 0, 10004}, {"alleleDigitUnits", required_argument, 0, 10005},
                                      {"alleleDelimiter", required_argument, 0, 10006}, {"varMaxGroup", required_argument, 0, 10007}, {"device", required_argument, 0, 10010},
-                                     {"barcodeEM", no_argument, 0, 10011}, {"barcodeEMPrior", required_argument, 0, 10012}, {0, 0, 0, 0}};
+                                     {"barcodeEM", no_argument, 0, 10011}, {"barcodeEMPrior", required_argument, 0, 10012}, {"umi", required_argument, 0, 10013},
+                                     {"umiMismatch", required_argument, 0, 10014}, {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
@@ -495,7 +601,9 @@ int t1k_analyzer_main(int argc, char **argv) {
   int varMaxGroup = 8;  // Analyzer.cpp:251
   bool barcodeEM = false;
   double emPrior = 0;
-  const char *emPriorText = nullptr;
+  const char *emPriorText = nullptr, *umiMismatchText = nullptr;
+  std::string umiPath;
+  int umiMismatch = 1;
   optind = 1;
   int c, idx = 0;
   while ((c = getopt_long(argc, argv, "f:a:u:1:2:o:t:n:s:", longOpts, &idx)) != -1) {
@@ -517,6 +625,8 @@ int t1k_analyzer_main(int argc, char **argv) {
       case 10010: p.device = atoi(optarg); break;
       case 10011: barcodeEM = true; break;
       case 10012: emPriorText = optarg; break;
+      case 10013: umiPath = optarg; break;
+      case 10014: umiMismatchText = optarg; break;
       default: fprintf(stderr, "%s", kAnalyzerUsage); return EXIT_FAILURE;
     }
   }
@@ -529,6 +639,21 @@ int t1k_analyzer_main(int argc, char **argv) {
     char *end = nullptr;
     emPrior = strtod(emPriorText, &end);
     if (end == emPriorText || *end || !(emPrior >= 0) || !std::isfinite(emPrior)) { fprintf(stderr, "--barcodeEMPrior needs a number >= 0.\n"); return EXIT_FAILURE; }
+  }
+  if (!umiPath.empty() && barcode.empty()) { fprintf(stderr, "--umi needs --barcode.\n"); return EXIT_FAILURE; }
+  if (umiMismatchText) {
+    if (strcmp(umiMismatchText, "0") && strcmp(umiMismatchText, "1")) { fprintf(stderr, "--umiMismatch needs 0 or 1.\n"); return EXIT_FAILURE; }
+    umiMismatch = atoi(umiMismatchText);
+  }
+  const bool umi = !umiPath.empty();
+  std::unique_ptr<UmiFile> umiFile;
+  double msUmiHost = 0, msUmiMerge = 0;
+  if (umi) {  // mapped and checked before anything else runs
+    const double t0 = nowMs();
+    std::string err;
+    umiFile.reset(new UmiFile);
+    if (!umiFile->open(umiPath, p.threads, err)) { fprintf(stderr, "analyzer: %s\n", err.c_str()); return EXIT_FAILURE; }
+    msUmiHost += nowMs() - t0;
   }
   if (p.dev.max_assign_cnt == 0) p.dev.max_assign_cnt = -1;
   std::set<std::string> selected;
@@ -552,9 +677,12 @@ int t1k_analyzer_main(int argc, char **argv) {
       fprintf(fb, "#barcode\n");
       fclose(fb);
     }
-    if (barcodeEM) {
-      FILE *fe = fopen((prefix + "_barcode_em.tsv").c_str(), "w");
-      if (!fe) { fprintf(stderr, "analyzer: cannot write %s_barcode_em.tsv\n", prefix.c_str()); return EXIT_FAILURE; }
+    const std::pair<const char *, bool> extra[] = {{"_barcode_em.tsv", barcodeEM}, {"_barcode_umi.tsv", umi}, {"_barcode_umi_em.tsv", umi && barcodeEM}};
+    for (const auto &x : extra) {
+      if (!x.second) continue;
+      const char *name = x.first;
+      FILE *fe = fopen((prefix + name).c_str(), "w");
+      if (!fe) { fprintf(stderr, "analyzer: cannot write %s%s\n", prefix.c_str(), name); return EXIT_FAILURE; }
       fprintf(fe, "#barcode\n");
       fclose(fe);
     }
@@ -622,8 +750,9 @@ int t1k_analyzer_main(int argc, char **argv) {
     std::vector<uint32_t> cnt;
     std::vector<t1k_row_entry> rows;
     std::vector<uint8_t> keepFlag;
-    std::unique_ptr<BarcodeEM> em(barcodeEM ? new BarcodeEM : nullptr);
+    std::unique_ptr<BarcodeLists> em(barcodeEM || umi ? new BarcodeLists : nullptr);
     std::vector<uint32_t> emList;
+    std::vector<uint32_t> countedFrag;  // --umi: the counted fragments, for the name merge behind the loop
     for (uint32_t f0 = 0; f0 < F; f0 += step) {
       const uint32_t n = std::min(step, F - f0);
       cnt.resize(n);
@@ -652,7 +781,7 @@ int t1k_analyzer_main(int argc, char **argv) {
           if (em) {
             emList.clear();
             for (uint32_t j = 0; j < k; ++j) if (keepFlag[j]) emList.push_back((uint32_t)rows[q + j].allele_idx);
-            em->add(bcOf[f], emList.data(), (uint32_t)emList.size());
+            if (em->add(bcOf[f], emList.data(), (uint32_t)emList.size()) && umi) countedFrag.push_back(f);
           }
           for (uint32_t j = 0; j < k; ++j, ++q) {
             if (!keepFlag[j]) continue;
@@ -664,13 +793,28 @@ int t1k_analyzer_main(int argc, char **argv) {
         if (em) {
           emList.clear();
           for (uint32_t j = 0; j < k; ++j) emList.push_back((uint32_t)rows[q + j].allele_idx);
-          em->add(bcOf[f0 + i], emList.data(), k);
+          if (em->add(bcOf[f0 + i], emList.data(), k) && umi) countedFrag.push_back(f0 + i);
         }
         for (uint32_t j = 0; j < k; ++j, ++q) {
           slot.first[rows[q].allele_idx] += 1.0 / k;
           if (k == 1) ++slot.second[rows[q].allele_idx];
         }
       }
+    }
+    if (umi) {
+      // every counted fragment's UMI word: the record of the UMI file that carries its read's name, one forward merge
+      const double t0 = nowMs();
+      em->fragUmi.resize(countedFrag.size());
+      for (size_t i = 0; i < countedFrag.size(); ++i) {
+        const uint32_t r = in.frag[countedFrag[i]];
+        if (in.noIds || !umiFile->take(in.side[0].idP[r], in.side[0].idL[r], em->fragUmi[i])) {
+          fprintf(stderr, "analyzer: read %s has no record in %s (the UMI file lists the reads in the order of the read files)\n",
+                  in.noIds ? "(unnamed)" : std::string(in.side[0].idP[r], in.side[0].idL[r]).c_str(), umiPath.c_str());
+          t1k_job_destroy(job);
+          return EXIT_FAILURE;
+        }
+      }
+      msUmiMerge = nowMs() - t0;
     }
     FILE *fp = fopen((prefix + "_barcode_expr.tsv").c_str(), "w");  // BarcodeSummary::Output (59-80)
     if (!fp) { fprintf(stderr, "analyzer: cannot write %s_barcode_expr.tsv\n", prefix.c_str()); t1k_job_destroy(job); return EXIT_FAILURE; }
@@ -690,10 +834,11 @@ int t1k_analyzer_main(int argc, char **argv) {
       std::unordered_map<int, uint32_t> rowOf;
       for (auto &kv : table) rowOf.emplace(kv.first, (uint32_t)rowOf.size());
       for (uint32_t &r : em->fragRow) r = rowOf.at((int)r);
-      std::vector<double> est;
-      if (em->run(job, (uint32_t)table.size(), emPrior, est) != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
-      FILE *fe = fopen((prefix + "_barcode_em.tsv").c_str(), "w");
-      if (!fe) { fprintf(stderr, "analyzer: cannot write %s_barcode_em.tsv\n", prefix.c_str()); t1k_job_destroy(job); return EXIT_FAILURE; }
+    }
+    // <prefix><name>: a table of expected counts in the rows of _barcode_expr.tsv
+    auto writeEstimates = [&](const char *name, const std::vector<double> &est) -> bool {
+      FILE *fe = fopen((prefix + name).c_str(), "w");
+      if (!fe) { fprintf(stderr, "analyzer: cannot write %s%s\n", prefix.c_str(), name); return false; }
       fprintf(fe, "#barcode");
       for (size_t a = 0; a < A; ++a) fprintf(fe, "\t%s", job->ref.al[a].name.c_str());
       fprintf(fe, "\n");
@@ -705,6 +850,36 @@ int t1k_analyzer_main(int argc, char **argv) {
         ++r;
       }
       fclose(fe);
+      return true;
+    };
+    if (barcodeEM) {
+      std::vector<double> est;
+      if (em->runEM(job, (uint32_t)table.size(), emPrior, est) != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
+      if (!writeEstimates("_barcode_em.tsv", est)) { t1k_job_destroy(job); return EXIT_FAILURE; }
+    }
+    if (umi) {
+      UmiTables T;
+      if (analyzerUmiCollapse(job, *em, (uint32_t)table.size(), umiMismatch, msUmiHost, msUmiMerge, T) != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
+      FILE *fu = fopen((prefix + "_barcode_umi.tsv").c_str(), "w");  // the layout of _barcode_expr.tsv
+      if (!fu) { fprintf(stderr, "analyzer: cannot write %s_barcode_umi.tsv\n", prefix.c_str()); t1k_job_destroy(job); return EXIT_FAILURE; }
+      fprintf(fu, "#barcode");
+      for (size_t a = 0; a < A; ++a) fprintf(fu, "\t%s", job->ref.al[a].name.c_str());
+      for (size_t a = 0; a < A; ++a) fprintf(fu, "\t%s_uniq", job->ref.al[a].name.c_str());
+      fprintf(fu, "\n");
+      size_t r = 0;
+      for (auto &kv : table) {
+        fprintf(fu, "%s", names[kv.first].c_str());
+        for (size_t a = 0; a < A; ++a) fprintf(fu, "\t%lf", T.frac[r * A + a]);
+        for (size_t a = 0; a < A; ++a) fprintf(fu, "\t%d", T.uniq[r * A + a]);
+        fprintf(fu, "\n");
+        ++r;
+      }
+      fclose(fu);
+      if (barcodeEM) {
+        std::vector<double> est;
+        if (T.molecules.runEM(job, (uint32_t)table.size(), emPrior, est, true, "barcode EM on molecules") != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
+        if (!writeEstimates("_barcode_umi_em.tsv", est)) { t1k_job_destroy(job); return EXIT_FAILURE; }
+      }
     }
   }
   logLine("Post analysis finishes.");
