@@ -346,6 +346,31 @@ int t1k_umi_collapse(t1k_ctx *ctx, uint32_t nFrag, const uint32_t *fragRow, cons
                      uint32_t nRows, const uint32_t *alleleGene, uint32_t nAlleles, uint32_t nGenes, int32_t mismatch, uint32_t *fragMol, uint32_t *nMol,
                      uint32_t *molRow, uint32_t *molFrags, uint64_t *molListPtr, uint32_t *molList, double *frac, int32_t *uniq, t1k_umi_stats *stats);
 
+/* ---- per-base pileup of alignments onto alleles (analyzer --pileup) ---------------------------------------------
+ * A table of 14 int32 counters per allele position lives on the context between t1k_pileup_begin and t1k_pileup_end.  It is
+ * COUNTER-MAJOR: with T = alleleOff[nAlleles], counter c of position p of allele a is counts[c * T + alleleOff[a] + p]; c = 0 .. 6 are
+ * A C G T N del ins weighted by w_all, c = 7 .. 13 the same seven weighted by w_uniq.  alleleOff[0] = 0, ascending.
+ * One record = one alignment: its edit string ops[ops_at .. ops_at + n_ops) (0 match, 1 mismatch, 2 insert, 3 delete) is walked from
+ * allele position seq_start and from text[read_at] (the first base of the read window, strand-corrected; a byte that is not A/C/G/T
+ * counts as N).  Ops 0 and 1 book the read base at the allele position and advance both; 3 books del and advances the allele; 2 books
+ * ins at the allele position consumed last before it (seq_start if none yet; clamped to the allele's last position) and advances the
+ * read.  Every booking adds w_all to the first seven counters' cell and w_uniq (<= w_all) to the second seven's.
+ * t1k_pileup_add may be called any number of times; text / ops are the call's own.  It books nothing unless the whole call is sound:
+ * T1K_ERR_ARG for an allele >= nAlleles, w_uniq > w_all, an op outside 0 .. 3, a walk that leaves the allele, `text` or `ops`;
+ * T1K_ERR_CAPACITY when the bookings on one allele (the sum of w_all * n_ops over the table's life) could carry a counter past
+ * 2^31 - 1; T1K_ERR_STATE for add / get / end without begin, or begin while a table is open.  kernelMs (may be NULL): device time of
+ * the call's kernels.  t1k_pileup_get copies the 14 * T counters out; the table stays open. */
+typedef struct {
+  uint32_t allele, seq_start;
+  uint64_t read_at, ops_at;
+  uint32_t n_ops, w_all, w_uniq, reserved;
+} t1k_pileup_aln;  /* 40 bytes */
+int t1k_pileup_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff /* [nAlleles + 1] */);
+int t1k_pileup_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const char *text, uint64_t textBytes, const int8_t *ops, uint64_t opsBytes,
+                   double *kernelMs);
+int t1k_pileup_get(t1k_ctx *ctx, int32_t *counts /* [14 * alleleOff[nAlleles]] */);
+int t1k_pileup_end(t1k_ctx *ctx);
+
 /* ---- profiling counters of the last t1k_assign_batch (algorithmic-traffic terms of SURVEY.md 8d) --------------- */
 typedef struct {
   uint64_t read_ends, lookups, postings, hits, groups, candidates, extended, near_best, dp_calls, rows, batches;

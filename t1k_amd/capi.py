@@ -62,6 +62,12 @@ VARIANT_DTYPE = np.dtype([("allele_idx", "<i4"), ("ref_pos", "<i4"), ("exon_pos"
                           ("output_group", "<i4"), ("_pad2", "<i4"), ("var_support", "<f8"), ("all_support", "<f8"), ("var_uniq_support", "<f8")])
 assert FRAG_ASG_DTYPE.itemsize == 136 and VARIANT_DTYPE.itemsize == 56
 
+# t1k_pileup_aln (per-base pileup) and the names of the 14 counter planes of its table
+PILEUP_ALN_DTYPE = np.dtype([("allele", "<u4"), ("seq_start", "<u4"), ("read_at", "<u8"), ("ops_at", "<u8"), ("n_ops", "<u4"), ("w_all", "<u4"), ("w_uniq", "<u4"),
+                             ("reserved", "<u4")])
+PILEUP_COUNTERS = ("A", "C", "G", "T", "N", "del", "ins", "A_uniq", "C_uniq", "G_uniq", "T_uniq", "N_uniq", "del_uniq", "ins_uniq")
+assert PILEUP_ALN_DTYPE.itemsize == 40
+
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_void_p)
 
 _lib = None
@@ -101,6 +107,10 @@ def lib():
     L.t1k_barcode_em.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int32, vp, vp, C.POINTER(C.c_double)]
     L.t1k_umi_collapse.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int32, vp, C.POINTER(C.c_uint32), vp, vp, vp, vp, vp, vp,
                                    C.POINTER(UmiStats)]
+    L.t1k_pileup_begin.argtypes = [vp, C.c_uint32, vp]
+    L.t1k_pileup_add.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_double)]
+    L.t1k_pileup_get.argtypes = [vp, vp]
+    L.t1k_pileup_end.argtypes = [vp]
     L.t1k_extract_batch.argtypes = [vp, C.c_uint32, vp, vp]
     L.t1k_extractor_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_stats_get.argtypes = [vp, C.POINTER(Stats)]
@@ -425,6 +435,52 @@ class Context:
         return dict(frag_mol=rank[frag_mol], mol_row=mol_row[order], mol_frags=mol_frags[order], mol_list_ptr=new_ptr, mol_list=mol_list[take] if m else mol_list[:0],
                     frac=frac, uniq=uniq,
                     stats=dict(distinct=int(st.distinct), keys=int(st.keys), corrected=int(st.corrected), split=int(st.split), no_umi=int(st.no_umi), kernel_ms=float(st.kernel_ms)))
+
+    # per-base pileup (t1k_pileup_begin / _add / _get / _end); raw=True returns the status code instead of raising
+    def pileup_begin(self, allele_off, raw=False):
+        off = np.ascontiguousarray(allele_off, np.uint64)
+        rc = lib().t1k_pileup_begin(self.h, max(len(off) - 1, 0), _ptr(off))
+        if rc == 0:
+            self._pileup_total = int(off[-1])
+        if raw:
+            return rc
+        self._check(rc, "t1k_pileup_begin")
+
+    def pileup_add(self, aln, text, ops, raw=False):
+        """aln: PILEUP_ALN_DTYPE records; text: bytes (or uint8 array) of strand-corrected read bases; ops: int8 edit columns.  Returns the
+        kernels' device time in ms"""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+        o = np.ascontiguousarray(ops, np.int8)
+        ms = C.c_double()
+        rc = lib().t1k_pileup_add(self.h, _ptr(a), len(a), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
+        if raw:
+            return rc
+        self._check(rc, "t1k_pileup_add")
+        return ms.value
+
+    def pileup_get(self):
+        """the table as int32 [14, positions]: row c = counter PILEUP_COUNTERS[c], column alleleOff[a] + p"""
+        counts = np.zeros((14, getattr(self, "_pileup_total", 0)), np.int32)
+        self._check(lib().t1k_pileup_get(self.h, _ptr(counts)), "t1k_pileup_get")
+        return counts
+
+    def pileup_end(self, raw=False):
+        rc = lib().t1k_pileup_end(self.h)
+        if raw:
+            return rc
+        self._check(rc, "t1k_pileup_end")
+
+    def pileup(self, allele_off, aln, text, ops, cuts=()):
+        """begin, add (the records split at the indices `cuts` into several calls), get, end: the table and the kernels' ms"""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        self.pileup_begin(allele_off)
+        try:
+            edges = [0] + [int(c) for c in cuts] + [len(a)]
+            ms = sum(self.pileup_add(a[lo:hi], text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
+            return self.pileup_get(), ms
+        finally:
+            self.pileup_end()
 
 
 class Readset:

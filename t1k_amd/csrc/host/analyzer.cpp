@@ -23,13 +23,28 @@ extern "C" {
 //       ReadAssignmentToFragmentAssignment's per-allele choice again (host/variants.cpp) -- the device rows keep the fragment's window only;
 //   (3) SeqSet::AddFragmentAlignmentInfo (611-668): one global alignment per distinct (read-end, overlap) on the GPU (t1k_align_batch);
 //   (4) VariantCaller::ComputeVariant on the host (host/variants.cpp).
+// analyzerAlignAssignments runs (1) - (3), analyzerCallVariants (4) behind it.
 struct AnalyzerVariants {
   std::vector<uint64_t> asgPtr;             // fragment -> its assignments
   std::vector<t1k_frag_assignment> asg;
   std::vector<int8_t> ops;
+  std::vector<double> abundance;            // the alleles' abundances after (1)
   std::unique_ptr<VariantCaller> vc;
   int emIterations = 0;
+  // T1K_DEBUG_PHASES: what (1) - (3) took
+  double msRowsEM = 0, msAssign = 0, msDetails = 0, msAlign = 0;
+  uint64_t nEnds = 0, nJobs = 0, nFast = 0;
 };
+
+// --pileup: the alignments of (3) booked per allele position by t1k_pileup_add, piece by piece, on the context of the
+// variant pass; what comes back is the counter-major table of t1k_pileup_get
+struct AnalyzerPileup {
+  std::vector<uint64_t> off;       // allele -> its first position in a plane; off[A] = positions per plane
+  std::vector<int32_t> counts;
+  uint64_t nAln = 0, nAsg = 0, nCols = 0;  // distinct alignments walked, assignments' overlaps behind them, columns booked (weights counted)
+  double msCalls = 0, msKernels = 0, msDownload = 0;
+};
+static const char *kPileupHeader = "#allele\tpos\texon_pos\tref\tA\tC\tG\tT\tN\tdel\tins\tA_uniq\tC_uniq\tG_uniq\tT_uniq\tN_uniq\tdel_uniq\tins_uniq\n";
 
 // every fragment's raw row (the reference's list order): cnt[f] entries at rows[rowAt[f]]
 static int analyzerRows(t1k_job *job, std::vector<uint32_t> &cnt, std::vector<uint64_t> &rowAt, std::vector<t1k_row_entry> &rows) {
@@ -81,10 +96,11 @@ static int analyzerPooledEM(t1k_job *job, const std::vector<uint32_t> &cnt, cons
   return T1K_OK;
 }
 
-static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants &V) {
+// steps (1) - (3): V.asgPtr / V.asg / V.ops and V.abundance; with `pile`, every piece's alignments go through t1k_pileup_add as well
+static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerPileup *pile) {
   const double tv0 = nowMs();
-  double msAssign = 0, msDetails = 0, msAlign = 0;
-  uint64_t nEnds = 0, nJobs = 0, nFast = 0;
+  double &msAssign = V.msAssign, &msDetails = V.msDetails, &msAlign = V.msAlign;
+  uint64_t &nEnds = V.nEnds, &nJobs = V.nJobs, &nFast = V.nFast;
   const ReadInput &in = *job->in;
   const RefSet &R = job->ref;
   const uint32_t F = (uint32_t)in.nFrag();
@@ -96,9 +112,9 @@ static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants 
   if ((rc = analyzerRows(job, cnt, rowAt, rows)) != T1K_OK) return rc;
   // (1) the analyzer's EM
   if ((rc = analyzerPooledEM(job, cnt, rowAt, rows, &V.emIterations)) != T1K_OK) return rc;
-  std::vector<double> abundance(R.al.size());
-  for (size_t a = 0; a < R.al.size(); ++a) abundance[a] = R.al[a].abundance;
-  const double tv1 = nowMs();
+  V.abundance.resize(R.al.size());
+  for (size_t a = 0; a < R.al.size(); ++a) V.abundance[a] = R.al[a].abundance;
+  V.msRowsEM = nowMs() - tv0;
   // (2) + (3)
   t1k_ctx *vctx = nullptr;
   if ((rc = t1k_ctx_create(job->prm.device, &job->prm.dev, &vctx)) != T1K_OK) { if (vctx) t1k_ctx_destroy(vctx); return jobFail(job, rc, "analyzer: cannot create the context of the variant pass"); }
@@ -110,6 +126,7 @@ static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants 
   if (refOff.back() >= (1ull << 32)) return jobFail(job, T1K_ERR_CAPACITY, "analyzer: the selected alleles hold more than 4 G bases");
   refText.reserve(refOff.back());
   for (const std::string &sq : R.seqs) refText += sq;
+  if (pile && (rc = t1k_pileup_begin(vctx, (uint32_t)R.seqs.size(), refOff.data())) != T1K_OK) return jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(vctx));
   V.asgPtr.assign(F + 1, 0);
   V.asg.resize(rows.size());
   for (uint32_t f = 0; f < F; ++f) V.asgPtr[f + 1] = V.asgPtr[f] + (job->fragAssigned[f] ? cnt[f] : 0);
@@ -287,6 +304,7 @@ static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants 
         for (uint32_t i = 0; i < n; ++i) { nOpsOfJob[slow[j0 + i]] = nOps[i]; slowOff[j0 + i] = oOff[i]; slowCall[j0 + i] = (uint32_t)(slowBuf.size() - 1); }
       }
       // every job's place in the store (job order, as before), then the strings, by the host threads
+      const uint64_t pieceOps0 = V.ops.size();
       {
         uint64_t at = V.ops.size();
         for (size_t j = 0; j < nJ; ++j) { if (fast[j]) nOpsOfJob[j] = jTL[j]; opsAtOfJob[j] = at; at += nOpsOfJob[j]; }
@@ -315,9 +333,59 @@ static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants 
         if (a.has_mate_pair) { a.ops2 = opsAtOfJob[j2]; a.n_ops2 = nOpsOfJob[j2]; }
       }
       msAlign += nowMs() - tc;
+      if (pile && nJ) {
+        // one record per alignment job; its weights = the assignments that point at it, and those of them whose fragment keeps one assignment
+        const double tp = nowMs();
+        std::vector<t1k_pileup_aln> recs(nJ);
+        for (size_t j = 0; j < nJ; ++j) {
+          const t1k_overlap &o = lists[listAt[jobs[j].end] + jobs[j].idx];
+          recs[j] = t1k_pileup_aln{(uint32_t)o.seq_idx, (uint32_t)o.seq_start, jP[j], opsAtOfJob[j] - pieceOps0, nOpsOfJob[j], 0, 0, 0};
+        }
+        for (uint32_t f = f0; f < f1; ++f) {
+          const bool one = V.asgPtr[f + 1] - V.asgPtr[f] == 1;
+          for (uint64_t q = V.asgPtr[f]; q < V.asgPtr[f + 1]; ++q) {
+            const t1k_frag_assignment &a = V.asg[q];
+            if (a.o1.seq_idx != a.allele_idx || (a.has_mate_pair && a.o2.seq_idx != a.allele_idx))
+              return jobFail(job, T1K_ERR_INTERNAL, "analyzer: an assignment's overlap lies on another allele than the assignment");
+            for (int m = 0; m < 2; ++m) {
+              const int64_t j = jobOfAsg[m][q - q0];
+              if (j < 0) continue;
+              ++recs[j].w_all;
+              if (one) ++recs[j].w_uniq;
+              ++pile->nAsg;
+              pile->nCols += nOpsOfJob[j];
+            }
+          }
+        }
+        double kernelMs = 0;
+        if ((rc = t1k_pileup_add(vctx, recs.data(), (uint32_t)nJ, pat.data(), pat.size(), V.ops.data() + pieceOps0, V.ops.size() - pieceOps0, &kernelMs)) != T1K_OK)
+          return jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(vctx));
+        pile->nAln += nJ;
+        pile->msKernels += kernelMs;
+        pile->msCalls += nowMs() - tp;
+      }
     }
     f0 = f1;
   }
+  if (pile) {
+    const double tp = nowMs();
+    pile->off = refOff;
+    pile->counts.assign((size_t)14 * refOff.back(), 0);
+    if ((rc = t1k_pileup_get(vctx, pile->counts.data())) != T1K_OK || (rc = t1k_pileup_end(vctx)) != T1K_OK) return jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(vctx));
+    pile->msDownload = nowMs() - tp;
+  }
+  return T1K_OK;
+}
+
+static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants &V, AnalyzerPileup *pile) {
+  const double tv0 = nowMs();
+  int rc;
+  if ((rc = analyzerAlignAssignments(job, V, pile)) != T1K_OK) return rc;
+  const ReadInput &in = *job->in;
+  const RefSet &R = job->ref;
+  const uint32_t F = (uint32_t)in.nFrag();
+  const bool paired = in.paired;
+  auto readOf = [&](uint32_t f, int m) { const uint32_t r = in.frag[f]; return std::pair<const char *, uint32_t>(in.side[m].seqP[r], in.side[m].seqL[r]); };
   const double tv2 = nowMs();
   // (4)
   std::vector<VariantCaller::Fragment> frags(F);
@@ -329,13 +397,49 @@ static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants 
     fr.r1 = a.first; fr.l1 = a.second;
     if (paired) { auto b = readOf(f, 1); fr.r2 = b.first; fr.l2 = b.second; }
   }
-  V.vc.reset(new VariantCaller(R, abundance, varMaxGroup));
+  V.vc.reset(new VariantCaller(R, V.abundance, varMaxGroup));
   V.vc->compute(frags, V.ops.data());
   if (getenv("T1K_DEBUG_PHASES"))
     fprintf(stderr, "[t1k analyzer] variant pass: rows + EM %.1f ms; %llu distinct read-ends re-assigned in %.1f ms, overlaps chosen in %.1f ms, %llu alignments (%llu of them on the host: equal lengths, at most two mismatches) in %.1f ms; "
-                    "VariantCaller %.1f ms (%zu assignments, %zu variants); %.1f ms in all\n", tv1 - tv0, (unsigned long long)nEnds, msAssign, msDetails, (unsigned long long)nJobs, (unsigned long long)nFast, msAlign,
+                    "VariantCaller %.1f ms (%zu assignments, %zu variants); %.1f ms in all\n", V.msRowsEM, (unsigned long long)V.nEnds, V.msAssign, V.msDetails, (unsigned long long)V.nJobs, (unsigned long long)V.nFast, V.msAlign,
             nowMs() - tv2, V.asg.size(), V.vc->variants.size(), nowMs() - tv0);
   return T1K_OK;
+}
+
+// <prefix>_allele_pileup.tsv: one line per base of every selected allele, in job->ref.al order.  pile == NULL: the header alone
+static bool analyzerWritePileup(t1k_job *job, const std::string &prefix, AnalyzerPileup *pile) {
+  const double t0 = nowMs();
+  FILE *fp = fopen((prefix + "_allele_pileup.tsv").c_str(), "w");
+  if (!fp) { fprintf(stderr, "analyzer: cannot write %s_allele_pileup.tsv\n", prefix.c_str()); return false; }
+  fputs(kPileupHeader, fp);
+  if (pile) {
+    const RefSet &R = job->ref;
+    const uint64_t T = pile->off.back();
+    std::string out;
+    char num[32];
+    for (size_t a = 0; a < R.seqs.size(); ++a) {
+      const std::string &sq = R.seqs[a];
+      int exonic = 0;  // exonic bases in front of the position (SeqSet::GetExonicPosition)
+      for (size_t pos = 0; pos < sq.size(); ++pos) {
+        out += R.al[a].name;
+        snprintf(num, sizeof num, "\t%zu\t", pos + 1);
+        out += num;
+        if (R.exon[a][pos]) { snprintf(num, sizeof num, "%d", ++exonic); out += num; } else out += '.';
+        out += '\t';
+        out += sq[pos];
+        for (int c = 0; c < 14; ++c) { snprintf(num, sizeof num, "\t%d", pile->counts[(size_t)c * T + pile->off[a] + pos]); out += num; }
+        out += '\n';
+        if (out.size() >= (1u << 20)) { fwrite(out.data(), 1, out.size(), fp); out.clear(); }
+      }
+    }
+    fwrite(out.data(), 1, out.size(), fp);
+  }
+  fclose(fp);
+  if (pile && getenv("T1K_DEBUG_PHASES"))
+    fprintf(stderr, "pileup: %llu alignments walked, %llu assignments behind them, %llu columns booked; upload %.1f ms, kernels %.1f ms, download + write %.1f ms\n",
+            (unsigned long long)pile->nAln, (unsigned long long)pile->nAsg, (unsigned long long)pile->nCols, std::max(0.0, pile->msCalls - pile->msKernels), pile->msKernels,
+            pile->msDownload + (nowMs() - t0));
+  return true;
 }
 
 // --barcodeEM and --umi (§11.2): the lists BarcodeSummary counts.  The summary loop hands every counted fragment's kept
@@ -582,6 +686,8 @@ static const char *kAnalyzerUsage =
     "\t--umi FILE: UMI file (prefix_umi.fa of bam-extractor --UMI): also write prefix_barcode_umi.tsv, the table of prefix_barcode_expr.tsv counted in molecules\n"
     "\t\tinstead of fragments, and with --barcodeEM prefix_barcode_umi_em.tsv (needs --barcode)\n"
     "\t--umiMismatch INT: 1 joins a UMI to a neighbour at one mismatch that is at least twice as frequent, 0 keeps every UMI (default: 1)\n"
+    "\t--pileup: also write prefix_allele_pileup.tsv, per base of every selected allele the read bases, deletions and inserted bases of the alignments\n"
+    "\t\tthe variant pass holds, over all assignments and over those of fragments with one assignment (_uniq)\n"
     "\t--relaxIntronAlign: allow one more mismatch in intronic alignment\n"
     "\t--alleleDigitUnits INT, --alleleDelimiter CHR: as in genotyper\n"
     "\t--varMaxGroup INT: the maximum variant group size to call novel variant. -1 for no limitation, 0 for no variant calling (default: 8)\n"
@@ -592,14 +698,14 @@ int t1k_analyzer_main(int argc, char **argv) {
   static struct option longOpts[] = {{"barcode", required_argument, 0, 10000}, {"relaxIntronAlign", no_argument, 0, 10004}, {"alleleDigitUnits", required_argument, 0, 10005},
                                      {"alleleDelimiter", required_argument, 0, 10006}, {"varMaxGroup", required_argument, 0, 10007}, {"device", required_argument, 0, 10010},
                                      {"barcodeEM", no_argument, 0, 10011}, {"barcodeEMPrior", required_argument, 0, 10012}, {"umi", required_argument, 0, 10013},
-                                     {"umiMismatch", required_argument, 0, 10014}, {0, 0, 0, 0}};
+                                     {"umiMismatch", required_argument, 0, 10014}, {"pileup", no_argument, 0, 10015}, {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
   std::string refFile, alleleFile, prefix = "t1k", barcode;
   std::vector<const char *> f1, f2, single;
   int varMaxGroup = 8;  // Analyzer.cpp:251
-  bool barcodeEM = false;
+  bool barcodeEM = false, pileup = false;
   double emPrior = 0;
   const char *emPriorText = nullptr, *umiMismatchText = nullptr;
   std::string umiPath;
@@ -627,6 +733,7 @@ int t1k_analyzer_main(int argc, char **argv) {
       case 10012: emPriorText = optarg; break;
       case 10013: umiPath = optarg; break;
       case 10014: umiMismatchText = optarg; break;
+      case 10015: pileup = true; break;
       default: fprintf(stderr, "%s", kAnalyzerUsage); return EXIT_FAILURE;
     }
   }
@@ -686,6 +793,7 @@ int t1k_analyzer_main(int argc, char **argv) {
       fprintf(fe, "#barcode\n");
       fclose(fe);
     }
+    if (pileup && !analyzerWritePileup(nullptr, prefix, nullptr)) return EXIT_FAILURE;
     logLine("Post analysis finishes.");
     return 0;
   }
@@ -712,10 +820,16 @@ int t1k_analyzer_main(int argc, char **argv) {
   for (uint32_t f = 0; f < F; ++f) nAssigned += job->fragAssigned[f] ? 1 : 0;
   logLine("Finish read fragment assignments. %d read fragments can be assigned.", (int)nAssigned);
   AnalyzerVariants V;
+  std::unique_ptr<AnalyzerPileup> pile(pileup ? new AnalyzerPileup : nullptr);
   if (varMaxGroup != 0) {  // (0: VariantCaller::ComputeVariant returns before it looks at a read, VariantCaller.hpp:980-981)
-    rc = analyzerCallVariants(job, varMaxGroup, V);
+    rc = analyzerCallVariants(job, varMaxGroup, V, pile.get());
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
     logLine("Finish allele quantification in %d EM iterations.", V.emIterations);
+  } else if (pileup) {
+    // no variant is called, but the pileup is of the alignments of steps (1) - (3): they run, VariantCaller does not (V.vc stays empty: the
+    // VCF is the empty file and the per-barcode table counts the raw lists)
+    rc = analyzerAlignAssignments(job, V, pile.get());
+    if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
   } else if (barcodeEM && emPrior > 0) {
     // the per-barcode EM's prior is the pooled EM's abundances: step (1) of the variant pass on its own (its outputs are not written)
     std::vector<uint32_t> cnt;
@@ -731,6 +845,10 @@ int t1k_analyzer_main(int argc, char **argv) {
     if (!fp) { fprintf(stderr, "analyzer: cannot write %s_allele.vcf\n", prefix.c_str()); t1k_job_destroy(job); return EXIT_FAILURE; }
     if (V.vc) { const std::string text = V.vc->vcfText(); fwrite(text.data(), 1, text.size(), fp); }
     fclose(fp);
+  }
+  if (pile) {
+    if (!analyzerWritePileup(job, prefix, pile.get())) { t1k_job_destroy(job); return EXIT_FAILURE; }
+    pile.reset();
   }
   if (in.hasBarcode) {
     // barcode ids in order of first appearance over ALL loaded fragments (Analyzer.cpp:380-392), counts in fragment order

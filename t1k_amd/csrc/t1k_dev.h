@@ -832,6 +832,11 @@ struct t1k_ctx {
   T1kDevBuf bAlign[12];
   // candidate extraction (t1k_extract.hip): bAlign-independent scratch [good flags | error word | statistics]
   T1kDevBuf bExtract;
+  // per-base pileup (t1k_pileup.hip): the counter-major table of an open t1k_pileup_begin .. _end, the staging block of one _add
+  // call, and per allele the bookings it may have received so far (sum of w_all * n_ops: the bound behind T1K_ERR_CAPACITY)
+  T1kDevBuf bPileup, bPileupIn;
+  bool pileupOpen = false;
+  std::vector<uint64_t> pileupOff, pileupLoad;
   t1k_stats stats{};
 };
 
