@@ -371,6 +371,29 @@ int t1k_pileup_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const ch
 int t1k_pileup_get(t1k_ctx *ctx, int32_t *counts /* [14 * alleleOff[nAlleles]] */);
 int t1k_pileup_end(t1k_ctx *ctx);
 
+/* ---- per-barcode pileup at sites (analyzer --barcodePileup) -------------------------------------------------------
+ * What t1k_pileup_* counts, split by barcode and restricted to nSites sites (siteAllele[s], sitePos[s]): strictly ascending by
+ * (allele, pos), pos 0-based and < the allele's length (else T1K_ERR_ARG).  The table is sparse: a list of (key, count) runs,
+ * key = ((barcode * nSites + site) * 7 + plane) * 2 + (1 - uniq), plane = 0 .. 6 for A C G T N del ins, ascending by key, only cells
+ * that received a booking.  A uniq booking is stored once, under uniq = 1 (the even key): the reader adds the even run of a cell to its
+ * plain counter as well (plain = even + odd, _uniq = even).  T1K_ERR_CAPACITY from _begin if nBarcodes > 2^31 or nBarcodes * nSites * 14
+ * does not fit the key (2^63); nSites = 0 is legal (the table stays empty).
+ * t1k_sitepile_add: records as for t1k_pileup_add (w_all / w_uniq are ignored); record i books once per entry of
+ * book[bookPtr[i] .. bookPtr[i + 1]), an entry being barcode << 1 | uniq.  Nothing is emitted unless the whole call is sound:
+ * T1K_ERR_ARG for an allele >= nAlleles, a barcode >= nBarcodes, a bookPtr that decreases, an op outside 0 .. 3, a walk that leaves its
+ * allele, `text` or `ops`; T1K_ERR_CAPACITY when the table and the call's keys exceed 2^31 entries or a counter would pass 2^31 - 1
+ * (the table is as before the call); T1K_ERR_STATE for add / get / stats / end without begin, or begin while a table is open.
+ * Pending keys are folded into runs whenever they reach 2^28 (env T1K_SITEPILE_PENDING) and at _get.
+ * t1k_sitepile_get: *nRuns = the runs; with keys and counts given (cap >= *nRuns entries each) they are copied out -- a size query
+ * (keys = NULL) followed by a fill.  The table stays open.  t1k_sitepile_stats: keys emitted and folds so far, device time of the folds. */
+int t1k_sitepile_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff /* [nAlleles + 1] */, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos,
+                       uint64_t nBarcodes);
+int t1k_sitepile_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const uint64_t *bookPtr /* [n + 1] */, const uint32_t *book, const char *text, uint64_t textBytes,
+                     const int8_t *ops, uint64_t opsBytes, double *kernelMs);
+int t1k_sitepile_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns);
+int t1k_sitepile_stats(t1k_ctx *ctx, uint64_t *keysEmitted, uint64_t *folds, double *foldMs);
+int t1k_sitepile_end(t1k_ctx *ctx);
+
 /* ---- profiling counters of the last t1k_assign_batch (algorithmic-traffic terms of SURVEY.md 8d) --------------- */
 typedef struct {
   uint64_t read_ends, lookups, postings, hits, groups, candidates, extended, near_best, dp_calls, rows, batches;

@@ -111,6 +111,11 @@ def lib():
     L.t1k_pileup_add.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_double)]
     L.t1k_pileup_get.argtypes = [vp, vp]
     L.t1k_pileup_end.argtypes = [vp]
+    L.t1k_sitepile_begin.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64]
+    L.t1k_sitepile_add.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_double)]
+    L.t1k_sitepile_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
+    L.t1k_sitepile_stats.argtypes = [vp, u64p, u64p, C.POINTER(C.c_double)]
+    L.t1k_sitepile_end.argtypes = [vp]
     L.t1k_extract_batch.argtypes = [vp, C.c_uint32, vp, vp]
     L.t1k_extractor_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_stats_get.argtypes = [vp, C.POINTER(Stats)]
@@ -481,6 +486,68 @@ class Context:
             return self.pileup_get(), ms
         finally:
             self.pileup_end()
+
+    # per-barcode pileup at sites (t1k_sitepile_begin / _add / _get / _end); raw=True returns the status code instead of raising
+    def sitepile_begin(self, allele_off, site_allele, site_pos, n_barcodes, raw=False):
+        off = np.ascontiguousarray(allele_off, np.uint64)
+        sa, sp = np.ascontiguousarray(site_allele, np.uint32), np.ascontiguousarray(site_pos, np.uint32)
+        assert len(sa) == len(sp)
+        rc = lib().t1k_sitepile_begin(self.h, max(len(off) - 1, 0), _ptr(off), len(sa), _ptr(sa), _ptr(sp), int(n_barcodes))
+        if raw:
+            return rc
+        self._check(rc, "t1k_sitepile_begin")
+
+    def sitepile_add(self, aln, book_ptr, book, text, ops, raw=False):
+        """aln: PILEUP_ALN_DTYPE records; record i books once per entry of book[book_ptr[i]:book_ptr[i + 1]] (barcode << 1 | uniq); text / ops
+        as for pileup_add.  Returns the kernels' device time in ms"""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        bp, bk = np.ascontiguousarray(book_ptr, np.uint64), np.ascontiguousarray(book, np.uint32)
+        assert len(bp) == len(a) + 1
+        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+        o = np.ascontiguousarray(ops, np.int8)
+        ms = C.c_double()
+        rc = lib().t1k_sitepile_add(self.h, _ptr(a), len(a), _ptr(bp), _ptr(bk), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
+        if raw:
+            return rc
+        self._check(rc, "t1k_sitepile_add")
+        return ms.value
+
+    def sitepile_get(self, raw=False):
+        """the table's runs, ascending: (keys uint64, counts int32); key = ((barcode * nSites + site) * 7 + plane) * 2 + (1 - uniq)"""
+        n = C.c_uint64()
+        rc = lib().t1k_sitepile_get(self.h, None, None, 0, C.byref(n))
+        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
+        if rc == 0 and n.value:
+            rc = lib().t1k_sitepile_get(self.h, _ptr(keys), _ptr(counts), n.value, C.byref(n))
+        if raw:
+            return rc
+        self._check(rc, "t1k_sitepile_get")
+        return keys, counts
+
+    def sitepile_stats(self):
+        """(keys emitted, folds, device ms of the folds) of the open table"""
+        k, f, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        self._check(lib().t1k_sitepile_stats(self.h, C.byref(k), C.byref(f), C.byref(ms)), "t1k_sitepile_stats")
+        return k.value, f.value, ms.value
+
+    def sitepile_end(self, raw=False):
+        rc = lib().t1k_sitepile_end(self.h)
+        if raw:
+            return rc
+        self._check(rc, "t1k_sitepile_end")
+
+    def sitepile(self, allele_off, site_allele, site_pos, n_barcodes, aln, book_ptr, book, text, ops, cuts=()):
+        """begin, add (the records split at the indices `cuts` into several calls), get, end: (keys, counts, kernels' ms, folds)"""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        bp = np.ascontiguousarray(book_ptr, np.uint64)
+        self.sitepile_begin(allele_off, site_allele, site_pos, n_barcodes)
+        try:
+            edges = [0] + [int(c) for c in cuts] + [len(a)]
+            ms = sum(self.sitepile_add(a[lo:hi], bp[lo:hi + 1], book, text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
+            keys, counts = self.sitepile_get()
+            return keys, counts, ms, self.sitepile_stats()[1]
+        finally:
+            self.sitepile_end()
 
 
 class Readset:

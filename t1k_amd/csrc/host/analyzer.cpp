@@ -46,6 +46,27 @@ struct AnalyzerPileup {
 };
 static const char *kPileupHeader = "#allele\tpos\texon_pos\tref\tA\tC\tG\tT\tN\tdel\tins\tA_uniq\tC_uniq\tG_uniq\tT_uniq\tN_uniq\tdel_uniq\tins_uniq\n";
 
+// --barcodePileup: the sites are known only after VariantCaller::compute, so the piece loop of analyzerAlignAssignments keeps
+// what a replay through t1k_sitepile_add needs -- per piece the pileup records, the pattern text and the booking lists (one entry
+// barcode << 1 | uniq per assignment overlap that points at the record); the edit strings stay in V.ops.  Retained host memory: roughly
+// the read text of the assigned fragments (once more for the read-ends with an overlap on the other strand) + 40 bytes per distinct
+// alignment + 4 bytes per assignment overlap.
+struct AnalyzerSitepile {
+  struct Piece {
+    std::vector<t1k_pileup_aln> recs;
+    std::string pat;
+    std::vector<uint64_t> bookPtr;
+    std::vector<uint32_t> book;
+    uint64_t ops0 = 0, ops1 = 0;   // the piece's edit strings: V.ops[ops0 .. ops1)
+  };
+  const std::vector<int> *bcOf = nullptr;  // fragment -> barcode id
+  std::vector<Piece> pieces;
+  // extra sites of --sites (allele, 0-based position), and the lines of the file that name an allele which is not selected
+  std::vector<std::pair<uint32_t, uint32_t>> fileSites;
+  uint64_t fileSkipped = 0;
+};
+static const char *kBarcodePileupHeader = "#barcode\tallele\tpos\texon_pos\tref\tvar\tA\tC\tG\tT\tN\tdel\tins\tA_uniq\tC_uniq\tG_uniq\tT_uniq\tN_uniq\tdel_uniq\tins_uniq\n";
+
 // every fragment's raw row (the reference's list order): cnt[f] entries at rows[rowAt[f]]
 static int analyzerRows(t1k_job *job, std::vector<uint32_t> &cnt, std::vector<uint64_t> &rowAt, std::vector<t1k_row_entry> &rows) {
   const uint32_t F = (uint32_t)job->in->nFrag();
@@ -96,8 +117,9 @@ static int analyzerPooledEM(t1k_job *job, const std::vector<uint32_t> &cnt, cons
   return T1K_OK;
 }
 
-// steps (1) - (3): V.asgPtr / V.asg / V.ops and V.abundance; with `pile`, every piece's alignments go through t1k_pileup_add as well
-static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerPileup *pile) {
+// steps (1) - (3): V.asgPtr / V.asg / V.ops and V.abundance; with `pile`, every piece's alignments go through t1k_pileup_add as well; with `sp`,
+// every piece's records, pattern text and booking lists are kept for analyzerSitepile
+static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerPileup *pile, AnalyzerSitepile *sp = nullptr) {
   const double tv0 = nowMs();
   double &msAssign = V.msAssign, &msDetails = V.msDetails, &msAlign = V.msAlign;
   uint64_t &nEnds = V.nEnds, &nJobs = V.nJobs, &nFast = V.nFast;
@@ -333,7 +355,7 @@ static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerP
         if (a.has_mate_pair) { a.ops2 = opsAtOfJob[j2]; a.n_ops2 = nOpsOfJob[j2]; }
       }
       msAlign += nowMs() - tc;
-      if (pile && nJ) {
+      if ((pile || sp) && nJ) {
         // one record per alignment job; its weights = the assignments that point at it, and those of them whose fragment keeps one assignment
         const double tp = nowMs();
         std::vector<t1k_pileup_aln> recs(nJ);
@@ -352,17 +374,38 @@ static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerP
               if (j < 0) continue;
               ++recs[j].w_all;
               if (one) ++recs[j].w_uniq;
-              ++pile->nAsg;
-              pile->nCols += nOpsOfJob[j];
+              if (pile) { ++pile->nAsg; pile->nCols += nOpsOfJob[j]; }
             }
           }
         }
-        double kernelMs = 0;
-        if ((rc = t1k_pileup_add(vctx, recs.data(), (uint32_t)nJ, pat.data(), pat.size(), V.ops.data() + pieceOps0, V.ops.size() - pieceOps0, &kernelMs)) != T1K_OK)
-          return jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(vctx));
-        pile->nAln += nJ;
-        pile->msKernels += kernelMs;
-        pile->msCalls += nowMs() - tp;
+        if (pile) {
+          double kernelMs = 0;
+          if ((rc = t1k_pileup_add(vctx, recs.data(), (uint32_t)nJ, pat.data(), pat.size(), V.ops.data() + pieceOps0, V.ops.size() - pieceOps0, &kernelMs)) != T1K_OK)
+            return jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(vctx));
+          pile->nAln += nJ;
+          pile->msKernels += kernelMs;
+          pile->msCalls += nowMs() - tp;
+        }
+        if (sp) {
+          // the same loop once more, now that every record's number of bookings (w_all) is known: its list, in fragment order
+          AnalyzerSitepile::Piece pc;
+          pc.bookPtr.assign(nJ + 1, 0);
+          for (size_t j = 0; j < nJ; ++j) pc.bookPtr[j + 1] = pc.bookPtr[j] + recs[j].w_all;
+          pc.book.resize(pc.bookPtr[nJ]);
+          std::vector<uint64_t> fill(pc.bookPtr.begin(), pc.bookPtr.end() - 1);
+          for (uint32_t f = f0; f < f1; ++f) {
+            const uint32_t one = V.asgPtr[f + 1] - V.asgPtr[f] == 1 ? 1u : 0u;
+            for (uint64_t q = V.asgPtr[f]; q < V.asgPtr[f + 1]; ++q)
+              for (int m = 0; m < 2; ++m) {
+                const int64_t j = jobOfAsg[m][q - q0];
+                if (j >= 0) pc.book[fill[j]++] = ((uint32_t)(*sp->bcOf)[f] << 1) | one;
+              }
+          }
+          pc.recs = std::move(recs);
+          pc.pat = std::move(pat);
+          pc.ops0 = pieceOps0; pc.ops1 = V.ops.size();
+          sp->pieces.push_back(std::move(pc));
+        }
       }
     }
     f0 = f1;
@@ -377,10 +420,10 @@ static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerP
   return T1K_OK;
 }
 
-static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants &V, AnalyzerPileup *pile) {
+static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants &V, AnalyzerPileup *pile, AnalyzerSitepile *sp) {
   const double tv0 = nowMs();
   int rc;
-  if ((rc = analyzerAlignAssignments(job, V, pile)) != T1K_OK) return rc;
+  if ((rc = analyzerAlignAssignments(job, V, pile, sp)) != T1K_OK) return rc;
   const ReadInput &in = *job->in;
   const RefSet &R = job->ref;
   const uint32_t F = (uint32_t)in.nFrag();
@@ -439,6 +482,157 @@ static bool analyzerWritePileup(t1k_job *job, const std::string &prefix, Analyze
     fprintf(stderr, "pileup: %llu alignments walked, %llu assignments behind them, %llu columns booked; upload %.1f ms, kernels %.1f ms, download + write %.1f ms\n",
             (unsigned long long)pile->nAln, (unsigned long long)pile->nAsg, (unsigned long long)pile->nCols, std::max(0.0, pile->msCalls - pile->msKernels), pile->msKernels,
             pile->msDownload + (nowMs() - t0));
+  return true;
+}
+
+// --sites FILE: allele_name<TAB>pos (1-based) per line; '#' lines and blank lines are skipped, a name that is not selected is counted and
+// skipped; a malformed line or a pos outside its allele is an error that names the file and the line
+static bool analyzerReadSites(t1k_job *job, const std::string &path, AnalyzerSitepile &sp) {
+  const RefSet &R = job->ref;
+  std::unordered_map<std::string, uint32_t> alleleOf;
+  for (size_t a = 0; a < R.al.size(); ++a) alleleOf.emplace(R.al[a].name, (uint32_t)a);
+  FILE *fp = fopen(path.c_str(), "r");
+  if (!fp) { fprintf(stderr, "analyzer: cannot open %s\n", path.c_str()); return false; }
+  std::string line;
+  char buf[4096];
+  uint64_t lineNo = 0;
+  bool ok = true, more = true;
+  while (ok && more) {
+    line.clear();
+    more = false;
+    while (fgets(buf, sizeof buf, fp)) {
+      more = true;
+      line += buf;
+      if (!line.empty() && line.back() == '\n') break;
+    }
+    if (!more) break;
+    ++lineNo;
+    while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+    if (line.empty() || line[0] == '#') continue;
+    const size_t tab = line.find('\t');
+    char *end = nullptr;
+    const long long pos = tab == std::string::npos ? 0 : strtoll(line.c_str() + tab + 1, &end, 10);
+    if (tab == std::string::npos || tab == 0 || end == line.c_str() + tab + 1 || *end || !isdigit((unsigned char)line[tab + 1])) {
+      fprintf(stderr, "analyzer: %s line %llu: expected allele_name<TAB>pos\n", path.c_str(), (unsigned long long)lineNo);
+      ok = false;
+      break;
+    }
+    auto it = alleleOf.find(line.substr(0, tab));
+    if (it == alleleOf.end()) { ++sp.fileSkipped; continue; }
+    if (pos < 1 || (unsigned long long)pos > R.seqs[it->second].size()) {
+      fprintf(stderr, "analyzer: %s line %llu: pos %lld lies outside 1 .. %zu of %s\n", path.c_str(), (unsigned long long)lineNo, pos, R.seqs[it->second].size(), line.substr(0, tab).c_str());
+      ok = false;
+      break;
+    }
+    sp.fileSites.emplace_back(it->second, (uint32_t)(pos - 1));
+  }
+  fclose(fp);
+  if (ok) fprintf(stderr, "--sites: %zu sites read from %s, %llu lines name an allele that is not selected\n", sp.fileSites.size(), path.c_str(), (unsigned long long)sp.fileSkipped);
+  return ok;
+}
+
+// <prefix>_barcode_pileup.tsv: the kept pieces through t1k_sitepile_add at the sites (the rows of _allele.vcf and those of --sites), the runs
+// that come back merged per (barcode, site) and written in barcode id order (the order of the lines of _barcode_expr.tsv), then allele, then pos
+static bool analyzerSitepile(t1k_job *job, const std::string &prefix, const AnalyzerVariants &V, AnalyzerSitepile &sp, const std::vector<std::string> &barcodeNames) {
+  const double t0 = nowMs();
+  const RefSet &R = job->ref;
+  const size_t A = R.seqs.size();
+  // the sites, and per site the called bases in VCF order
+  std::vector<std::pair<uint32_t, uint32_t>> sites(sp.fileSites);
+  std::map<std::pair<uint32_t, uint32_t>, std::string> varOf;
+  if (V.vc)
+    for (const VariantRec &v : V.vc->variants) {
+      const std::pair<uint32_t, uint32_t> k((uint32_t)v.allele, (uint32_t)v.refPos);
+      sites.push_back(k);
+      std::string &s = varOf[k];
+      if (!s.empty()) s += ',';
+      s += v.var;
+    }
+  std::sort(sites.begin(), sites.end());
+  sites.erase(std::unique(sites.begin(), sites.end()), sites.end());
+  const size_t nSites = sites.size();
+  std::vector<uint32_t> siteAllele(nSites), sitePos(nSites);
+  for (size_t i = 0; i < nSites; ++i) { siteAllele[i] = sites[i].first; sitePos[i] = sites[i].second; }
+  std::vector<uint64_t> refOff(A + 1, 0);
+  for (size_t a = 0; a < A; ++a) refOff[a + 1] = refOff[a] + R.seqs[a].size();
+  t1k_ctx *ctx = job->ctx;
+  auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
+  int rc;
+  double msKernels = 0, msFold = 0;
+  uint64_t nRecs = 0, nRuns = 0, emitted = 0, folds = 0;
+  std::vector<uint64_t> keys;
+  std::vector<int32_t> counts;
+  if (nSites) {
+    if ((rc = t1k_sitepile_begin(ctx, (uint32_t)A, refOff.data(), nSites, siteAllele.data(), sitePos.data(), barcodeNames.size())) != T1K_OK) return fail(rc);
+    for (const AnalyzerSitepile::Piece &pc : sp.pieces) {
+      double ms = 0;
+      if ((rc = t1k_sitepile_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), pc.bookPtr.data(), pc.book.data(), pc.pat.data(), pc.pat.size(), V.ops.data() + pc.ops0, pc.ops1 - pc.ops0, &ms)) != T1K_OK) {
+        fail(rc);
+        t1k_sitepile_end(ctx);
+        return false;
+      }
+      msKernels += ms;
+      nRecs += pc.recs.size();
+    }
+    if ((rc = t1k_sitepile_get(ctx, nullptr, nullptr, 0, &nRuns)) == T1K_OK && nRuns) {
+      keys.resize(nRuns); counts.resize(nRuns);
+      rc = t1k_sitepile_get(ctx, keys.data(), counts.data(), nRuns, &nRuns);
+    }
+    if (rc == T1K_OK) rc = t1k_sitepile_stats(ctx, &emitted, &folds, &msFold);
+    if (rc != T1K_OK) { fail(rc); t1k_sitepile_end(ctx); return false; }
+    if ((rc = t1k_sitepile_end(ctx)) != T1K_OK) return fail(rc);
+  }
+  sp.pieces.clear();
+  const double tw = nowMs();
+  FILE *fp = fopen((prefix + "_barcode_pileup.tsv").c_str(), "w");
+  if (!fp) { fprintf(stderr, "analyzer: cannot write %s_barcode_pileup.tsv\n", prefix.c_str()); return false; }
+  fputs(kBarcodePileupHeader, fp);
+  // exonic position per site (SeqSet::GetExonicPosition), one pass per allele
+  std::vector<int> exonPos(nSites, 0);
+  for (size_t i = 0; i < nSites;) {
+    const uint32_t a = siteAllele[i];
+    int exonic = 0;
+    uint32_t p = 0;
+    for (; i < nSites && siteAllele[i] == a; ++i) {
+      for (; p <= sitePos[i]; ++p) exonic += R.exon[a][p] ? 1 : 0;
+      exonPos[i] = R.exon[a][sitePos[i]] ? exonic : 0;
+    }
+  }
+  std::string out;
+  char num[48];
+  uint64_t cells = 0;
+  for (size_t i = 0; i < keys.size();) {
+    const uint64_t cell = keys[i] / 14;  // barcode * nSites + site: its runs are consecutive
+    int32_t c[14] = {0};
+    for (; i < keys.size() && keys[i] / 14 == cell; ++i) {
+      const uint32_t plane = (uint32_t)((keys[i] % 14) >> 1);
+      c[plane] += counts[i];                                  // a uniq booking counts in the plain counter as well
+      if ((keys[i] & 1) == 0) c[7 + plane] += counts[i];
+    }
+    const uint64_t bc = cell / nSites, site = cell % nSites;
+    const uint32_t a = siteAllele[site], pos = sitePos[site];
+    ++cells;
+    out += barcodeNames[bc];
+    out += '\t';
+    out += R.al[a].name;
+    snprintf(num, sizeof num, "\t%u\t", pos + 1);
+    out += num;
+    if (exonPos[site]) { snprintf(num, sizeof num, "%d", exonPos[site]); out += num; } else out += '.';
+    out += '\t';
+    out += R.seqs[a][pos];
+    out += '\t';
+    auto it = varOf.find(sites[site]);
+    out += it == varOf.end() ? std::string(".") : it->second;
+    for (int k = 0; k < 14; ++k) { snprintf(num, sizeof num, "\t%d", c[k]); out += num; }
+    out += '\n';
+    if (out.size() >= (1u << 20)) { fwrite(out.data(), 1, out.size(), fp); out.clear(); }
+  }
+  fwrite(out.data(), 1, out.size(), fp);
+  fclose(fp);
+  if (getenv("T1K_DEBUG_PHASES"))
+    fprintf(stderr, "barcode pileup: %zu sites, %llu records, %llu keys emitted, %llu folds, %llu cells; upload %.1f ms, kernels %.1f ms, fold %.1f ms, write %.1f ms\n", nSites,
+            (unsigned long long)nRecs, (unsigned long long)emitted, (unsigned long long)folds, (unsigned long long)cells, std::max(0.0, (tw - t0) - msKernels - msFold), msKernels, msFold,
+            nowMs() - tw);
   return true;
 }
 
@@ -688,6 +882,10 @@ static const char *kAnalyzerUsage =
     "\t--umiMismatch INT: 1 joins a UMI to a neighbour at one mismatch that is at least twice as frequent, 0 keeps every UMI (default: 1)\n"
     "\t--pileup: also write prefix_allele_pileup.tsv, per base of every selected allele the read bases, deletions and inserted bases of the alignments\n"
     "\t\tthe variant pass holds, over all assignments and over those of fragments with one assignment (_uniq)\n"
+    "\t--barcodePileup: also write prefix_barcode_pileup.tsv, the counters of --pileup per barcode at the positions of prefix_allele.vcf and of --sites,\n"
+    "\t\tone line per (barcode, site) with a read (needs --barcode)\n"
+    "\t--sites FILE: more sites for --barcodePileup, one per line as allele_name<TAB>pos (1-based, the pos column of prefix_allele_pileup.tsv); '#' lines,\n"
+    "\t\tblank lines and alleles that are not selected are skipped\n"
     "\t--relaxIntronAlign: allow one more mismatch in intronic alignment\n"
     "\t--alleleDigitUnits INT, --alleleDelimiter CHR: as in genotyper\n"
     "\t--varMaxGroup INT: the maximum variant group size to call novel variant. -1 for no limitation, 0 for no variant calling (default: 8)\n"
@@ -698,17 +896,18 @@ int t1k_analyzer_main(int argc, char **argv) {
   static struct option longOpts[] = {{"barcode", required_argument, 0, 10000}, {"relaxIntronAlign", no_argument, 0, 10004}, {"alleleDigitUnits", required_argument, 0, 10005},
                                      {"alleleDelimiter", required_argument, 0, 10006}, {"varMaxGroup", required_argument, 0, 10007}, {"device", required_argument, 0, 10010},
                                      {"barcodeEM", no_argument, 0, 10011}, {"barcodeEMPrior", required_argument, 0, 10012}, {"umi", required_argument, 0, 10013},
-                                     {"umiMismatch", required_argument, 0, 10014}, {"pileup", no_argument, 0, 10015}, {0, 0, 0, 0}};
+                                     {"umiMismatch", required_argument, 0, 10014}, {"pileup", no_argument, 0, 10015}, {"barcodePileup", no_argument, 0, 10016},
+                                     {"sites", required_argument, 0, 10017}, {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
   std::string refFile, alleleFile, prefix = "t1k", barcode;
   std::vector<const char *> f1, f2, single;
   int varMaxGroup = 8;  // Analyzer.cpp:251
-  bool barcodeEM = false, pileup = false;
+  bool barcodeEM = false, pileup = false, barcodePileup = false;
   double emPrior = 0;
   const char *emPriorText = nullptr, *umiMismatchText = nullptr;
-  std::string umiPath;
+  std::string umiPath, sitesPath;
   int umiMismatch = 1;
   optind = 1;
   int c, idx = 0;
@@ -734,6 +933,8 @@ int t1k_analyzer_main(int argc, char **argv) {
       case 10013: umiPath = optarg; break;
       case 10014: umiMismatchText = optarg; break;
       case 10015: pileup = true; break;
+      case 10016: barcodePileup = true; break;
+      case 10017: sitesPath = optarg; break;
       default: fprintf(stderr, "%s", kAnalyzerUsage); return EXIT_FAILURE;
     }
   }
@@ -748,6 +949,8 @@ int t1k_analyzer_main(int argc, char **argv) {
     if (end == emPriorText || *end || !(emPrior >= 0) || !std::isfinite(emPrior)) { fprintf(stderr, "--barcodeEMPrior needs a number >= 0.\n"); return EXIT_FAILURE; }
   }
   if (!umiPath.empty() && barcode.empty()) { fprintf(stderr, "--umi needs --barcode.\n"); return EXIT_FAILURE; }
+  if (barcodePileup && barcode.empty()) { fprintf(stderr, "--barcodePileup needs --barcode.\n"); return EXIT_FAILURE; }
+  if (!sitesPath.empty() && !barcodePileup) { fprintf(stderr, "--sites has no meaning without --barcodePileup: ignored.\n"); sitesPath.clear(); }
   if (umiMismatchText) {
     if (strcmp(umiMismatchText, "0") && strcmp(umiMismatchText, "1")) { fprintf(stderr, "--umiMismatch needs 0 or 1.\n"); return EXIT_FAILURE; }
     umiMismatch = atoi(umiMismatchText);
@@ -794,6 +997,12 @@ int t1k_analyzer_main(int argc, char **argv) {
       fclose(fe);
     }
     if (pileup && !analyzerWritePileup(nullptr, prefix, nullptr)) return EXIT_FAILURE;
+    if (barcodePileup) {  // (no allele is selected: every name of --sites would be skipped)
+      FILE *fs = fopen((prefix + "_barcode_pileup.tsv").c_str(), "w");
+      if (!fs) { fprintf(stderr, "analyzer: cannot write %s_barcode_pileup.tsv\n", prefix.c_str()); return EXIT_FAILURE; }
+      fputs(kBarcodePileupHeader, fs);
+      fclose(fs);
+    }
     logLine("Post analysis finishes.");
     return 0;
   }
@@ -805,6 +1014,8 @@ int t1k_analyzer_main(int argc, char **argv) {
     return EXIT_FAILURE;
   }
   job->analyzer = true;
+  std::unique_ptr<AnalyzerSitepile> sp(barcodePileup ? new AnalyzerSitepile : nullptr);
+  if (sp && !sitesPath.empty() && !analyzerReadSites(job, sitesPath, *sp)) { t1k_job_destroy(job); return EXIT_FAILURE; }
   const bool paired = !f2.empty();
   const std::vector<const char *> &first = !f1.empty() ? f1 : single;
   if (first.empty()) { fprintf(stderr, "analyzer: no read file given (-u, or -1 and -2)\n"); t1k_job_destroy(job); return EXIT_FAILURE; }
@@ -819,16 +1030,33 @@ int t1k_analyzer_main(int argc, char **argv) {
   uint64_t nAssigned = 0;
   for (uint32_t f = 0; f < F; ++f) nAssigned += job->fragAssigned[f] ? 1 : 0;
   logLine("Finish read fragment assignments. %d read fragments can be assigned.", (int)nAssigned);
+  // barcode ids in order of first appearance over ALL loaded fragments (Analyzer.cpp:380-392): the rows of the per-barcode tables, and the
+  // barcodes of --barcodePileup's bookings, which the variant pass collects
+  std::vector<std::string> names;
+  std::vector<int> bcOf;
+  if (in.hasBarcode) {
+    std::unordered_map<std::string, int> idOf;
+    bcOf.resize(F);
+    for (uint32_t f = 0; f < F; ++f) {
+      const uint32_t r = in.frag[f];
+      std::string s(in.bc.seqP[r], in.bc.seqL[r]);
+      auto it = idOf.find(s);
+      if (it == idOf.end()) { it = idOf.emplace(s, (int)names.size()).first; names.push_back(s); }
+      bcOf[f] = it->second;
+    }
+  }
+  if (sp && !in.hasBarcode) { fprintf(stderr, "analyzer: --barcodePileup: the barcode file gave no barcodes\n"); t1k_job_destroy(job); return EXIT_FAILURE; }
+  if (sp) sp->bcOf = &bcOf;
   AnalyzerVariants V;
   std::unique_ptr<AnalyzerPileup> pile(pileup ? new AnalyzerPileup : nullptr);
   if (varMaxGroup != 0) {  // (0: VariantCaller::ComputeVariant returns before it looks at a read, VariantCaller.hpp:980-981)
-    rc = analyzerCallVariants(job, varMaxGroup, V, pile.get());
+    rc = analyzerCallVariants(job, varMaxGroup, V, pile.get(), sp.get());
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
     logLine("Finish allele quantification in %d EM iterations.", V.emIterations);
-  } else if (pileup) {
+  } else if (pileup || (sp && !sp->fileSites.empty())) {
     // no variant is called, but the pileup is of the alignments of steps (1) - (3): they run, VariantCaller does not (V.vc stays empty: the
-    // VCF is the empty file and the per-barcode table counts the raw lists)
-    rc = analyzerAlignAssignments(job, V, pile.get());
+    // VCF is the empty file and the per-barcode table counts the raw lists).  --barcodePileup without sites of its own has nothing to book.
+    rc = analyzerAlignAssignments(job, V, pile.get(), sp.get());
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
   } else if (barcodeEM && emPrior > 0) {
     // the per-barcode EM's prior is the pooled EM's abundances: step (1) of the variant pass on its own (its outputs are not written)
@@ -850,18 +1078,12 @@ int t1k_analyzer_main(int argc, char **argv) {
     if (!analyzerWritePileup(job, prefix, pile.get())) { t1k_job_destroy(job); return EXIT_FAILURE; }
     pile.reset();
   }
+  if (sp) {
+    if (!analyzerSitepile(job, prefix, V, *sp, names)) { t1k_job_destroy(job); return EXIT_FAILURE; }
+    sp.reset();
+  }
   if (in.hasBarcode) {
-    // barcode ids in order of first appearance over ALL loaded fragments (Analyzer.cpp:380-392), counts in fragment order
-    std::unordered_map<std::string, int> idOf;
-    std::vector<std::string> names;
-    std::vector<int> bcOf(F);
-    for (uint32_t f = 0; f < F; ++f) {
-      const uint32_t r = in.frag[f];
-      std::string s(in.bc.seqP[r], in.bc.seqL[r]);
-      auto it = idOf.find(s);
-      if (it == idOf.end()) { it = idOf.emplace(s, (int)names.size()).first; names.push_back(s); }
-      bcOf[f] = it->second;
-    }
+    // counts in fragment order
     const size_t A = job->ref.al.size();
     std::map<int, std::pair<std::vector<double>, std::vector<int>>> table;  // barcode -> (fractional counts, unique counts)
     const uint32_t step = 1u << 18;

@@ -313,7 +313,7 @@ void t1k_ctx_destroy(t1k_ctx *ctx) {
                       &ctx->bWgStage, &ctx->bWgBig, &ctx->bWgCache, &ctx->bLists, &ctx->bCand, &ctx->bExt, &ctx->bCandStart, &ctx->bCandCount, &ctx->bListPtr, &ctx->bListCount,
                       &ctx->bOvlWork, &ctx->bDedupScratch, &ctx->bDedupBases, &ctx->bDedupN, &ctx->bDedupLen, &ctx->bDedupWeight, &ctx->bOvlStart, &ctx->bOvlCount, &ctx->bCounters, &ctx->bSlowQueue, &ctx->bSlowScratch, &ctx->bSortScratch, &ctx->bEqTrace, &ctx->bSortTmp, &ctx->bJobSort, &ctx->bEnd1, &ctx->bEnd2,
                       &ctx->bHasN, &ctx->bRows, &ctx->bRowStart, &ctx->bRowCount, &ctx->bFragAssigned, &ctx->bPairScratch, &ctx->bPairOverflow, &ctx->bPairBig, &ctx->bExtractHuge, &ctx->bEmRowPtr, &ctx->bEmEc,
-                      &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bExtract, &ctx->bPileup, &ctx->bPileupIn};
+                      &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bExtract, &ctx->bPileup, &ctx->bPileupIn, &ctx->bSpSites, &ctx->bSpKeys, &ctx->bSpVals, &ctx->bSpWork, &ctx->bSpIn};
   for (auto *b : all) freeBuf(*b);
   for (auto &slot : ctx->storeChunks)
     for (auto &b : slot) freeBuf(b);
@@ -334,7 +334,7 @@ uint64_t t1k_ctx_mem_report(t1k_ctx *ctx, const char *tag, int print) {
     B(bWgStage), B(bWgBig), B(bWgCache), B(bLists), B(bCand), B(bExt), B(bCandStart), B(bCandCount), B(bListPtr), B(bListCount), B(bOvlWork), B(bDedupScratch), B(bDedupBases), B(bDedupN),
     B(bDedupLen), B(bDedupWeight), B(bOvlStart), B(bOvlCount), B(bCounters), B(bSlowQueue), B(bSlowScratch), B(bSortScratch), B(bEqTrace), B(bSortTmp), B(bJobSort), B(bEnd1),
     B(bEnd2), B(bHasN), B(bRows), B(bRowStart), B(bRowCount), B(bFragAssigned), B(bPairScratch), B(bPairOverflow), B(bPairBig), B(bExtractHuge), B(bEmRowPtr), B(bEmEc), B(bEmCount),
-    B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract), B(bPileup), B(bPileupIn)};
+    B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract), B(bPileup), B(bPileupIn), B(bSpSites), B(bSpKeys), B(bSpVals), B(bSpWork), B(bSpIn)};
 #undef B
   uint64_t tot = 0, ref = 0, store = 0, align = 0;
   std::string line;

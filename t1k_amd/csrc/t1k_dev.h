@@ -837,6 +837,16 @@ struct t1k_ctx {
   T1kDevBuf bPileup, bPileupIn;
   bool pileupOpen = false;
   std::vector<uint64_t> pileupOff, pileupLoad;
+  // per-barcode pileup at sites (t1k_sitepile.hip), open from t1k_sitepile_begin to _end: [site bitmap | rank directory | alleleOff] (pieces at
+  // spSiteAt), the table -- spRuns folded (key, count) pairs, then spPending keys of count 1, room for spCap -- the fold's scratch and the
+  // staging block of one _add call
+  T1kDevBuf bSpSites, bSpKeys, bSpVals, bSpWork, bSpIn;
+  bool spOpen = false;
+  std::vector<uint64_t> spOff;
+  size_t spSiteAt[3] = {0, 0, 0};
+  uint64_t spSites = 0, spBarcodes = 0, spRuns = 0, spPending = 0, spCap = 0, spBound = 0, spEmitted = 0, spFolds = 0;
+  int spEndBit = 64;
+  double spFoldMs = 0;
   t1k_stats stats{};
 };
 

@@ -5,7 +5,7 @@
 //   k_pileup<false>  the check: walks every record's edit string without booking -- an op outside 0 .. 3, a walk that leaves its allele
 //                    or the text sets a flag word.  Only when the flag comes back clear does the host launch
 //   k_pileup<true>   the booking: the same walk with integer atomicAdd into the counter-major table.
-// One wave64 per record, 64 edit columns per step.  A lane's allele coordinate is seq_start + the non-insert ops before it, its read
+// One wave64 per record, 64 edit columns per step (the walk itself: t1k_walk.h, shared with k_sitepile).  A lane's allele coordinate is seq_start + the non-insert ops before it, its read
 // coordinate the non-delete ops before it: a ballot, a population count below the lane, and wave-uniform running totals -- no lane
 // walks the string.  The table is counter-major (14 planes of alleleOff[nAlleles] ints), so a run of matches books 64 consecutive
 // ints of at most five planes.  Record index, n_ops and the step count are wave-uniform (readfirstlane): no exec-mask loop around
@@ -13,9 +13,7 @@
 #include <algorithm>
 #include <cstring>
 #include "t1k_dev.h"
-
-enum { PILEUP_PLANES = 14, PILEUP_N = 4, PILEUP_DEL = 5, PILEUP_INS = 6, PILEUP_UNIQ = 7 };
-enum { PILEUP_BAD_OP = 1, PILEUP_BAD_ALLELE_WALK = 2, PILEUP_BAD_TEXT_WALK = 4 };
+#include "t1k_walk.h"
 
 struct PileupArgs {
   const t1k_pileup_aln *aln;
@@ -29,14 +27,6 @@ struct PileupArgs {
   uint32_t *flag;
 };
 
-__device__ __forceinline__ uint32_t pileupUniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ unsigned long long pileupUniform64(unsigned long long v) {
-  return ((unsigned long long)pileupUniform((uint32_t)(v >> 32)) << 32) | pileupUniform((uint32_t)v);
-}
-__device__ __forceinline__ uint32_t pileupBelow(uint64_t m) {  // set bits of m below this lane
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 template <bool BOOK>
 __global__ __launch_bounds__(256) void k_pileup(PileupArgs P) {
   const uint32_t lane = threadIdx.x & 63u;
@@ -49,42 +39,18 @@ __global__ __launch_bounds__(256) void k_pileup(PileupArgs P) {
     if (BOOK && wAll == 0) continue;
     const unsigned long long base = pileupUniform64(P.alleleOff[allele]);
     const unsigned long long len = pileupUniform64(P.alleleOff[allele + 1]) - base;
-    unsigned long long t = seqStart, p = 0;  // next allele position, read bases consumed: wave-uniform
-    uint32_t bad = 0;
-    for (uint32_t c0 = 0; c0 < nOps; c0 += 64u) {
-      const uint32_t col = c0 + lane;
-      const bool active = col < nOps;
-      const int op = active ? (int)P.ops[opsAt + col] : -1;
-      const bool isT = active && op != 2, isP = active && op != 3;
-      const uint64_t mT = __ballot(isT ? 1 : 0), mP = __ballot(isP ? 1 : 0);
-      if (BOOK) {
-        if (active) {
-          const unsigned long long myT = t + pileupBelow(mT), myP = p + pileupBelow(mP);
-          unsigned long long pos = myT;
-          uint32_t plane;
-          if (op == 2) {
-            plane = PILEUP_INS;
-            pos = myT > seqStart ? myT - 1 : myT;   // the allele position consumed last; none yet: seq_start
-            if (pos >= len) pos = len - 1;            // (an all-insert window at the allele's end)
-          } else if (op == 3) {
-            plane = PILEUP_DEL;
-          } else {
-            const char c = P.text[readAt + myP];
-            plane = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : (uint32_t)PILEUP_N;
-          }
-          int32_t *cell = P.table + (unsigned long long)plane * P.total + base + pos;
-          atomicAdd(cell, (int32_t)wAll);
-          if (wUniq) atomicAdd(cell + (unsigned long long)PILEUP_UNIQ * P.total, (int32_t)wUniq);
-        }
-      } else {
-        bad |= __ballot((active && (op < 0 || op > 3)) ? 1 : 0) ? (uint32_t)PILEUP_BAD_OP : 0u;
-      }
-      t += (uint32_t)__popcll(mT);
-      p += (uint32_t)__popcll(mP);
-    }
+    // (the walk itself lives in t1k_walk.h; the check instantiation asks for no columns)
+    const PileupWalkEnd end = pileupWalk<!BOOK, BOOK>(P.ops, opsAt, nOps, seqStart, len, lane, [&](bool active, int op, unsigned long long pos, unsigned long long myP) {
+      if (!active) return;
+      const uint32_t plane = op == 2 ? (uint32_t)PILEUP_INS : op == 3 ? (uint32_t)PILEUP_DEL : pileupBasePlane(P.text[readAt + myP]);
+      int32_t *cell = P.table + (unsigned long long)plane * P.total + base + pos;
+      atomicAdd(cell, (int32_t)wAll);
+      if (wUniq) atomicAdd(cell + (unsigned long long)PILEUP_UNIQ * P.total, (int32_t)wUniq);
+    });
     if (!BOOK) {
-      if (len == 0 || t > len) bad |= PILEUP_BAD_ALLELE_WALK;
-      if (readAt + p > P.textBytes) bad |= PILEUP_BAD_TEXT_WALK;
+      uint32_t bad = end.bad;
+      if (len == 0 || end.t > len) bad |= PILEUP_BAD_ALLELE_WALK;
+      if (readAt + end.p > P.textBytes) bad |= PILEUP_BAD_TEXT_WALK;
       if (bad && lane == 0) atomicOr(P.flag, bad);
     }
   }
