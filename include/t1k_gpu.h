@@ -119,6 +119,16 @@ int t1k_assign_range(t1k_ctx *ctx, uint64_t first, uint32_t count);
 /* copy the overlap lists out (tests / --outputReadAssignment): counts[nReadEnds]; ovl may be NULL to query the total */
 int t1k_overlaps_download(t1k_ctx *ctx, uint32_t *counts, t1k_overlap *ovl, uint64_t cap, uint64_t *total);
 
+/* TEST-ONLY: overlap lists made by the host instead of t1k_assign_range's, so that mate pairing can be checked on lists a test
+ * constructed.  counts[nReadEnds] for the context's own uploaded read set (whose text is irrelevant to pairing), ovl = the lists one
+ * after the other (`similarity` is not stored: pairing recomputes it from the other fields).  T1K_ERR_ARG if a record lies outside its
+ * allele or does not fit the packed form of the overlap store. */
+int t1k_overlaps_upload(t1k_ctx *ctx, const uint32_t *counts, const t1k_overlap *ovl);
+/* TEST-ONLY: the sizes at which the pairing kernel changes its route: out[0] = overlaps of both mates the in-LDS join table takes (more:
+ * the per-workgroup tables in device memory), out[1] = overlaps of both mates the first launch takes (more: the second launch),
+ * out[2] = row entries per tile of the rowset form's rank sort, out[3] = list records per round of the streamed passes. */
+void t1k_pair_limits(uint32_t out[4]);
+
 /* One kept (fragment, allele) assignment: Genotyper::_readAssignment (Genotyper.hpp:44-56). 24 bytes. */
 typedef struct {
   int32_t allele_idx, start, end;

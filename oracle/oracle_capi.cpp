@@ -28,6 +28,7 @@ void orc_destroy(void *h) { delete (Oracle *)h; }
 int orc_load_reference(void *h, const char *fasta) { return ((Oracle *)h)->loadReference(fasta); }
 int orc_allele_count(void *h) { return (int)((Oracle *)h)->alleles.size(); }
 const char *orc_allele_name(void *h, int i) { return ((Oracle *)h)->alleles[i].name.c_str(); }
+int orc_allele_major(void *h, int i) { return ((Oracle *)h)->alleles[i].majorAllele; }  // index of its major-allele series (Genotyper::InitAlleleInfo)
 
 // SeqSet::AssignRead restatement.  out: 12 int32 per overlap
 // (seqIdx, readStart, readEnd, seqStart, seqEnd, strand, matchCnt, leftClip, rightClip, relaxedMatchCnt, simNumer, simDenom);
@@ -45,6 +46,43 @@ int orc_assign_read(void *h, const char *read, int weight, int *out, double *sim
     ++n;
   }
   return (int)ov.size();
+}
+
+// SeqSet::ReadAssignmentToFragmentAssignment + Genotyper::SetReadAssignments for one fragment.  l1 / l2: overlap lists in the layout
+// orc_assign_read writes (12 int32 per overlap, similarity beside them); l2 == NULL: single-end run.  whitelist: [nAlleles] or NULL
+// (Genotyper.hpp:822-823: an allele outside it is left out of the row, nothing else changes).  rowI / rowF: 3 int32 (alleleIdx, start, end)
+// and 3 floats (weight, qual, adjustWeight) per row entry, at most rowCap of them written.  *fragAssigned: the list
+// ReadAssignmentToFragmentAssignment returned is not empty (Genotyper.cpp:564-565).  rawI (may be NULL): that list itself, 3 int32
+// (seqIdx, seqStart, seqEnd) per fragment overlap, at most rawCap written, its length in *nRaw.  Returns the number of row entries.
+static void listFrom(const int *l, const double *s, int n, std::vector<Overlap> &out) {
+  out.resize(n);
+  for (int i = 0; i < n; ++i) {
+    const int *r = l + 12 * i;
+    Overlap &o = out[i];
+    o.seqIdx = r[0]; o.readStart = r[1]; o.readEnd = r[2]; o.seqStart = r[3]; o.seqEnd = r[4]; o.strand = r[5];
+    o.matchCnt = r[6]; o.leftClip = r[7]; o.rightClip = r[8]; o.relaxedMatchCnt = r[9];
+    o.similarity = s[i];
+  }
+}
+int orc_pair_rows(void *h, const int *l1, const double *s1, int n1, const int *l2, const double *s2, int n2, int hasN, const unsigned char *whitelist,
+                  int *rowI, float *rowF, int rowCap, int *fragAssigned, int *rawI, int rawCap, int *nRaw) {
+  Oracle *o = (Oracle *)h;
+  std::vector<Overlap> a, b;
+  listFrom(l1, s1, n1, a);
+  if (l2) listFrom(l2, s2, n2, b);
+  std::vector<FragmentOverlap> frag;
+  o->pairFragments(a, l2 ? &b : nullptr, hasN != 0, frag);
+  if (fragAssigned) *fragAssigned = frag.empty() ? 0 : 1;
+  if (nRaw) *nRaw = (int)frag.size();
+  if (rawI)
+    for (int i = 0; i < (int)frag.size() && i < rawCap; ++i) { rawI[3 * i] = frag[i].seqIdx; rawI[3 * i + 1] = frag[i].seqStart; rawI[3 * i + 2] = frag[i].seqEnd; }
+  std::vector<RowEntry> row;
+  o->fragmentToRow(frag, row, whitelist);
+  for (int i = 0; i < (int)row.size() && i < rowCap; ++i) {
+    rowI[3 * i] = row[i].alleleIdx; rowI[3 * i + 1] = row[i].start; rowI[3 * i + 2] = row[i].end;
+    rowF[3 * i] = row[i].weight; rowF[3 * i + 1] = row[i].qual; rowF[3 * i + 2] = row[i].adjustWeight;
+  }
+  return (int)row.size();
 }
 
 // per-base coverage of the allele's own base (the only counter GetSeqMissingBaseCoverage reads, SeqSet.hpp:2729)

@@ -878,8 +878,8 @@ int Oracle::pairFragments(const std::vector<Overlap> &ov1, const std::vector<Ove
   return (int)assign.size();
 }
 
-// Genotyper::SetReadAssignments + ReadAssignmentWeight (Genotyper.hpp:778-832, 205-230); whitelist unused
-void Oracle::fragmentToRow(const std::vector<FragmentOverlap> &frag, std::vector<RowEntry> &row) {
+// Genotyper::SetReadAssignments + ReadAssignmentWeight (Genotyper.hpp:778-832, 205-230)
+void Oracle::fragmentToRow(const std::vector<FragmentOverlap> &frag, std::vector<RowEntry> &row, const unsigned char *whitelist) {
   row.clear();
   int n = (int)frag.size();
   if (prm.maxAssignCnt > 0 && n > prm.maxAssignCnt) return;
@@ -889,6 +889,7 @@ void Oracle::fragmentToRow(const std::vector<FragmentOverlap> &frag, std::vector
   for (auto &f : frag) maxSim = std::max(maxSim, f.similarity);
   if (maxSim < 1) adjust = 0.25;
   for (auto &f : frag) {
+    if (whitelist && !whitelist[f.seqIdx]) continue;  // 822-823: after the -n and separator drops, the adjustment counts every fragment
     RowEntry e;
     e.alleleIdx = f.seqIdx; e.start = f.seqStart; e.end = f.seqEnd;
     double w = 1, seg = (1 - prm.refSeqSimilarity) / 4.0;

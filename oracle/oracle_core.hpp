@@ -96,8 +96,8 @@ class Oracle {
   int assignRead(const std::string &read, int weight, std::vector<Overlap> &out);
   // SeqSet::ReadAssignmentToFragmentAssignment (SeqSet.hpp:2310-2655); o2 may be NULL (single-end)
   int pairFragments(const std::vector<Overlap> &o1, const std::vector<Overlap> *o2, bool hasN, std::vector<FragmentOverlap> &out);
-  // Genotyper::SetReadAssignments (Genotyper.hpp:778-832)
-  void fragmentToRow(const std::vector<FragmentOverlap> &frag, std::vector<RowEntry> &row);
+  // Genotyper::SetReadAssignments (Genotyper.hpp:778-832); whitelist: [alleles.size()] flags or NULL (every allele whitelisted)
+  void fragmentToRow(const std::vector<FragmentOverlap> &frag, std::vector<RowEntry> &row, const unsigned char *whitelist = nullptr);
 
   // ---- group side ----
   std::vector<std::vector<RowEntry>> groups;  // coalesced read groups ("readAssignments", Genotyper.hpp:443)

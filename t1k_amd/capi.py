@@ -184,6 +184,19 @@ def lib():
     L.t1k_readset_size.restype = C.c_uint32
     L.t1k_readset_destroy.argtypes = [vp]
     L.t1k_coverage_selected.argtypes = [vp, vp, vp, u64p]
+    L.t1k_overlaps_upload.argtypes = [vp, vp, vp]
+    L.t1k_pair_limits.argtypes = [vp]
+    L.t1k_pair_limits.restype = None
+    L.t1k_rowset_create.argtypes = [vp, C.c_uint64, vp, C.POINTER(vp)]
+    L.t1k_rowset_destroy.argtypes = [vp]
+    L.t1k_rowset_destroy.restype = None
+    L.t1k_rowset_set_raw.argtypes = [vp, C.c_int]
+    L.t1k_rowset_last_error.argtypes = [vp]
+    L.t1k_rowset_last_error.restype = C.c_char_p
+    L.t1k_pair_into.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64]
+    L.t1k_rowset_rows_download.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
+    L.t1k_rowset_assigned_range.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
+    L.t1k_rowset_coalesce.argtypes = [vp, u64p, u64p, u64p]
     _lib = L
     return L
 
@@ -273,6 +286,13 @@ class Context:
         out = np.zeros(tot.value, dtype=OVERLAP_DTYPE)
         self._check(lib().t1k_overlaps_download(self.h, _ptr(counts), _ptr(out), tot.value, C.byref(tot)), "t1k_overlaps_download")
         return counts, out
+
+    def overlaps_upload(self, counts, ovl):
+        """test-only (t1k_overlaps_upload): overlap lists made by the host become the lists of the uploaded read set"""
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        o = np.ascontiguousarray(ovl, dtype=OVERLAP_DTYPE)
+        assert len(c) == self.n_read_ends and int(c.sum()) == len(o)
+        self._check(lib().t1k_overlaps_upload(self.h, _ptr(c), _ptr(o)), "t1k_overlaps_upload")
 
     def pair(self, end1, end2, has_n):
         e1 = np.asarray(end1, dtype=np.uint32)
@@ -548,6 +568,68 @@ class Context:
             return keys, counts, ms, self.sitepile_stats()[1]
         finally:
             self.sitepile_end()
+
+
+def pair_limits():
+    """(LDS join capacity, first launch's fragment capacity, rank-sort tile, records per streamed round) of the pairing kernel as built"""
+    out = np.zeros(4, dtype=np.uint32)
+    lib().t1k_pair_limits(_ptr(out))
+    return tuple(int(x) for x in out)
+
+
+class Rowset:
+    """All fragment rows of a job on one GPU (t1k_rowset): filled by pair_into, read back row by row or coalesced into read groups."""
+
+    def __init__(self, ctx, n_fragments, whitelist=None, raw=False):
+        wl = None if whitelist is None else np.ascontiguousarray(whitelist, dtype=np.uint8)
+        h = C.c_void_p()
+        ctx._check(lib().t1k_rowset_create(ctx.h, n_fragments, _ptr(wl), C.byref(h)), "t1k_rowset_create")
+        self.h, self.ctx, self.n_fragments = h, ctx, n_fragments
+        if raw:
+            self._check(lib().t1k_rowset_set_raw(self.h, 1), "t1k_rowset_set_raw")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise T1kError("%s failed (%d): %s" % (what, rc, lib().t1k_rowset_last_error(self.h).decode()))
+
+    def close(self):
+        if self.h:
+            lib().t1k_rowset_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def pair_into(self, ctx, end1, end2, has_n, frag_base=0):
+        e1 = np.asarray(end1, dtype=np.uint32)
+        e2 = None if end2 is None else np.asarray(end2, dtype=np.uint32)
+        hn = np.asarray(has_n, dtype=np.uint8)
+        ctx._check(lib().t1k_pair_into(ctx.h, self.h, _ptr(e1), _ptr(e2), _ptr(hn), len(e1), frag_base), "t1k_pair_into")
+
+    def rows(self, first=0, count=None):
+        """(row counts, rows in the reference's row order) of fragments [first, first + count)"""
+        count = self.n_fragments - first if count is None else count
+        counts = np.zeros(count, dtype=np.uint32)
+        tot = C.c_uint64()
+        self._check(lib().t1k_rowset_rows_download(self.h, first, count, _ptr(counts), None, 0, C.byref(tot)), "t1k_rowset_rows_download")
+        out = np.zeros(tot.value, dtype=ROW_DTYPE)
+        self._check(lib().t1k_rowset_rows_download(self.h, first, count, _ptr(counts), _ptr(out), tot.value, C.byref(tot)), "t1k_rowset_rows_download")
+        return counts, out
+
+    def assigned(self, first=0, count=None):
+        count = self.n_fragments - first if count is None else count
+        out = np.zeros(count, dtype=np.uint8)
+        self._check(lib().t1k_rowset_assigned_range(self.h, first, count, _ptr(out)), "t1k_rowset_assigned_range")
+        return out
+
+    def coalesce(self):
+        """(read groups, their entries, fragments with the fragmentAssigned flag)"""
+        g, e, a = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(lib().t1k_rowset_coalesce(self.h, C.byref(g), C.byref(e), C.byref(a)), "t1k_rowset_coalesce")
+        return g.value, e.value, a.value
 
 
 class Readset:

@@ -311,7 +311,7 @@ void t1k_ctx_destroy(t1k_ctx *ctx) {
   for (auto &b : ctx->refBufs) freeBuf(b);
   T1kDevBuf *all[] = {&ctx->bReadAscii, &ctx->bReadOffs, &ctx->bReadBases, &ctx->bReadN, &ctx->bReadLen, &ctx->bReadWeight, &ctx->bWgHits, &ctx->bWgGroups,
                       &ctx->bWgStage, &ctx->bWgBig, &ctx->bWgCache, &ctx->bLists, &ctx->bCand, &ctx->bExt, &ctx->bCandStart, &ctx->bCandCount, &ctx->bListPtr, &ctx->bListCount,
-                      &ctx->bOvlWork, &ctx->bDedupScratch, &ctx->bDedupBases, &ctx->bDedupN, &ctx->bDedupLen, &ctx->bDedupWeight, &ctx->bOvlStart, &ctx->bOvlCount, &ctx->bCounters, &ctx->bSlowQueue, &ctx->bSlowScratch, &ctx->bSortScratch, &ctx->bEqTrace, &ctx->bSortTmp, &ctx->bJobSort, &ctx->bEnd1, &ctx->bEnd2,
+                      &ctx->bOvlWork, &ctx->bOvlUpload, &ctx->bDedupScratch, &ctx->bDedupBases, &ctx->bDedupN, &ctx->bDedupLen, &ctx->bDedupWeight, &ctx->bOvlStart, &ctx->bOvlCount, &ctx->bCounters, &ctx->bSlowQueue, &ctx->bSlowScratch, &ctx->bSortScratch, &ctx->bEqTrace, &ctx->bSortTmp, &ctx->bJobSort, &ctx->bEnd1, &ctx->bEnd2,
                       &ctx->bHasN, &ctx->bRows, &ctx->bRowStart, &ctx->bRowCount, &ctx->bFragAssigned, &ctx->bPairScratch, &ctx->bPairOverflow, &ctx->bPairBig, &ctx->bExtractHuge, &ctx->bEmRowPtr, &ctx->bEmEc,
                       &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bExtract, &ctx->bPileup, &ctx->bPileupIn, &ctx->bSpSites, &ctx->bSpKeys, &ctx->bSpVals, &ctx->bSpWork, &ctx->bSpIn};
   for (auto *b : all) freeBuf(*b);
@@ -331,7 +331,7 @@ uint64_t t1k_ctx_mem_report(t1k_ctx *ctx, const char *tag, int print) {
   if (!ctx) return 0;
 #define B(x) {#x, &ctx->x}
   const struct { const char *name; T1kDevBuf *b; } all[] = {B(bReadAscii), B(bReadOffs), B(bReadBases), B(bReadN), B(bReadLen), B(bReadWeight), B(bWgHits), B(bWgGroups),
-    B(bWgStage), B(bWgBig), B(bWgCache), B(bLists), B(bCand), B(bExt), B(bCandStart), B(bCandCount), B(bListPtr), B(bListCount), B(bOvlWork), B(bDedupScratch), B(bDedupBases), B(bDedupN),
+    B(bWgStage), B(bWgBig), B(bWgCache), B(bLists), B(bCand), B(bExt), B(bCandStart), B(bCandCount), B(bListPtr), B(bListCount), B(bOvlWork), B(bOvlUpload), B(bDedupScratch), B(bDedupBases), B(bDedupN),
     B(bDedupLen), B(bDedupWeight), B(bOvlStart), B(bOvlCount), B(bCounters), B(bSlowQueue), B(bSlowScratch), B(bSortScratch), B(bEqTrace), B(bSortTmp), B(bJobSort), B(bEnd1),
     B(bEnd2), B(bHasN), B(bRows), B(bRowStart), B(bRowCount), B(bFragAssigned), B(bPairScratch), B(bPairOverflow), B(bPairBig), B(bExtractHuge), B(bEmRowPtr), B(bEmEc), B(bEmCount),
     B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract), B(bPileup), B(bPileupIn), B(bSpSites), B(bSpKeys), B(bSpVals), B(bSpWork), B(bSpIn)};
@@ -1099,6 +1099,44 @@ int t1k_overlaps_download(t1k_ctx *ctx, uint32_t *counts, t1k_overlap *out, uint
       r.similarity = (double)o.matchCnt / (double)(o.readEnd - o.readStart + 1 + o.seqEnd - o.seqStart + 1 + 2 * o.leftClip + 2 * o.rightClip);
     }
   }
+  return T1K_OK;
+}
+
+// TEST-ONLY (like t1k_align_batch): overlap lists made by the host take the place of t1k_assign_range's, so that the pairing stage can be
+// run on lists a test constructed.  counts[nReadEnds] records per read-end of the uploaded read set, ovl = the lists one after the other.
+int t1k_overlaps_upload(t1k_ctx *ctx, const uint32_t *counts, const t1k_overlap *ovl) {
+  if (!ctx || !counts) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_overlaps_upload: bad arguments");
+  if (!ctx->ref.bases) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_overlaps_upload: no reference");
+  if (!ctx->reads.listPtr || ctx->readsShared) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_overlaps_upload: no read set of this context's own");
+  T1K_HIP(ctx, hipSetDevice(ctx->device));
+  const uint32_t n = ctx->reads.nReadEnds;
+  uint64_t tot = 0;
+  for (uint32_t i = 0; i < n; ++i) tot += counts[i];
+  if (tot && !ovl) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_overlaps_upload: bad arguments");
+  std::vector<T1kOvlP> packed(tot);
+  for (uint64_t g = 0; g < tot; ++g) {
+    const t1k_overlap &r = ovl[g];
+    const bool fits = r.seq_idx >= 0 && (uint32_t)r.seq_idx < ctx->ref.nAlleles && (r.strand == 1 || r.strand == -1) && r.read_start >= 0 && r.read_end >= 0 && r.read_start < 65536 &&
+                      r.read_end < 65536 && r.match_cnt >= 0 && r.match_cnt < 65536 && r.relaxed_match_cnt >= 0 && r.relaxed_match_cnt < 65536 && r.left_clip >= 0 &&
+                      r.left_clip < 65536 && r.right_clip >= 0 && r.right_clip < 65536 && r.read_start <= r.read_end && r.seq_start >= 0 && r.seq_start <= r.seq_end &&
+                      r.seq_idx >= 0 && (uint32_t)r.seq_idx < ctx->ref.nAlleles && (uint32_t)r.seq_end < ctx->hAlleleLen[r.seq_idx];  // (inside its allele: the kernel looks separators up by these)
+    T1kOvl o{};
+    o.allele = (uint32_t)r.seq_idx; o.seqStart = r.seq_start; o.seqEnd = r.seq_end; o.readStart = (uint16_t)r.read_start; o.readEnd = (uint16_t)r.read_end;
+    o.matchCnt = (uint16_t)r.match_cnt; o.relaxed = (uint16_t)r.relaxed_match_cnt; o.leftClip = (uint16_t)r.left_clip; o.rightClip = (uint16_t)r.right_clip;
+    o.flags = r.strand == -1 ? 2u : 0u;
+    if (!fits || !t1k_ovl_pack(o, packed[g])) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_overlaps_upload: record " + std::to_string(g) + " lies outside its allele or does not fit the packed overlap fields");
+  }
+  int rc;
+  if ((rc = t1k_ensure(ctx, ctx->bOvlUpload, (size_t)tot * sizeof(T1kOvlP) + 16))) return rc;
+  std::vector<unsigned long long> ptr(n);
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < n; ++i) { ptr[i] = (unsigned long long)((const T1kOvlP *)ctx->bOvlUpload.p + at); at += counts[i]; }
+  if (tot) T1K_HIP(ctx, hipMemcpyAsync(ctx->bOvlUpload.p, packed.data(), (size_t)tot * sizeof(T1kOvlP), hipMemcpyHostToDevice, ctx->stream));
+  if (n) {
+    T1K_HIP(ctx, hipMemcpyAsync(ctx->reads.listPtr, ptr.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    T1K_HIP(ctx, hipMemcpyAsync(ctx->reads.listCount, counts, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the host vectors are pageable: the copies are done when they return, the barrier is for the error code)
   return T1K_OK;
 }
 

@@ -25,6 +25,7 @@
 // Join table of one fragment in LDS: allele -> (index in list 1 + 1) | membership bit 15 | (index in list 2 + 1) << 16.  Open addressing,
 // LJ_SLOTS slots (4096 or 2048: a template parameter of the kernel); fragments whose two lists hold more than 68 % of that (or a list
 // with a repeated allele) use the per-workgroup direct-address tables in HBM instead.
+constexpr uint32_t ljCapacity(uint32_t slots) { return slots * 17 / 25; }  // overlaps of both lists the table takes (the kernel's route choice and t1k_pair_limits read it here)
 template <int LJ_SLOTS>
 __device__ __forceinline__ uint32_t ljHash(uint32_t allele) { return (allele * 2654435761u) >> (LJ_SLOTS == 4096 ? 20 : 21); }  // 12 / 11 bits
 template <int LJ_SLOTS>
@@ -213,7 +214,7 @@ template <int WG, int LJ_SLOTS>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAVES, T1K_PAIR_WAVES))) void k_pair(PairArgs P) {
   constexpr int NWAVE = WG / 64;
   constexpr int PU = T1K_PAIR_UNROLL;  // records of a list a lane requests before it looks at the first (the streamed passes)
-  constexpr uint32_t LJ_CAP = LJ_SLOTS * 17 / 25;
+  constexpr uint32_t LJ_CAP = ljCapacity(LJ_SLOTS);
   __shared__ uint32_t warpSums[NWAVE];
   __shared__ int sDup, sFail, sBestM, sBestIdx, sAnySep, sNotOne;
   __shared__ double sBestSim;
@@ -817,6 +818,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
 #endif
 }
 
+// the shape k_pair is launched with: threads per fragment and slots of the LDS join table (pairLaunch says why these), and what a workgroup's own
+// scratch holds in the first launch
+constexpr int PAIR_WG = 256, PAIR_LJ_SLOTS = 4096;
+static uint32_t pairFragCap() {
+  static const uint32_t cap = [] { const char *e = getenv("T1K_PAIR_FRAGCAP"); return e ? (uint32_t)std::max(8, atoi(e)) : 8192u; }();  // (tests: force the second launch)
+  return cap;
+}
+
 // shared by t1k_pair_batch (rs == NULL) and t1k_pair_into
 static int pairLaunch(t1k_ctx *ctx, t1k_rowset *rs, const uint32_t *end1, const uint32_t *end2, const uint8_t *hasN, uint32_t nFragments, uint64_t fragBase,
                       const uint8_t *dWhitelist) {
@@ -833,8 +842,8 @@ static int pairLaunch(t1k_ctx *ctx, t1k_rowset *rs, const uint32_t *end1, const 
   // records: each of its four sweeps over a fragment's two lists misses the L2 that 128 fragments per XCD share)
   static const int maxWg = [] { const char *e = getenv("T1K_PAIR_WGS"); return e ? std::max(64, std::min(4096, atoi(e))) : 1024; }();
   const int nWg = (int)std::min<uint32_t>(maxWg, std::max<uint32_t>(n, 1));
-  auto launch = [&](unsigned grid, const PairArgs &args) { hipLaunchKernelGGL((k_pair<256, 4096>), dim3(grid), dim3(256), 0, ctx->stream, args); };
-  static const uint32_t envFragCap = [] { const char *e = getenv("T1K_PAIR_FRAGCAP"); return e ? (uint32_t)std::max(8, atoi(e)) : 8192u; }();  // (tests: force the second launch)
+  auto launch = [&](unsigned grid, const PairArgs &args) { hipLaunchKernelGGL((k_pair<PAIR_WG, PAIR_LJ_SLOTS>), dim3(grid), dim3(PAIR_WG), 0, ctx->stream, args); };
+  const uint32_t envFragCap = pairFragCap();
   static const uint64_t envBigCap = [] { const char *e = getenv("T1K_PAIR_BIGCAP"); return e ? (uint64_t)std::max(64, atoi(e)) : (uint64_t)(8u << 20); }();
   const uint32_t fragCap = envFragCap;   // overlaps of both mates a workgroup's own scratch holds; longer fragments: the second launch, scratch from the big arena
   const uint32_t A = ctx->ref.nAlleles;
@@ -952,6 +961,14 @@ int t1k_pair_into(t1k_ctx *ctx, t1k_rowset *rs, const uint32_t *end1, const uint
   if (fragBase + nFragments > rs->nFrag) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_pair_into: fragments outside the rowset");
   if (rs->device != ctx->device) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_pair_into: rowset lives on another device");
   return pairLaunch(ctx, rs, end1, end2, hasN, nFragments, fragBase, rs->whitelist);
+}
+
+// TEST-ONLY: the sizes at which k_pair changes its route, as this library was built (tests place their list lengths on them)
+void t1k_pair_limits(uint32_t out[4]) {
+  out[0] = ljCapacity(PAIR_LJ_SLOTS); // overlaps of both lists the LDS join table takes (the kernel's LJ_CAP)
+  out[1] = pairFragCap();             // overlaps of both lists the first launch takes
+  out[2] = SORT_TILE;
+  out[3] = PAIR_WG * T1K_PAIR_UNROLL; // list records one round of the streamed passes covers
 }
 
 int t1k_rows_download(t1k_ctx *ctx, uint32_t *rowCounts, uint8_t *fragAssigned, t1k_row_entry *rows, uint64_t cap, uint64_t *total) {

@@ -66,6 +66,48 @@ def test_oracle_vs_live_reference_binary(built, tmp_path):
     assert open(os.path.join(tmp, "a_assign.tsv")).read() == open(os.path.join(tmp, "b_assign.tsv")).read()
 
 
+def test_oracle_whitelist_rows_vs_live_reference_binary(built, tmp_path):
+    """the allele whitelist's drop in SetReadAssignments (Genotyper.hpp:822-823), which Oracle.pair_rows restates for the pairing tests: its
+    rows against the --outputReadAssignment table of the reference binary run with --alleleWhitelist"""
+    import numpy as np
+    import t1k_amd
+    util.need(util.REF_BIN)
+    tmp = str(tmp_path)
+    ref = os.path.join(tmp, "ref.fa")
+    util.synth_ref("ref-rna", ref, genes=3, scale=0.02, seed=77)
+    util.synth_reads(ref, os.path.join(tmp, "r"), pairs=150, len=150, seed=78)
+    orc = util.Oracle(ref, similarity=0.95)
+    names = orc.allele_names()
+    listed = names[::3]
+    wl = os.path.join(tmp, "whitelist.txt")
+    open(wl, "w").write("\n".join(listed) + "\n")
+    args = ["-f", ref, "-1", os.path.join(tmp, "r_1.fq"), "-2", os.path.join(tmp, "r_2.fq"), "-s", "0.95"]
+    table = {}
+    for tag, extra in (("all", []), ("wl", ["--alleleWhitelist", wl])):
+        subprocess.run([util.REF_BIN] + args + extra + ["-o", os.path.join(tmp, tag), "--outputReadAssignment", "-t", "1"], check=True, stderr=subprocess.PIPE)
+        table[tag] = open(os.path.join(tmp, tag + "_assign.tsv")).read()
+    flags = orc.whitelist_of(listed)
+    assert 0 < flags.sum() < len(flags) and table["wl"] != table["all"] and table["wl"].count("\n") > 100
+
+    def structured(o, s):
+        l = np.zeros(len(o), dtype=t1k_amd.OVERLAP_DTYPE)
+        for k, f in enumerate(("seq_idx", "read_start", "read_end", "seq_start", "seq_end", "strand", "match_cnt", "left_clip", "right_clip", "relaxed_match_cnt")):
+            l[f] = o[:, k]
+        l["similarity"] = s
+        return l
+
+    r1, r2 = util.fastx_records(os.path.join(tmp, "r_1.fq")), util.fastx_records(os.path.join(tmp, "r_2.fq"))
+    got = {"all": [], "wl": []}
+    for (name, a), (_, b) in zip(r1, r2):
+        rid = name[:-2] if name.endswith("/1") else name
+        l1, l2 = structured(*orc.assign_read(a)), structured(*orc.assign_read(b))
+        for tag, w in (("all", None), ("wl", flags)):
+            rows, _ = orc.pair_rows(l1, l2, "N" in a or "N" in b, whitelist=w)
+            got[tag] += ["%s\t%s\t%d\t%d\n" % (rid, names[r["allele_idx"]], r["start"], r["end"]) for r in rows]
+    assert "".join(got["all"]) == table["all"]
+    assert "".join(got["wl"]) == table["wl"]
+
+
 LIVE_TABLE_CASES = [  # (kind, genes, scale, read sets mixed into one sample, read length, flags): mixtures give genes more than two allele types
     ("ref-rna", 5, 0.02, 3, 150, ["-s", "0.9", "--crossGeneRate", "1.0"]),
     ("ref-rna", 4, 0.04, 3, 100, ["-s", "0.95", "--frac", "0.3", "--crossGeneRate", "0"]),

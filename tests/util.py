@@ -136,6 +136,9 @@ class Oracle:
         L.orc_allele_name.restype = C.c_char_p
         L.orc_destroy.argtypes = [C.c_void_p]
         L.orc_global_alignment.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.orc_pair_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.orc_allele_major.argtypes = [C.c_void_p, C.c_int]
         self.L = L
         self.h = L.orc_create(similarity, 1 if relax else 0, max_assign, digit_units, delimiter)
         if fasta is not None:
@@ -149,6 +152,46 @@ class Oracle:
         n = self.L.orc_assign_read(self.h, seq.encode(), weight, out.ctypes.data, sim.ctypes.data, cap)
         assert n <= cap
         return out[:n], sim[:n]
+
+    @staticmethod
+    def _list(l):
+        """a structured overlap array (t1k_amd.OVERLAP_DTYPE, what Context.overlaps() returns) in orc_assign_read's layout"""
+        out = np.zeros((len(l), 12), dtype=np.int32)
+        for k, f in enumerate(("seq_idx", "read_start", "read_end", "seq_start", "seq_end", "strand", "match_cnt", "left_clip", "right_clip", "relaxed_match_cnt")):
+            out[:, k] = l[f]
+        return out, np.ascontiguousarray(l["similarity"], dtype=np.float64)
+
+    def pair_rows(self, l1, l2, has_n, whitelist=None, raw=False):
+        """ReadAssignmentToFragmentAssignment + SetReadAssignments of one fragment (orc_pair_rows).  l2 None: single-end.  Returns
+        (rows as t1k_amd.ROW_DTYPE, fragmentAssigned) and, with raw, the undropped fragment list as an int32 [n, 3] array
+        (seqIdx, seqStart, seqEnd)."""
+        import t1k_amd
+        L = self.L
+        a, sa = self._list(l1)
+        b, sb = self._list(l2) if l2 is not None else (None, None)
+        cap = len(l1) + (len(l2) if l2 is not None else 0) + 1
+        ri, rf, rw = np.zeros((cap, 3), dtype=np.int32), np.zeros((cap, 3), dtype=np.float32), np.zeros((cap, 3), dtype=np.int32)
+        flag, nraw = C.c_int(), C.c_int()
+        wl = None if whitelist is None else np.ascontiguousarray(whitelist, dtype=np.uint8)
+        assert wl is None or len(wl) == self.n_alleles
+        n = L.orc_pair_rows(self.h, a.ctypes.data, sa.ctypes.data, len(a), None if b is None else b.ctypes.data, None if b is None else sb.ctypes.data,
+                            0 if b is None else len(b), 1 if has_n else 0, None if wl is None else wl.ctypes.data, ri.ctypes.data, rf.ctypes.data, cap,
+                            C.byref(flag), rw.ctypes.data, cap, C.byref(nraw))
+        assert n <= cap and nraw.value <= cap
+        rows = np.zeros(n, dtype=t1k_amd.ROW_DTYPE)
+        rows["allele_idx"], rows["start"], rows["end"] = ri[:n, 0], ri[:n, 1], ri[:n, 2]
+        rows["weight"], rows["qual"], rows["adjust_weight"] = rf[:n, 0], rf[:n, 1], rf[:n, 2]
+        return (rows, flag.value, rw[:nraw.value].copy()) if raw else (rows, flag.value)
+
+    def allele_names(self):
+        return [self.L.orc_allele_name(self.h, i).decode() for i in range(self.n_alleles)]
+
+    def whitelist_of(self, listed):
+        """Genotyper::SetAlleleWhitelist (Genotyper.hpp:684-705): the alleles of every major-allele series that has a listed member"""
+        major = [self.L.orc_allele_major(self.h, i) for i in range(self.n_alleles)]
+        idx = {n: i for i, n in enumerate(self.allele_names())}
+        chosen = set(major[idx[n]] for n in listed if n in idx)
+        return np.array([1 if m in chosen else 0 for m in major], dtype=np.uint8)
 
     def coverage(self, allele, length):
         out = np.zeros(length, dtype=np.int32)
