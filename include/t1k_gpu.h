@@ -180,6 +180,10 @@ int t1k_rowset_assigned_download(t1k_rowset *rs, uint8_t *fragAssigned);
 int t1k_rowset_assigned_range(t1k_rowset *rs, uint64_t first, uint64_t count, uint8_t *fragAssigned);
 /* rows of fragments [first, first + count) in the reference's row order (--outputReadAssignment, tests) */
 int t1k_rowset_rows_download(t1k_rowset *rs, uint64_t first, uint32_t count, uint32_t *rowCounts, t1k_row_entry *rows, uint64_t cap, uint64_t *total);
+/* TEST-ONLY: the sizes at which t1k_rowset_coalesce's fold changes its route: out[0] = rows per batch of the pipelined loops, out[1] = the
+ * run length (fragments of a group) from which this process folds a group with the four-wavefront kernel (4096, or T1K_CO_LONG_RUN as the
+ * library read it), out[2] = slots (entries of a group) per tile. */
+void t1k_coalesce_limits(uint32_t out[3]);
 
 /* ---- multi-GPU: one rank per GPU, each owning a contiguous slice of the fragments in file order -------------------
  * Ranks are processes (one per GPU, e.g. under torch.distributed.run: rank 0 calls t1k_comm_unique_id and hands the 128 bytes to

@@ -54,7 +54,8 @@ OVERLAP_DTYPE = np.dtype([("seq_idx", "<i4"), ("read_start", "<i4"), ("read_end"
                           ("right_clip", "<i4"), ("relaxed_match_cnt", "<i4"), ("similarity", "<f8")])
 ROW_DTYPE = np.dtype([("allele_idx", "<i4"), ("start", "<i4"), ("end", "<i4"), ("weight", "<f4"), ("qual", "<f4"),
                       ("adjust_weight", "<f4")])
-assert OVERLAP_DTYPE.itemsize == 48 and ROW_DTYPE.itemsize == 24
+GROUP_DTYPE = np.dtype([("allele", "<i4"), ("start", "<i4"), ("end", "<i4"), ("weight", "<f4"), ("adjust_weight", "<f4")])  # t1k_group_entry
+assert OVERLAP_DTYPE.itemsize == 48 and ROW_DTYPE.itemsize == 24 and GROUP_DTYPE.itemsize == 20
 # t1k_frag_assignment / t1k_variant (novel-variant calling of the analyzer stage, host code)
 FRAG_ASG_DTYPE = np.dtype([("allele_idx", "<i4"), ("has_mate_pair", "<i4"), ("o1_from_r2", "<i4"), ("_pad", "<i4"), ("o1", OVERLAP_DTYPE), ("o2", OVERLAP_DTYPE),
                            ("ops1", "<u8"), ("ops2", "<u8"), ("n_ops1", "<u4"), ("n_ops2", "<u4")])
@@ -197,6 +198,15 @@ def lib():
     L.t1k_rowset_rows_download.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
     L.t1k_rowset_assigned_range.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
     L.t1k_rowset_coalesce.argtypes = [vp, u64p, u64p, u64p]
+    L.t1k_rowset_groups_download.argtypes = [vp, vp, vp, vp]
+    L.t1k_rowset_device_bytes.argtypes = [vp, u64p, u64p]
+    L.t1k_coalesce_limits.argtypes = [vp]
+    L.t1k_coalesce_limits.restype = None
+    L.t1k_rowset_exchange.argtypes = [vp, vp, C.c_uint64]
+    L.t1k_rowset_groups_gather.argtypes = [vp, vp, u64p, u64p, u64p]
+    L.t1k_rowset_groups_download_all.argtypes = [vp, vp, vp, vp]
+    L.t1k_comm_abort.argtypes = [vp]
+    L.t1k_ref_share.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -253,6 +263,11 @@ class Context:
             ex = np.concatenate([np.asarray(m, dtype=np.uint8) for m in exon_masks]) if len(seqs) else np.zeros(0, np.uint8)
         self.allele_len = np.array([len(s) for s in seqs], dtype=np.int64)
         self._check(lib().t1k_ref_upload(self.h, blob, _ptr(offs), _ptr(ex), len(seqs)), "t1k_ref_upload")
+
+    def ref_share(self, src):
+        """this context reads the reference another context of the same GPU uploaded (t1k_ref_share); src must outlive it"""
+        self.allele_len = src.allele_len
+        self._check(lib().t1k_ref_share(self.h, src.h), "t1k_ref_share")
 
     def reads_upload(self, seqs, weights=None):
         blob, offs = _concat(seqs)
@@ -585,6 +600,7 @@ class Rowset:
         h = C.c_void_p()
         ctx._check(lib().t1k_rowset_create(ctx.h, n_fragments, _ptr(wl), C.byref(h)), "t1k_rowset_create")
         self.h, self.ctx, self.n_fragments = h, ctx, n_fragments
+        self._counts = self._all = None   # (groups, entries) of the last coalesce() / groups_gather()
         if raw:
             self._check(lib().t1k_rowset_set_raw(self.h, 1), "t1k_rowset_set_raw")
 
@@ -629,7 +645,53 @@ class Rowset:
         """(read groups, their entries, fragments with the fragmentAssigned flag)"""
         g, e, a = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(lib().t1k_rowset_coalesce(self.h, C.byref(g), C.byref(e), C.byref(a)), "t1k_rowset_coalesce")
+        self._counts = (g.value, e.value)
         return g.value, e.value, a.value
+
+    def groups(self):
+        """the read-group table of the last coalesce() (t1k_rowset_groups_download): (group_ptr uint64 [G + 1], entries as GROUP_DTYPE,
+        first_fragment uint32 [G])"""
+        if self._counts is None:
+            raise T1kError("Rowset.groups: coalesce() has not been called")
+        g, e = self._counts
+        ptr, ent, first = np.zeros(g + 1, dtype=np.uint64), np.zeros(e, dtype=GROUP_DTYPE), np.zeros(g, dtype=np.uint32)
+        self._check(lib().t1k_rowset_groups_download(self.h, _ptr(ptr), _ptr(ent), _ptr(first)), "t1k_rowset_groups_download")
+        return ptr, ent, first
+
+    def device_bytes(self):
+        """(device bytes of the per-fragment arrays and the row chunks, row entries the calls have taken from the chunks so far)"""
+        b, n = C.c_uint64(), C.c_uint64()
+        self._check(lib().t1k_rowset_device_bytes(self.h, C.byref(b), C.byref(n)), "t1k_rowset_device_bytes")
+        return b.value, n.value
+
+    # ---- multi-GPU (collective calls: every rank's thread or process makes them in the same order) ----
+    def exchange(self, comm, frag_base):
+        """every fragment row goes to the rank that owns its pattern (t1k_rowset_exchange); frag_base = global index of this rank's first fragment"""
+        self._check(lib().t1k_rowset_exchange(self.h, comm.h, frag_base), "t1k_rowset_exchange")
+
+    def groups_gather(self, comm):
+        """after coalesce() on every rank: all ranks' tables on every rank (t1k_rowset_groups_gather): (groups, entries, fragments with a row)"""
+        g, e, a = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(lib().t1k_rowset_groups_gather(self.h, comm.h, C.byref(g), C.byref(e), C.byref(a)), "t1k_rowset_groups_gather")
+        self._all = (g.value, e.value)
+        return g.value, e.value, a.value
+
+    def groups_all(self):
+        """the gathered tables, concatenated in rank order (t1k_rowset_groups_download_all): (sizes uint32 [G], entries as GROUP_DTYPE,
+        first_fragment uint32 [G] -- global fragment indices)"""
+        if self._all is None:
+            raise T1kError("Rowset.groups_all: groups_gather() has not been called")
+        g, e = self._all
+        sizes, ent, first = np.zeros(g, dtype=np.uint32), np.zeros(e, dtype=GROUP_DTYPE), np.zeros(g, dtype=np.uint32)
+        self._check(lib().t1k_rowset_groups_download_all(self.h, _ptr(sizes), _ptr(ent), _ptr(first)), "t1k_rowset_groups_download_all")
+        return sizes, ent, first
+
+
+def coalesce_limits():
+    """(rows per batch, run length from which a group is folded by the four-wavefront kernel in this process, slots per tile) of the read-group fold"""
+    out = np.zeros(3, dtype=np.uint32)
+    lib().t1k_coalesce_limits(_ptr(out))
+    return tuple(int(x) for x in out)
 
 
 class Readset:
@@ -937,7 +999,10 @@ class Comm:
         rc = lib().t1k_comm_init(ctx, n_ranks, rank, _ptr(uid), group.h if group is not None else None, transport, C.byref(h))
         self.h = h
         if rc != 0:
-            raise T1kError("t1k_comm_init failed (%d): %s" % (rc, lib().t1k_comm_last_error(h).decode() if h else ""))
+            msg = lib().t1k_comm_last_error(h).decode() if h else ""
+            if h:
+                lib().t1k_comm_abort(h)   # the ranks that wait for this one at the group's meeting point are released
+            raise T1kError("t1k_comm_init failed (%d): %s" % (rc, msg))
 
     def bind(self, owner):
         """owner: a Job or a Context, as in __init__"""
@@ -947,6 +1012,11 @@ class Comm:
 
     def is_rccl(self):
         return bool(lib().t1k_comm_is_rccl(self.h))
+
+    def abort(self):
+        """a rank that cannot go on releases the ranks waiting for it (t1k_comm_abort): their collectives fail instead of waiting"""
+        if self.h:
+            lib().t1k_comm_abort(self.h)
 
     def close(self):
         if self.h:

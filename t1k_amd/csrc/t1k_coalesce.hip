@@ -274,6 +274,13 @@ __global__ void k_co_unsort(const unsigned long long *rowPtr, const uint32_t *ro
   }
 }
 
+// the run length from which this process folds a group with k_co_reduce_long (T1K_CO_LONG_RUN, read once; never below
+// 2 CO_B + 2, the shortest run that kernel is written for).  The launch and t1k_coalesce_limits both ask here.
+static uint32_t coLongRun() {
+  static const uint32_t longRun = getenv("T1K_CO_LONG_RUN") ? (uint32_t)std::max(2 * CO_B + 2, atoi(getenv("T1K_CO_LONG_RUN"))) : (uint32_t)CO_LONG_RUN;  // (0xFFFFFFFF-like values: every group through k_co_reduce)
+  return longRun;
+}
+
 static int rsFail(t1k_rowset *rs, int code, const std::string &m) { if (rs) rs->err = m; return code; }
 #define RS_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return rsFail(rs, T1K_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 
@@ -297,6 +304,11 @@ int t1k_rowset_chunk_full(t1k_rowset *rs, t1k_ctx *, size_t chunk) {
 }
 
 extern "C" {
+
+// TEST-ONLY: the sizes at which the fold changes its route, as this library was built and as this process runs it
+void t1k_coalesce_limits(uint32_t out[3]) {
+  out[0] = CO_B; out[1] = coLongRun(); out[2] = 64;
+}
 
 int t1k_rowset_create(t1k_ctx *owner, uint64_t nFragments, const uint8_t *whitelist, t1k_rowset **out) {
   if (!owner || !out) return T1K_ERR_ARG;
@@ -461,7 +473,7 @@ int t1k_rowset_coalesce_sized(t1k_rowset *rs, uint64_t *nGroups, uint64_t *nEntr
   unsigned long long *ptrSorted = k1;  // the sorted hash words are no longer needed
   hipLaunchKernelGGL(k_co_ptrs, dim3(nbM), dim3(256), 0, st, idx, rs->rowPtr, ptrSorted, M);
   {
-    static const uint32_t longRun = getenv("T1K_CO_LONG_RUN") ? (uint32_t)std::max(2 * CO_B + 2, atoi(getenv("T1K_CO_LONG_RUN"))) : (uint32_t)CO_LONG_RUN;  // (0xFFFFFFFF-like values: every group through k_co_reduce)
+    const uint32_t longRun = coLongRun();
     hipLaunchKernelGGL(k_co_reduce_long, dim3((unsigned)nTiles), dim3(256), 0, st, tileGroup, tilePtr, order, runStart, ptrSorted, gSize, groupPtr,
                        (T1kGroupEnt *)rs->bGroupEnt.p, longRun, 0u);
     hipLaunchKernelGGL(k_co_reduce, dim3((unsigned)((nTiles + 3) / 4)), dim3(256), 0, st, tileGroup, tilePtr, order, runStart, ptrSorted, gSize, groupPtr,
