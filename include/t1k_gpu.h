@@ -316,6 +316,9 @@ typedef void (*t1k_allreduce_fn)(void *dev_f64, uint64_t n, void *user);
 int t1k_em_setup(t1k_ctx *ctx, const uint64_t *rowPtr, const uint32_t *ecIdx, const double *count, const int32_t *ecLen, uint32_t nGroups,
                  uint32_t nEc, t1k_allreduce_fn allreduce, void *user);
 int t1k_em_update(t1k_ctx *ctx, const double *x0, double *x1, double *ecReadCount, double *diff);
+/* TEST-ONLY: the step sizes of t1k_em_update's ordered sums: out[0] = entries per ordered piece (a read group's row and a class are added
+ * one piece at a time, the sum carried from piece to piece), out[1] = entries per step of the class pass (the unit of its prefetches). */
+void t1k_em_limits(uint32_t out[2]);
 
 /* ---- per-barcode allele EM (analyzer --barcodeEM; no counterpart in the reference; estimator: DESIGN §11) ---------------------
  * One independent EM per barcode, the whole iteration loop in one launch.  Barcode b (of the slice [0, nBarcodes)):

@@ -97,6 +97,19 @@ int orc_coverage(void *h, int allele, int *out, int cap) {
   return L;
 }
 
+// Genotyper::EMupdate (Genotyper.hpp:372-421) on a table a test made: CSR over the read groups (rowPtr[nGroups + 1] into ecIdx), the groups'
+// read counts, the classes' lengths.  x1 and n receive nEc doubles each; returns the sum of |x1 - x0|.
+double orc_em_update(const unsigned long long *rowPtr, const unsigned *ecIdx, const double *count, const int *ecLen, unsigned nGroups, unsigned nEc,
+                     const double *x0, double *x1, double *n) {
+  std::vector<std::vector<int>> rows(nGroups);
+  for (unsigned g = 0; g < nGroups; ++g) rows[g].assign(ecIdx + rowPtr[g], ecIdx + rowPtr[g + 1]);
+  std::vector<double> c(count, count + nGroups), a(x0, x0 + nEc), b(nEc), m(nEc);
+  std::vector<int> len(ecLen, ecLen + nEc);
+  const double diff = Oracle::emUpdate(a, b, m, rows, c, len);
+  if (nEc) { memcpy(x1, b.data(), (size_t)nEc * 8); memcpy(n, m.data(), (size_t)nEc * 8); }
+  return diff;
+}
+
 // ---- candidate extraction (oracle_extract.cpp) ----
 int orc_load_reference_fa(void *h, const char *fasta) { return ((Oracle *)h)->loadReferenceFa(fasta); }
 int orc_infer_kmer_length(void *h) { return ((Oracle *)h)->inferKmerLength(); }

@@ -1011,10 +1011,10 @@ void Oracle::setAlleleAbundance(const std::vector<double> &n, std::vector<double
     if (majorAbund[a.majorAllele] > geneMax[a.gene]) geneMax[a.gene] = majorAbund[a.majorAllele];
 }
 
-// Genotyper::EMupdate (Genotyper.hpp:372-421)
+// Genotyper::EMupdate (Genotyper.hpp:372-421); the class count and lengths as arguments (orc_em_update: tables a test made)
 double Oracle::emUpdate(const std::vector<double> &x0, std::vector<double> &x1, std::vector<double> &n,
-                        const std::vector<std::vector<int>> &rows, const std::vector<double> &count) {
-  size_t E = ecAlleles.size();
+                        const std::vector<std::vector<int>> &rows, const std::vector<double> &count, const std::vector<int> &ecLen) {
+  size_t E = ecLen.size();
   std::fill(n.begin(), n.end(), 0.0);
   for (size_t g = 0; g < rows.size(); ++g) {
     double psum = 0;
@@ -1023,13 +1023,17 @@ double Oracle::emUpdate(const std::vector<double> &x0, std::vector<double> &x1, 
     for (int ec : rows[g]) n[ec] += count[g] * (x0[ec] * 1 / psum);
   }
   double diff = 0, norm = 0;
-  for (size_t i = 0; i < E; ++i) norm += n[i] / ecLength[i];
+  for (size_t i = 0; i < E; ++i) norm += n[i] / ecLen[i];
   for (size_t i = 0; i < E; ++i) {
-    double t = n[i] / ecLength[i] / norm;
+    double t = n[i] / ecLen[i] / norm;
     diff += std::fabs(t - x0[i]);
     x1[i] = t;
   }
   return diff;
+}
+double Oracle::emUpdate(const std::vector<double> &x0, std::vector<double> &x1, std::vector<double> &n,
+                        const std::vector<std::vector<int>> &rows, const std::vector<double> &count) {
+  return emUpdate(x0, x1, n, rows, count, ecLength);  // (ecLength has one entry per class: quantify sizes it from ecAlleles)
 }
 
 // Genotyper::QuantifyAlleleEquivalentClass (Genotyper.hpp:1142-1328)

@@ -135,6 +135,9 @@ class Oracle {
   int missingBaseCoverage(int seqIdx, double ratio) const;  // SeqSet.hpp:2717-2755
   void parseAlleleName(const std::string &allele, std::string &gene, std::string &major) const;  // Genotyper.hpp:63-131
 
+  // Genotyper::EMupdate (372-421) with the classes' lengths as an argument (their number is its size): what quantify's updates run
+  static double emUpdate(const std::vector<double> &x0, std::vector<double> &x1, std::vector<double> &n,
+                         const std::vector<std::vector<int>> &rows, const std::vector<double> &count, const std::vector<int> &ecLen);
  private:
   std::vector<uint32_t> idxStart;   // 4^k + 1
   std::vector<Posting> idxPost;

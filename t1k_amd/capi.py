@@ -105,6 +105,9 @@ def lib():
     L.t1k_align_count_batch.argtypes = [vp, C.c_char_p, vp, C.c_char_p, vp, vp, C.c_uint32, vp]
     L.t1k_em_setup.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, ALLREDUCE_FN, vp]
     L.t1k_em_update.argtypes = [vp, vp, vp, vp, vp]
+    L.t1k_em_shard.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    L.t1k_em_limits.argtypes = [vp]
+    L.t1k_em_limits.restype = None
     L.t1k_barcode_em.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int32, vp, vp, C.POINTER(C.c_double)]
     L.t1k_umi_collapse.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int32, vp, C.POINTER(C.c_uint32), vp, vp, vp, vp, vp, vp,
                                    C.POINTER(UmiStats)]
@@ -394,12 +397,29 @@ class Context:
                                                 _ptr(out)), "t1k_align_count_batch")
         return out
 
-    def em_setup(self, row_ptr, ec_idx, count, ec_len, allreduce=None):
-        self._em_keep = (np.asarray(row_ptr, np.uint64), np.asarray(ec_idx, np.uint32), np.asarray(count, np.float64), np.asarray(ec_len, np.int32))
+    def em_setup(self, row_ptr, ec_idx, count, ec_len, allreduce=None, raw=False):
+        """raw=True returns the status code instead of raising (argument-error tests)"""
+        self._em_keep = (np.ascontiguousarray(row_ptr, np.uint64), np.ascontiguousarray(ec_idx, np.uint32), np.ascontiguousarray(count, np.float64),
+                         np.ascontiguousarray(ec_len, np.int32))
         rp, ei, ct, el = self._em_keep
+        assert len(rp) == len(ct) + 1 and int(rp[-1]) == len(ei)
         self._em_cb = ALLREDUCE_FN(allreduce) if allreduce else C.cast(None, ALLREDUCE_FN)
         self._em_nec = len(el)
-        self._check(lib().t1k_em_setup(self.h, _ptr(rp), _ptr(ei), _ptr(ct), _ptr(el), len(ct), len(el), self._em_cb, None), "t1k_em_setup")
+        rc = lib().t1k_em_setup(self.h, _ptr(rp), _ptr(ei), _ptr(ct), _ptr(el), len(ct), len(el), self._em_cb, None)
+        if raw:
+            return rc
+        self._check(rc, "t1k_em_setup")
+
+    def em_shard(self, row_begin, row_end, comm=None, raw=False):
+        """this rank's t1k_em_update sums the read groups [row_begin, row_end) only (t1k_em_shard; collective when comm has several ranks:
+        the ranks' ranges partition the read groups in rank order).  raw=True returns the status code instead of raising"""
+        rc = lib().t1k_em_shard(self.h, row_begin, row_end, comm.h if comm is not None else None)
+        if raw:
+            return rc
+        self._check(rc, "t1k_em_shard")
+
+    def last_error(self):
+        return lib().t1k_last_error(self.h).decode()
 
     def em_update(self, x0):
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
@@ -685,6 +705,13 @@ class Rowset:
         sizes, ent, first = np.zeros(g, dtype=np.uint32), np.zeros(e, dtype=GROUP_DTYPE), np.zeros(g, dtype=np.uint32)
         self._check(lib().t1k_rowset_groups_download_all(self.h, _ptr(sizes), _ptr(ent), _ptr(first)), "t1k_rowset_groups_download_all")
         return sizes, ent, first
+
+
+def em_limits():
+    """(entries per ordered piece, entries per step of the class pass) of t1k_em_update's sums as built"""
+    out = np.zeros(2, dtype=np.uint32)
+    lib().t1k_em_limits(_ptr(out))
+    return tuple(int(x) for x in out)
 
 
 def coalesce_limits():

@@ -20,6 +20,13 @@
 #include "t1k_dev.h"
 #include "t1k_launch.h"
 
+// The two step sizes of the ordered sums (t1k_em_limits reports them): an ordered piece is one wavefront of operands; the class pass takes
+// EM_K pieces per step.
+constexpr int EM_PIECE = 64;
+constexpr int EM_K = 8;
+constexpr uint64_t EM_STEP = (uint64_t)EM_PIECE * EM_K;
+static_assert(EM_PIECE == 64, "an ordered piece is one operand per lane of a wavefront");
+
 // acc + v(lane 0) + v(lane 1) + ... + v(lane cnt-1), added strictly in that order (the floating-point sums of the EM must follow
 // the reference's order).  The operands go through 512 bytes of LDS that belong to the wavefront: every lane reads them back at the same
 // addresses (a broadcast, two doubles a read) and runs the same chain of additions.  Taking them out of the lanes with v_readlane, as
@@ -30,11 +37,11 @@ __device__ __forceinline__ double waveOrderedSum(double v, int cnt, double acc, 
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  if (cnt == 64) {
+  if (cnt == EM_PIECE) {
     // a full wavefront of operands (all but the last piece of a long list): no loop control between the dependent additions -- the
     // chain of one long class is the critical path of the whole E-step
 #pragma unroll
-    for (int j = 0; j < 64; ++j) acc += slot[j];
+    for (int j = 0; j < EM_PIECE; ++j) acc += slot[j];
   } else {
     for (int j = 0; j < cnt; ++j) acc += slot[j];
   }
@@ -47,15 +54,15 @@ __device__ __forceinline__ double waveOrderedSum(double v, int cnt, double acc, 
 __global__ __launch_bounds__(256) void k_em_psum(const uint64_t *rowPtr, const uint32_t *ecIdx, const double *x, double *psumOut, uint32_t nGroups) {
   const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
-  __shared__ __attribute__((aligned(16))) double sOrd[4][64];
+  __shared__ __attribute__((aligned(16))) double sOrd[4][EM_PIECE];
   if (g >= nGroups) return;
   double *slot = sOrd[threadIdx.x >> 6];
   const uint64_t b = rowPtr[g], e = rowPtr[g + 1];
   double psum = 0;
-  for (uint64_t base = b; base < e; base += 64) {
+  for (uint64_t base = b; base < e; base += EM_PIECE) {
     const uint64_t p = base + lane;
     const double v = p < e ? x[ecIdx[p]] : 0.0;
-    psum = waveOrderedSum(v, (int)(e - base < 64 ? e - base : 64), psum, slot, lane);
+    psum = waveOrderedSum(v, (int)(e - base < EM_PIECE ? e - base : EM_PIECE), psum, slot, lane);
   }
   if (psum == 0) psum = 1;
   if (lane == 0) psumOut[g] = psum;
@@ -68,11 +75,11 @@ __global__ __launch_bounds__(256) void k_em_psum(const uint64_t *rowPtr, const u
 // before the additions of this one start.
 __global__ __launch_bounds__(256) void k_em_cols(const uint64_t *colPtr, const uint32_t *rowOf, const double *count, const double *psum, const double *x, double *n, uint32_t nEc,
                                                  uint32_t rowLo, uint32_t rowHi) {
-  constexpr int K = 8;
-  constexpr uint64_t S = 64 * K;
+  constexpr int K = EM_K;
+  constexpr uint64_t S = EM_STEP;
   const uint32_t ec = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
-  __shared__ __attribute__((aligned(16))) double sOrd[4][64];
+  __shared__ __attribute__((aligned(16))) double sOrd[4][EM_PIECE];
   if (ec >= nEc) return;
   double *slot = sOrd[threadIdx.x >> 6];
   const uint64_t b = colPtr[ec], e = colPtr[ec + 1];
@@ -83,7 +90,7 @@ __global__ __launch_bounds__(256) void k_em_cols(const uint64_t *colPtr, const u
   auto rows = [&](uint64_t start) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const uint64_t p = start + 64 * k + lane;
+      const uint64_t p = start + EM_PIECE * k + lane;
       const uint32_t r = p < e ? rowOf[p] : ~0u;
       g[k] = r != ~0u && r - rowLo < rowHi - rowLo ? r : ~0u;
     }
@@ -111,8 +118,8 @@ __global__ __launch_bounds__(256) void k_em_cols(const uint64_t *colPtr, const u
     rows(base + 2 * S);  // the read groups of the piece after next
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const uint64_t cb = base + 64 * k;
-      if (cb < e) s = waveOrderedSum(v[k], (int)(e - cb < 64 ? e - cb : 64), s, slot, lane);
+      const uint64_t cb = base + EM_PIECE * k;
+      if (cb < e) s = waveOrderedSum(v[k], (int)(e - cb < EM_PIECE ? e - cb : EM_PIECE), s, slot, lane);
     }
   }
   if (lane == 0) n[ec] = s;
@@ -429,6 +436,7 @@ int t1k_em_update(t1k_ctx *ctx, const double *x0, double *x1, double *ecReadCoun
   ctx->emMs[3] += 1;
   return T1K_OK;
 }
+void t1k_em_limits(uint32_t out[2]) { out[0] = EM_PIECE; out[1] = (uint32_t)EM_STEP; }
 void t1k_em_times(const t1k_ctx *ctx, double *ms4) { for (int i = 0; i < 4; ++i) ms4[i] = ctx ? ctx->emMs[i] : 0; }
 
 }  // extern "C"

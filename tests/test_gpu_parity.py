@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import em_ref
 import goldens
 import util
 import t1k_amd
@@ -138,7 +139,7 @@ def test_job_api_batching_and_rerun_invariance(built, tmp_path):
 
 @pytest.mark.parametrize("G,E,long_classes", [(3000, 257, False), (20000, 37, True)])
 def test_em_update_bit_exact(ctx, G, E, long_classes):
-    """t1k_em_update vs a sequential numpy restatement of Genotyper::EMupdate (same order of double operations).  The second shape has
+    """t1k_em_update vs the sequential restatement of Genotyper::EMupdate (tests/em_ref.py: same order of double operations).  The second shape has
     classes of thousands of entries (the class pass takes them 512 at a time, 64 to an ordered piece), one of exactly 1024, and an empty one."""
     rng = np.random.default_rng(5)
     if long_classes:
@@ -156,22 +157,7 @@ def test_em_update_bit_exact(ctx, G, E, long_classes):
     x0[rng.integers(0, E, 20)] = 0.0
     ctx.em_setup(row_ptr, ec_idx, count, ec_len)
     x1, n, diff = ctx.em_update(x0)
-    n_ref = np.zeros(E)
-    for g, r in enumerate(rows):
-        psum = 0.0
-        for e in r:
-            psum += x0[e]
-        if psum == 0:
-            psum = 1
-        for e in r:
-            n_ref[e] += count[g] * (x0[e] / psum)
-    norm = 0.0
-    for i in range(E):
-        norm += n_ref[i] / ec_len[i]
-    x_ref = np.array([n_ref[i] / ec_len[i] / norm for i in range(E)])
-    d_ref = 0.0
-    for i in range(E):
-        d_ref += abs(x_ref[i] - x0[i])
+    x_ref, n_ref, d_ref = em_ref.em_update_ref(row_ptr, ec_idx, count, ec_len, x0)
     assert np.array_equal(n, n_ref) and np.array_equal(x1, x_ref) and diff == d_ref
 
 

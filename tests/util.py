@@ -198,6 +198,19 @@ class Oracle:
         self.L.orc_coverage(self.h, allele, out.ctypes.data, length)
         return out
 
+    @staticmethod
+    def em_update(row_ptr, ec_idx, count, ec_len, x0):
+        """Genotyper::EMupdate on a table a test made (orc_em_update: the routine the oracle's own quantify runs): (x1, n, diff)"""
+        L = C.CDLL(ORACLE_SO)
+        L.orc_em_update.restype = C.c_double
+        L.orc_em_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+        rp, ei = np.ascontiguousarray(row_ptr, np.uint64), np.ascontiguousarray(ec_idx, np.uint32)
+        ct, el, x = np.ascontiguousarray(count, np.float64), np.ascontiguousarray(ec_len, np.int32), np.ascontiguousarray(x0, np.float64)
+        assert len(rp) == len(ct) + 1 and int(rp[-1]) == len(ei) and len(x) == len(el)
+        x1, n = np.zeros(len(el), np.float64), np.zeros(len(el), np.float64)
+        diff = L.orc_em_update(rp.ctypes.data, ei.ctypes.data, ct.ctypes.data, el.ctypes.data, len(ct), len(el), x.ctypes.data, x1.ctypes.data, n.ctypes.data)
+        return x1, n, diff
+
     def global_alignment(self, t, p):
         ops = np.zeros(len(t) + len(p) + 2, dtype=np.int8)
         n = C.c_int()
