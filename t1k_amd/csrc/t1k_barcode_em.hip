@@ -17,6 +17,7 @@
 #include <cstring>
 #include <numeric>
 #include "t1k_dev.h"
+#include "t1k_launch.h"
 
 static constexpr int kWaves = 4;              // barcodes (waves) per workgroup
 static constexpr uint32_t kArenaWords = 2048; // LDS per wave: 8 KiB -> 4 x 8.5 KiB per workgroup, four workgroups per CU
@@ -242,19 +243,16 @@ int t1k_barcode_em(t1k_ctx *ctx, uint32_t nBarcodes, const uint64_t *bcAllelePtr
   for (auto &x : bAP) x -= aB;
   for (auto &x : bGP) x -= gB;
   if (nG) for (uint64_t g = 0; g <= nG; ++g) gEP[g] = groupEntryPtr[gB + g] - eB;
-  size_t off = 0;
-  auto piece = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256 + 256; return o; };
+  T1kCarve piece;
   const size_t oOrder = piece(4ull * nBarcodes), oAP = piece(8 * bAP.size()), oGP = piece(8 * bGP.size()), oEP = piece(8 * gEP.size()), oCP = piece(8 * colPtr.size()),
                oEL = piece(4 * nE), oCG = piece(4 * nE), oCnt = piece(8 * nG), oPri = piece(8 * prior.size()), oTh = piece(8 * nL), oPs = piece(8 * nG),
                oN = piece(8 * nL), oIt = piece(4ull * nBarcodes), oCur = piece(16);
   T1K_HIP(ctx, hipSetDevice(ctx->device));
-  T1kDevBuf blk;
+  T1kCallBlock blk;  // (freed on every return, behind the stream's work)
   int rc;
-  if ((rc = t1k_ensure(ctx, blk, off))) return rc;
+  if ((rc = blk.alloc(ctx, piece.off))) return rc;
   hipStream_t st = ctx->stream;
-  // (on every return: the stream drained first, so that no launch of this call still uses the block the pool hands out again)
-  struct Free { void *p; hipStream_t s; ~Free() { (void)hipStreamSynchronize(s); (void)t1k_dev_free(p); } } guard{blk.p, st};
-  char *D = (char *)blk.p;
+  char *D = (char *)blk.buf.p;
   auto put = [&](size_t o, const void *src, size_t bytes) -> hipError_t { return bytes ? hipMemcpyAsync(D + o, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
   T1K_HIP(ctx, put(oOrder, order.data(), 4ull * nBarcodes));
   T1K_HIP(ctx, put(oAP, bAP.data(), 8 * bAP.size()));
@@ -274,9 +272,7 @@ int t1k_barcode_em(t1k_ctx *ctx, uint32_t nBarcodes, const uint64_t *bcAllelePtr
   a.alpha = alpha; a.tol = tol; a.maxIter = maxIter; a.nBarcodes = nBarcodes; a.budget = budget;
   a.theta = (double *)(D + oTh); a.psum = (double *)(D + oPs); a.n = (double *)(D + oN); a.iters = (int32_t *)(D + oIt); a.cursor = (unsigned *)(D + oCur);
   // persistent waves: at most four workgroups per CU (the LDS arena's occupancy), fewer when there are fewer barcodes
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-  const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * 4, (nBarcodes + kWaves - 1) / kWaves));
+  const unsigned blocks = t1k_grid(ctx, nBarcodes, kWaves, 4);
   T1K_HIP(ctx, hipEventRecord(ctx->ev[0], st));
   hipLaunchKernelGGL(k_barcode_em, dim3(blocks), dim3(64 * kWaves), 0, st, a);
   T1K_HIP(ctx, hipGetLastError());

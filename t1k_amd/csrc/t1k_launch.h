@@ -1,5 +1,6 @@
 // t1k_amd/csrc/t1k_launch.h -- internal: kernel argument blocks and host launchers shared by the .hip files
 #pragma once
+#include <algorithm>
 #include <mutex>
 #include "t1k_dev.h"
 
@@ -133,10 +134,43 @@ struct t1k_rowset {
   hipStream_t copyStream = nullptr; // t1k_rowset_assigned_range: copies beside the pipelines (non-blocking stream)
   std::string err;
 };
+// ---- small host helpers of the device stages (beside t1k_ensure, t1k_dev.h) ----
+// offsets of the pieces of one device block, in the order asked for: every piece starts 256-byte aligned and has 256 bytes behind it;
+// `off` ends as the size of the block
+struct T1kCarve {
+  size_t off = 0;
+  size_t operator()(size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256 + 256; return o; }
+};
+// a device block that lives for one call.  On every return: the stream drained first, so that no launch of the call still uses the
+// block the pool hands out again
+struct T1kCallBlock {
+  T1kDevBuf buf;
+  hipStream_t stream = nullptr;
+  T1kCallBlock() = default;
+  T1kCallBlock(const T1kCallBlock &) = delete;
+  T1kCallBlock &operator=(const T1kCallBlock &) = delete;
+  int alloc(t1k_ctx *ctx, size_t bytes) { stream = ctx->stream; return t1k_ensure(ctx, buf, bytes); }
+  ~T1kCallBlock() {
+    if (!buf.p) return;
+    (void)hipStreamSynchronize(stream);
+    (void)t1k_dev_free(buf.p);
+  }
+};
+// workgroups of a grid-stride launch over `items`, perBlock of them per workgroup and pass: enough for all, at most blocksPerCu per CU, at least one
+inline unsigned t1k_grid(t1k_ctx *ctx, uint64_t items, uint32_t perBlock, uint32_t blocksPerCu = 16) {
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * blocksPerCu, (items + perBlock - 1) / perBlock));
+}
+inline int t1k_bits(unsigned long long v) {  // bits that hold every value <= v (at least 1)
+  int b = 1;
+  while (b < 64 && (v >> b)) ++b;
+  return b;
+}
+
 int t1k_rowset_chunk(t1k_rowset *rs, t1k_ctx *ctx, size_t *chunk, t1k_row_entry **rows, uint64_t *cap, unsigned long long **cursor);
 int t1k_rowset_chunk_full(t1k_rowset *rs, t1k_ctx *ctx, size_t chunk);
 int t1k_exclusive_sum64(t1k_ctx *ctx, const uint32_t *in, unsigned long long *out, uint32_t n);
-int t1k_inclusive_sum_n(t1k_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n);
 int t1k_exclusive_sum32(t1k_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n);
 int t1k_exclusive_sum_u64(t1k_ctx *ctx, const unsigned long long *in, unsigned long long *out, uint64_t n);
 
@@ -157,7 +191,7 @@ void t1k_launch_fullalign_slow(t1k_ctx *ctx, const SlowArgs &a, int nBlocks);
 void t1k_launch_align_flags(t1k_ctx *ctx, const SlowArgs &a, uint32_t *flags);
 void t1k_launch_align_reps(t1k_ctx *ctx, const uint32_t *flags, const uint32_t *runOf, uint32_t *rep, uint32_t n);
 void t1k_launch_align_fill_apply(t1k_ctx *ctx, const SlowArgs &a, bool eq);
-int t1k_inclusive_sum(t1k_ctx *ctx, const uint32_t *in, uint32_t *out, uint32_t n);
+int t1k_inclusive_sum(t1k_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n);
 void t1k_launch_truncate(t1k_ctx *ctx, const TruncArgs &a, int nWg);
 void t1k_launch_coverage_scan(t1k_ctx *ctx, const T1kRefDev &ref, int32_t *out, const uint64_t *outOff);
 int t1k_fetch_counters(t1k_ctx *ctx, unsigned long long *h);
@@ -175,6 +209,11 @@ uint64_t t1k_arena_estimate(const t1k_ctx *ctx, int arena, uint64_t cap, uint32_
 void t1k_arena_estimate_set(t1k_ctx *ctx, int arena, uint64_t total, uint32_t nRe);
 void t1k_launch_extend_retry_dev(t1k_ctx *ctx, const ExtendArgs &a, const uint32_t *list, int arena, uint64_t est);
 void t1k_arena_compact64(t1k_ctx *ctx, int arena, const unsigned long long *src, uint32_t segCap, unsigned long long *dst, uint32_t maxSeg);
+// keys[0 .. n) ascending -> runStart[0 .. runs] (runStart[runs] = n), runKey[0 .. runs), *runs on the host (one small copy back, stream
+// synchronised).  flag and scan are scratch of n + 1 words each (left as: flag[i] = position i starts a run, scan[i] = runs in front
+// of position i).  lone (or NULL): a key equal to *lone never joins a run.
+int t1k_run_table(t1k_ctx *ctx, const unsigned long long *keys, uint32_t n, const unsigned long long *lone,
+                  uint32_t *flag, uint32_t *scan, uint32_t *runStart, unsigned long long *runKey, uint32_t *runs);
 int t1k_sort_pairs(t1k_ctx *ctx, const unsigned long long *keysIn, unsigned long long *keysOut, const uint32_t *valsIn, uint32_t *valsOut, uint32_t n, int endBit = 64);
 void t1k_arena_compact(t1k_ctx *ctx, int arena, const uint32_t *src, uint32_t segCap, uint32_t *dst, uint32_t maxSeg);
 

@@ -337,7 +337,7 @@ extern "C" int t1k_ref_upload(t1k_ctx *ctx, const char *seqs, const uint64_t *of
   if ((rc = t1k_ensure(ctx, bNeed, (nKeys + 1) * 4)) || (rc = t1k_ensure(ctx, bRowOf, (nKeys + 1) * 4))) { freeScratch2(); return rc; }
   hipLaunchKernelGGL(k_ref_flags, dim3((unsigned)((nKeys + 255) / 256)), dim3(256), 0, st, (const uint32_t *)dKStart, (const uint32_t *)dPostAllele, nKeys, k, (uint32_t *)dHas,
                      (uint32_t *)dMulti, (uint32_t *)dHasPre, (uint32_t *)bNeed.p);
-  if ((rc = t1k_inclusive_sum_n(ctx, (const uint32_t *)bNeed.p, (uint32_t *)bRowOf.p, nKeys))) { freeScratch2(); return rc; }
+  if ((rc = t1k_inclusive_sum(ctx, (const uint32_t *)bNeed.p, (uint32_t *)bRowOf.p, nKeys))) { freeScratch2(); return rc; }
   uint32_t rows = 0;
   RU_HIP(hipMemcpyAsync(&rows, (uint32_t *)bRowOf.p + (nKeys - 1), 4, hipMemcpyDeviceToHost, st));
   RU_HIP(hipStreamSynchronize(st));

@@ -4,7 +4,8 @@
 //
 // Sites: a bitmap over the allele-offset space (bit alleleOff[a] + p) and a rank directory (sites in front of each 64-bit word): a lane
 // maps its allele position to a site index with one bit test and one population count.
-// One kernel, two instantiations, one wave64 per record, the walk of k_pileup (t1k_walk.h):
+// One kernel, two instantiations, one wave64 per record; the record header, the walk and its verdict are k_pileup's, and so is the host's
+// front end of a batch (all in t1k_walk.h):
 //   k_sitepile<false>  check and count: the walk's checks (an op outside 0 .. 3, a walk that leaves its allele or the text) and per record
 //                      hits x bookings, hits = its columns that book at a site.  Only when the flag word comes back clear does the host
 //                      take the exclusive sum of the counts and launch
@@ -14,7 +15,7 @@
 // counts in the plain counter as well as in the _uniq one where the runs are read: the reader of t1k_sitepile_get adds the even run of a
 // cell to its plain counter (plain = even + odd, _uniq = even).  So no booking is ever stored twice.
 // Fold: the table is (key, count) pairs followed by the pending keys (count 1).  t1k_sort_pairs over the bits of the largest possible
-// key, head flags + exclusive scan number the runs, an inclusive scan of the counts (uint32, exact modulo 2^32) gives every run's sum as
+// key, t1k_run_table (t1k_sort.hip) numbers the runs, an inclusive scan of the counts (uint32, exact modulo 2^32) gives every run's sum as
 // the difference of the scan at its last element and at the previous run's last element: a run's sum is at most (2^31 - 1) + the pending
 // keys < 2^32, so the difference is exact, and no lane ever walks a run.  A sum beyond 2^31 - 1 refuses the fold (T1K_ERR_CAPACITY) and
 // leaves the table as it was.  The table is folded whenever the pending keys reach a bound (2^28, env T1K_SITEPILE_PENDING) and at _get.
@@ -28,12 +29,7 @@
 enum { SITEPILE_BASE_PLANES = 7 };
 
 struct SitepileArgs {
-  const t1k_pileup_aln *aln;
-  uint32_t n;
-  const char *text;
-  unsigned long long textBytes;
-  const int8_t *ops;
-  const unsigned long long *alleleOff;  // [nAlleles + 1]
+  PileupBatch in;
   const unsigned long long *bits;       // [total / 64 + 1] bit alleleOff[a] + p = (a, p) is a site
   const uint32_t *rank;                 // [total / 64 + 1] sites in front of the word
   unsigned long long nSites;
@@ -42,25 +38,21 @@ struct SitepileArgs {
   unsigned long long *count;            // [n + 1]: <false> writes hits x bookings, <true> reads their exclusive sums
   unsigned long long *keys;             // <true>: the pending keys of this call
   uint32_t *vals;                       //         and their counts (1 each)
-  uint32_t *flag;
 };
 
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_sitepile(SitepileArgs P) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t nWaves = gridDim.x * 4u;
-  for (uint32_t r = pileupUniform(blockIdx.x * 4u + (threadIdx.x >> 6)); r < P.n; r += nWaves) {
-    const t1k_pileup_aln *rec = P.aln + r;
-    const uint32_t allele = pileupUniform(rec->allele), seqStart = pileupUniform(rec->seq_start), nOps = pileupUniform(rec->n_ops);
-    const unsigned long long readAt = pileupUniform64(rec->read_at), opsAt = pileupUniform64(rec->ops_at);
+  for (uint32_t r = pileupUniform(blockIdx.x * 4u + (threadIdx.x >> 6)); r < P.in.n; r += nWaves) {
     const unsigned long long bookAt = pileupUniform64(P.bookPtr[r]);
     const uint32_t nBook = (uint32_t)(pileupUniform64(P.bookPtr[r + 1]) - bookAt);
     if (EMIT && nBook == 0) continue;
-    const unsigned long long base = pileupUniform64(P.alleleOff[allele]);
-    const unsigned long long len = pileupUniform64(P.alleleOff[allele + 1]) - base;
+    const PileupRec R = pileupLoadRec(P.in.aln, P.in.alleleOff, r);  // (its weights are not read here)
+    const unsigned long long base = R.base, len = R.len, readAt = R.readAt;
     unsigned long long slot = EMIT ? pileupUniform64(P.count[r]) : 0ull;  // wave-uniform: the next free key of this record
     unsigned long long hits = 0;
-    const PileupWalkEnd end = pileupWalk<!EMIT, true>(P.ops, opsAt, nOps, seqStart, len, lane, [&](bool active, int op, unsigned long long pos, unsigned long long myP) {
+    const PileupWalkEnd end = pileupWalk<!EMIT, true>(P.in.ops, R.opsAt, R.nOps, R.seqStart, len, lane, [&](bool active, int op, unsigned long long pos, unsigned long long myP) {
       bool hit = false;
       uint32_t site = 0;
       if (active && pos < len) {  // (pos >= len: only in the check pass, on a walk it is about to refuse)
@@ -73,7 +65,7 @@ __global__ __launch_bounds__(256) void k_sitepile(SitepileArgs P) {
       if (!EMIT) { hits += h; return; }
       if (h == 0) return;  // wave-uniform
       unsigned long long cell = 0;
-      if (hit) cell = (unsigned long long)site * SITEPILE_BASE_PLANES + (op == 2 ? (uint32_t)PILEUP_INS : op == 3 ? (uint32_t)PILEUP_DEL : pileupBasePlane(P.text[readAt + myP]));
+      if (hit) cell = (unsigned long long)site * SITEPILE_BASE_PLANES + (op == 2 ? (uint32_t)PILEUP_INS : op == 3 ? (uint32_t)PILEUP_DEL : pileupBasePlane(P.in.text[readAt + myP]));
       const unsigned long long mine = slot + pileupBelow(mH);
       for (uint32_t b = 0; b < nBook; ++b) {
         const uint32_t e = pileupUniform(P.book[bookAt + b]);
@@ -86,52 +78,23 @@ __global__ __launch_bounds__(256) void k_sitepile(SitepileArgs P) {
       slot += (unsigned long long)h * nBook;
     });
     if (!EMIT) {
-      uint32_t bad = end.bad;
-      if (len == 0 || end.t > len) bad |= PILEUP_BAD_ALLELE_WALK;
-      if (readAt + end.p > P.textBytes) bad |= PILEUP_BAD_TEXT_WALK;
+      const uint32_t bad = pileupWalkVerdict(end, len, readAt, P.in.textBytes);
       if (lane == 0) {
-        if (bad) atomicOr(P.flag, bad);
+        if (bad) atomicOr(P.in.flag, bad);
         P.count[r] = hits * nBook;
       }
     }
   }
 }
 
-// flag[i] = position i starts a run of equal keys; flag[n] = 0 for the scan's total
-__global__ __launch_bounds__(256) void k_sitepile_heads(const unsigned long long *keys, uint32_t n, uint32_t *flag) {
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i <= n; i += gridDim.x * 256u) flag[i] = (i < n && (i == 0 || keys[i - 1] != keys[i])) ? 1u : 0u;
-}
-
-// the last element of run r = scan[i] + flag[i] - 1 writes the run's key and the inclusive sum of the counts up to it
-__global__ __launch_bounds__(256) void k_sitepile_tails(const unsigned long long *keys, uint32_t n, const uint32_t *flag, const uint32_t *scan, const uint32_t *incl,
-                                                         unsigned long long *runKey, uint32_t *runEnd) {
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-    if (i + 1 < n && keys[i + 1] == keys[i]) continue;
-    const uint32_t r = scan[i] + flag[i] - 1u;
-    runKey[r] = keys[i];
-    runEnd[r] = incl[i];
-  }
-}
-
-// count of run r = runEnd[r] - runEnd[r - 1] modulo 2^32 (exact: see the header); beyond 2^31 - 1 sets *over
-__global__ __launch_bounds__(256) void k_sitepile_counts(const uint32_t *runEnd, uint32_t nRuns, uint32_t *runCount, uint32_t *over) {
+// count of run r = the inclusive sum of the sorted counts at its last element minus that at the previous run's, modulo 2^32 (exact: see
+// the header); beyond 2^31 - 1 sets *over
+__global__ __launch_bounds__(256) void k_sitepile_counts(const uint32_t *incl, const uint32_t *runStart, uint32_t nRuns, uint32_t *runCount, uint32_t *over) {
   for (uint32_t r = blockIdx.x * 256u + threadIdx.x; r < nRuns; r += gridDim.x * 256u) {
-    const uint32_t c = runEnd[r] - (r ? runEnd[r - 1] : 0u);
+    const uint32_t c = incl[runStart[r + 1] - 1] - (r ? incl[runStart[r] - 1] : 0u);
     runCount[r] = c;
     if (c > 0x7FFFFFFFu) atomicOr(over, 1u);
   }
-}
-
-static unsigned sitepileGrid(t1k_ctx *ctx, uint64_t items, uint32_t perBlock) {
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * 16, (items + perBlock - 1) / perBlock));
-}
-
-static int sitepileBits(unsigned long long v) {  // bits that hold every value <= v (at least 1)
-  int b = 1;
-  while (b < 64 && (v >> b)) ++b;
-  return b;
 }
 
 // room for `want` (key, count) pairs in the table; what it holds is kept
@@ -165,31 +128,23 @@ static int sitepileFold(t1k_ctx *ctx) {
   if (ctx->spPending == 0 || n64 == 0) return T1K_OK;
   const uint32_t n = (uint32_t)n64;  // (< 2^31: t1k_sitepile_add)
   hipStream_t st = ctx->stream;
-  size_t off = 0;
-  auto piece = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256 + 256; return o; };
+  T1kCarve piece;
   const size_t oKey = piece(8ull * n), oVal = piece(4ull * n), oFlag = piece(4ull * (n + 1ull)), oScan = piece(4ull * (n + 1ull)), oIncl = piece(4ull * n),
-               oRunKey = piece(8ull * n), oRunEnd = piece(4ull * n), oRunCount = piece(4ull * n), oOver = piece(8);
+               oRunKey = piece(8ull * n), oRunStart = piece(4ull * (n + 1ull)), oRunCount = piece(4ull * n), oOver = piece(8);
   int rc;
-  if ((rc = t1k_ensure(ctx, ctx->bSpWork, off))) return rc;
+  if ((rc = t1k_ensure(ctx, ctx->bSpWork, piece.off))) return rc;
   char *D = (char *)ctx->bSpWork.p;
   unsigned long long *keyB = (unsigned long long *)(D + oKey), *runKey = (unsigned long long *)(D + oRunKey);
-  uint32_t *valB = (uint32_t *)(D + oVal), *flag = (uint32_t *)(D + oFlag), *scan = (uint32_t *)(D + oScan), *incl = (uint32_t *)(D + oIncl), *runEnd = (uint32_t *)(D + oRunEnd),
+  uint32_t *valB = (uint32_t *)(D + oVal), *flag = (uint32_t *)(D + oFlag), *scan = (uint32_t *)(D + oScan), *incl = (uint32_t *)(D + oIncl), *runStart = (uint32_t *)(D + oRunStart),
            *runCount = (uint32_t *)(D + oRunCount), *over = (uint32_t *)(D + oOver);
   T1K_HIP(ctx, hipEventRecord(ctx->ev[2], st));
   T1K_HIP(ctx, hipMemsetAsync(over, 0, 8, st));
   if ((rc = t1k_sort_pairs(ctx, (const unsigned long long *)ctx->bSpKeys.p, keyB, (const uint32_t *)ctx->bSpVals.p, valB, n, ctx->spEndBit))) return rc;
-  const unsigned grid = sitepileGrid(ctx, (uint64_t)n + 1, 256);
-  hipLaunchKernelGGL(k_sitepile_heads, dim3(grid), dim3(256), 0, st, (const unsigned long long *)keyB, n, flag);
-  T1K_HIP(ctx, hipGetLastError());
-  if ((rc = t1k_exclusive_sum32(ctx, flag, scan, (uint64_t)n + 1))) return rc;
-  if ((rc = t1k_inclusive_sum_n(ctx, valB, incl, n))) return rc;
-  hipLaunchKernelGGL(k_sitepile_tails, dim3(grid), dim3(256), 0, st, (const unsigned long long *)keyB, n, (const uint32_t *)flag, (const uint32_t *)scan, (const uint32_t *)incl, runKey, runEnd);
-  T1K_HIP(ctx, hipGetLastError());
   uint32_t nRuns = 0;
-  T1K_HIP(ctx, hipMemcpyAsync(&nRuns, scan + n, 4, hipMemcpyDeviceToHost, st));
-  T1K_HIP(ctx, hipStreamSynchronize(st));
+  if ((rc = t1k_run_table(ctx, keyB, n, nullptr, flag, scan, runStart, runKey, &nRuns))) return rc;
   if (nRuns == 0 || nRuns > n) return t1k_fail(ctx, T1K_ERR_INTERNAL, "t1k_sitepile: the runs of the fold do not add up");
-  hipLaunchKernelGGL(k_sitepile_counts, dim3(sitepileGrid(ctx, nRuns, 256)), dim3(256), 0, st, (const uint32_t *)runEnd, nRuns, runCount, over);
+  if ((rc = t1k_inclusive_sum(ctx, valB, incl, n))) return rc;
+  hipLaunchKernelGGL(k_sitepile_counts, dim3(t1k_grid(ctx, nRuns, 256)), dim3(256), 0, st, (const uint32_t *)incl, (const uint32_t *)runStart, nRuns, runCount, over);
   T1K_HIP(ctx, hipGetLastError());
   uint32_t hOver = 0;
   T1K_HIP(ctx, hipMemcpyAsync(&hOver, over, 4, hipMemcpyDeviceToHost, st));
@@ -212,11 +167,10 @@ extern "C" {
 int t1k_sitepile_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos, uint64_t nBarcodes) {
   if (!ctx) return T1K_ERR_ARG;
   if (ctx->spOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_sitepile_begin: a table is open already (t1k_sitepile_end first)");
-  if (!alleleOff || alleleOff[0] != 0 || (nSites && (!siteAllele || !sitePos))) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_begin: bad arguments (NULL arrays, or alleleOff not starting at 0)");
-  for (uint32_t a = 0; a < nAlleles; ++a)
-    if (alleleOff[a + 1] < alleleOff[a]) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_begin: the allele offsets decrease");
+  if (nSites && (!siteAllele || !sitePos)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_begin: bad arguments (NULL arrays, or alleleOff not starting at 0)");
+  int rc;
+  if ((rc = pileupCheckOffsets(ctx, "t1k_sitepile_begin", "NULL arrays, or alleleOff not starting at 0", nAlleles, alleleOff))) return rc;
   const uint64_t total = alleleOff[nAlleles];
-  if (total >= (1ull << 32)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_sitepile_begin: more than 2^32 allele positions");
   if (nSites > total) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_begin: more sites than allele positions (the sites are not strictly ascending)");
   // a booking names its barcode in 31 bits; the largest key, nBarcodes * nSites * 14 - 1, must leave the top bit of the 64 alone
   if (nBarcodes > (1ull << 31)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_sitepile_begin: more than 2^31 barcodes");
@@ -236,11 +190,9 @@ int t1k_sitepile_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOf
   for (uint64_t w = 1; w < words; ++w) rank[w] = rank[w - 1] + (uint32_t)__builtin_popcountll(bits[w - 1]);
   T1K_HIP(ctx, hipSetDevice(ctx->device));
   // [bits | rank | alleleOff]
-  size_t off = 0;
-  auto piece = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256 + 256; return o; };
+  T1kCarve piece;
   const size_t oBits = piece(8 * words), oRank = piece(4 * words), oOff = piece(8ull * (nAlleles + 1));
-  int rc;
-  if ((rc = t1k_ensure(ctx, ctx->bSpSites, off))) return rc;
+  if ((rc = t1k_ensure(ctx, ctx->bSpSites, piece.off))) return rc;
   char *D = (char *)ctx->bSpSites.p;
   T1K_HIP(ctx, hipMemcpyAsync(D + oBits, bits.data(), 8 * words, hipMemcpyHostToDevice, ctx->stream));
   T1K_HIP(ctx, hipMemcpyAsync(D + oRank, rank.data(), 4 * words, hipMemcpyHostToDevice, ctx->stream));
@@ -250,7 +202,7 @@ int t1k_sitepile_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOf
   ctx->spSiteAt[0] = oBits; ctx->spSiteAt[1] = oRank; ctx->spSiteAt[2] = oOff;
   ctx->spSites = nSites;
   ctx->spBarcodes = nBarcodes;
-  ctx->spEndBit = sitepileBits(space ? (unsigned long long)(space - 1) : 0ull);
+  ctx->spEndBit = t1k_bits(space ? (unsigned long long)(space - 1) : 0ull);
   ctx->spRuns = ctx->spPending = ctx->spEmitted = ctx->spFolds = 0;
   ctx->spFoldMs = 0;
   ctx->spBound = 1ull << 28;
@@ -266,16 +218,12 @@ int t1k_sitepile_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const 
   if (!ctx->spOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_sitepile_add: no table is open (t1k_sitepile_begin first)");
   if (n == 0) return T1K_OK;
   if (!aln || !bookPtr || (textBytes && !text) || (opsBytes && !ops)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: bad arguments (NULL arrays)");
-  const uint32_t nAlleles = (uint32_t)ctx->spOff.size() - 1;
   // what the host can tell from the records and the booking lists alone; the strings themselves are walked on the device before anything is emitted
   for (uint32_t i = 0; i < n; ++i) {
-    const t1k_pileup_aln &r = aln[i];
     if (bookPtr[i + 1] < bookPtr[i]) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: bookPtr decreases at record " + std::to_string(i));
     if (bookPtr[i + 1] - bookPtr[i] >= (1ull << 32)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_sitepile_add: record " + std::to_string(i) + " has 2^32 bookings or more");
-    if (r.allele >= nAlleles) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: record " + std::to_string(i) + " names an unknown allele");
-    if (r.ops_at > opsBytes || r.n_ops > opsBytes - r.ops_at) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: the edit string of record " + std::to_string(i) + " leaves `ops`");
-    if (r.read_at > textBytes) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: the read window of record " + std::to_string(i) + " starts behind `text`");
-    if (r.seq_start > ctx->spOff[r.allele + 1] - ctx->spOff[r.allele]) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: record " + std::to_string(i) + " starts behind its allele");
+    const std::string fault = pileupRecordFault(aln[i], i, ctx->spOff, textBytes, opsBytes);
+    if (!fault.empty()) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: " + fault);
   }
   const uint64_t book0 = bookPtr[0], nBook = bookPtr[n] - book0;
   if (nBook && !book) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: bad arguments (NULL book)");
@@ -285,40 +233,31 @@ int t1k_sitepile_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const 
   for (uint32_t i = 0; i <= n; ++i) bp[i] = bookPtr[i] - book0;
   T1K_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  size_t off = 0;
-  auto piece = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256 + 256; return o; };
-  const size_t oAln = piece(sizeof(t1k_pileup_aln) * (size_t)n), oText = piece(textBytes), oOps = piece(opsBytes), oBp = piece(8ull * (n + 1ull)), oBook = piece(4 * nBook),
-               oCount = piece(8ull * (n + 1ull)), oFlag = piece(4);
+  const char *S = (const char *)ctx->bSpSites.p;
+  SitepileArgs a{};
+  a.in = PileupBatch{aln, n, text, textBytes, ops, (const unsigned long long *)(S + ctx->spSiteAt[2]), nullptr};
+  size_t oBp = 0, oBook = 0, oCount = 0;
   int rc;
-  if ((rc = t1k_ensure(ctx, ctx->bSpIn, off))) return rc;
+  if ((rc = pileupStage(ctx, ctx->bSpIn, opsBytes, [&](T1kCarve &piece) { oBp = piece(8ull * (n + 1ull)); oBook = piece(4 * nBook); oCount = piece(8ull * (n + 1ull)); }, a.in))) return rc;
   char *D = (char *)ctx->bSpIn.p;
-  T1K_HIP(ctx, hipMemcpyAsync(D + oAln, aln, sizeof(t1k_pileup_aln) * (size_t)n, hipMemcpyHostToDevice, st));
-  if (textBytes) T1K_HIP(ctx, hipMemcpyAsync(D + oText, text, textBytes, hipMemcpyHostToDevice, st));
-  if (opsBytes) T1K_HIP(ctx, hipMemcpyAsync(D + oOps, ops, opsBytes, hipMemcpyHostToDevice, st));
   T1K_HIP(ctx, hipMemcpyAsync(D + oBp, bp.data(), 8ull * (n + 1ull), hipMemcpyHostToDevice, st));
   if (nBook) T1K_HIP(ctx, hipMemcpyAsync(D + oBook, book + book0, 4 * nBook, hipMemcpyHostToDevice, st));
   T1K_HIP(ctx, hipMemsetAsync(D + oCount, 0, 8ull * (n + 1ull), st));
-  T1K_HIP(ctx, hipMemsetAsync(D + oFlag, 0, 4, st));
-  SitepileArgs a{};
-  a.aln = (const t1k_pileup_aln *)(D + oAln); a.n = n; a.text = D + oText; a.textBytes = textBytes; a.ops = (const int8_t *)(D + oOps);
-  const char *S = (const char *)ctx->bSpSites.p;
-  a.bits = (const unsigned long long *)(S + ctx->spSiteAt[0]); a.rank = (const uint32_t *)(S + ctx->spSiteAt[1]); a.alleleOff = (const unsigned long long *)(S + ctx->spSiteAt[2]);
+  a.bits = (const unsigned long long *)(S + ctx->spSiteAt[0]); a.rank = (const uint32_t *)(S + ctx->spSiteAt[1]);
   a.nSites = ctx->spSites;
   a.bookPtr = (const unsigned long long *)(D + oBp); a.book = (const uint32_t *)(D + oBook);
-  a.count = (unsigned long long *)(D + oCount); a.flag = (uint32_t *)(D + oFlag);
-  const unsigned grid = sitepileGrid(ctx, n, 4);
+  a.count = (unsigned long long *)(D + oCount);
+  const unsigned grid = t1k_grid(ctx, n, 4);
   T1K_HIP(ctx, hipEventRecord(ctx->ev[0], st));
   hipLaunchKernelGGL(k_sitepile<false>, dim3(grid), dim3(256), 0, st, a);
   T1K_HIP(ctx, hipGetLastError());
   if ((rc = t1k_exclusive_sum_u64(ctx, a.count, a.count, (uint64_t)n + 1))) return rc;  // (in place: every tile is read before it is written)
   uint32_t flag = 0;
   unsigned long long emit = 0;
-  T1K_HIP(ctx, hipMemcpyAsync(&flag, a.flag, 4, hipMemcpyDeviceToHost, st));
+  T1K_HIP(ctx, hipMemcpyAsync(&flag, a.in.flag, 4, hipMemcpyDeviceToHost, st));
   T1K_HIP(ctx, hipMemcpyAsync(&emit, a.count + n, 8, hipMemcpyDeviceToHost, st));
   T1K_HIP(ctx, hipStreamSynchronize(st));
-  if (flag)
-    return t1k_fail(ctx, T1K_ERR_ARG, std::string("t1k_sitepile_add: nothing emitted:") + ((flag & PILEUP_BAD_OP) ? " an op outside 0 .. 3;" : "") +
-                                          ((flag & PILEUP_BAD_ALLELE_WALK) ? " a walk leaves its allele;" : "") + ((flag & PILEUP_BAD_TEXT_WALK) ? " a walk leaves `text`;" : ""));
+  if (flag) return t1k_fail(ctx, T1K_ERR_ARG, pileupRefusal("t1k_sitepile_add", "nothing emitted", flag));
   if (emit == 0) {
     T1K_HIP(ctx, hipEventRecord(ctx->ev[1], st));
     T1K_HIP(ctx, hipStreamSynchronize(st));

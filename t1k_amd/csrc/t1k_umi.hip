@@ -4,8 +4,8 @@
 // Everything is a sort, a run table or a lane per item; no float atomic, no order of arrival in any result:
 //   k_umi_keys     a lane per fragment: key = bucket << 32 | code, bucket = ((row * nGenes + gene) << 4) | (length - 1); all ones = no UMI
 //   sort           t1k_sort_pairs over the 64 bits (stable, value = the fragment)
-//   run table      k_heads + exclusive scan + k_runs: the distinct UMIs of every bucket in code order, their first position (counts are
-//                  differences of consecutive starts).  A fragment without a UMI is a run of its own.
+//   run table      t1k_run_table (t1k_sort.hip): the distinct UMIs of every bucket in code order, their first position (counts are
+//                  differences of consecutive starts).  A fragment without a UMI is a run of its own (the table's lone key).
 //   k_umi_parent   a lane per distinct UMI: its bucket's range by two binary searches, then its 3 * L neighbours by binary search inside
 //                  that range; writes its own parent only, from counts nobody changes
 //   k_umi_root     a lane per distinct UMI follows the parents (read only)
@@ -65,26 +65,6 @@ __global__ __launch_bounds__(256) void k_umi_keys(UmiArgs P) {
     umiCount(P.counters + UMI_C_NOUMI, u == kNoUmi);
     P.keyA[f] = key;
     P.valA[f] = f;
-  }
-}
-
-// flag[i] = position i starts a run of equal keys (alone: a key of all ones never joins a run); flag[n] = 0 for the scan's total
-__global__ __launch_bounds__(256) void k_umi_heads(const unsigned long long *keys, uint32_t n, int noneAlone, uint32_t *flag) {
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i <= n; i += gridDim.x * 256u) {
-    uint32_t h = 0;
-    if (i < n) {
-      const unsigned long long k = keys[i];
-      h = (i == 0 || keys[i - 1] != k || (noneAlone && k == kNoUmi)) ? 1u : 0u;
-    }
-    flag[i] = h;
-  }
-}
-
-// scan[i] = runs before position i (scan[n] = all of them): run r starts at runStart[r], runStart[runs] = n
-__global__ __launch_bounds__(256) void k_umi_runs(const unsigned long long *keys, uint32_t n, const uint32_t *flag, const uint32_t *scan, uint32_t *runStart, unsigned long long *runKey) {
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i <= n; i += gridDim.x * 256u) {
-    if (i == n) runStart[scan[n]] = n;
-    else if (flag[i]) { runStart[scan[i]] = i; runKey[scan[i]] = keys[i]; }
   }
 }
 
@@ -239,32 +219,6 @@ __global__ __launch_bounds__(256) void k_umi_table(UmiArgs P, uint32_t nRuns) {
   }
 }
 
-static unsigned umiGrid(t1k_ctx *ctx, uint64_t items) {
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * 16, (items + 255) / 256));
-}
-
-// keys[0 .. n) sorted -> flag, scan, runStart, runKey; *runs = their number (one small copy back)
-static int umiRunTable(t1k_ctx *ctx, const UmiArgs &a, const unsigned long long *keys, uint32_t n, int noneAlone, uint32_t *runs) {
-  hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(k_umi_heads, dim3(umiGrid(ctx, (uint64_t)n + 1)), dim3(256), 0, st, keys, n, noneAlone, a.flag);
-  T1K_HIP(ctx, hipGetLastError());
-  int rc = t1k_exclusive_sum32(ctx, a.flag, a.scan, (uint64_t)n + 1);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_umi_runs, dim3(umiGrid(ctx, (uint64_t)n + 1)), dim3(256), 0, st, keys, n, (const uint32_t *)a.flag, (const uint32_t *)a.scan, a.runStart, a.runKey);
-  T1K_HIP(ctx, hipGetLastError());
-  T1K_HIP(ctx, hipMemcpyAsync(runs, a.scan + n, 4, hipMemcpyDeviceToHost, st));
-  T1K_HIP(ctx, hipStreamSynchronize(st));
-  return T1K_OK;
-}
-
-static int umiBits(unsigned long long v) {  // bits that hold every value <= v (at least 1)
-  int b = 1;
-  while (b < 64 && (v >> b)) ++b;
-  return b;
-}
-
 extern "C" {
 
 int t1k_umi_collapse(t1k_ctx *ctx, uint32_t nFrag, const uint32_t *fragRow, const uint64_t *fragUmi, const uint64_t *listPtr, const uint32_t *listAllele, uint32_t nRows,
@@ -306,26 +260,24 @@ int t1k_umi_collapse(t1k_ctx *ctx, uint32_t nFrag, const uint32_t *fragRow, cons
     maxList = std::max(maxList, (uint32_t)(listPtr[f + 1] - listPtr[f]));
   }
   const uint64_t nE = listPtr[nFrag] - eB;
-  const int nb = umiBits(maxList), cellBits = umiBits(nCells ? nCells - 1 : 0);
+  const int nb = t1k_bits(maxList), cellBits = t1k_bits(nCells ? nCells - 1 : 0);
   if (nb + cellBits > 64) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_umi_collapse: a table cell and a list length do not fit 64 bits");
   std::vector<uint32_t> lp(nFrag + 1);
   for (uint32_t f = 0; f <= nFrag; ++f) lp[f] = (uint32_t)(listPtr[f] - eB);
   // device: one block, 256-byte aligned pieces, sized by the upper bounds (molecules <= fragments, their entries <= the fragments')
   const uint64_t M = std::max<uint64_t>(nFrag, nE);
-  size_t off = 0;
-  auto piece = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256 + 256; return o; };
+  T1kCarve piece;
   const size_t oRow = piece(4ull * nFrag), oUmi = piece(8ull * nFrag), oLp = piece(4ull * (nFrag + 1)), oList = piece(4 * nE), oGene = piece(4ull * nAlleles),
                oKeyA = piece(8 * M), oKeyB = piece(8 * M), oValA = piece(4 * M), oValB = piece(4 * M), oFlag = piece(4 * (M + 1)), oScan = piece(4 * (M + 1)),
                oRunStart = piece(4 * (M + 1)), oRunKey = piece(8 * M), oParent = piece(4ull * nFrag), oRoot = piece(4ull * nFrag), oKMol = piece(4ull * (nFrag + 1)),
                oKLen = piece(4ull * (nFrag + 1)), oFragMol = piece(4ull * nFrag), oMolRow = piece(4ull * nFrag), oMolFrags = piece(4ull * nFrag),
                oMolStart = piece(4ull * (nFrag + 1)), oMolList = piece(4 * nE), oFrac = piece(8 * nCells), oUniq = piece(4 * nCells), oCnt = piece(4 * UMI_C_WORDS);
   T1K_HIP(ctx, hipSetDevice(ctx->device));
-  T1kDevBuf blk;
+  T1kCallBlock blk;
   int rc;
-  if ((rc = t1k_ensure(ctx, blk, off))) return rc;
+  if ((rc = blk.alloc(ctx, piece.off))) return rc;
   hipStream_t st = ctx->stream;
-  struct Free { void *p; hipStream_t s; ~Free() { (void)hipStreamSynchronize(s); (void)t1k_dev_free(p); } } guard{blk.p, st};
-  char *D = (char *)blk.p;
+  char *D = (char *)blk.buf.p;
   T1K_HIP(ctx, hipMemcpyAsync(D + oRow, fragRow, 4ull * nFrag, hipMemcpyHostToDevice, st));
   T1K_HIP(ctx, hipMemcpyAsync(D + oUmi, fragUmi, 8ull * nFrag, hipMemcpyHostToDevice, st));
   T1K_HIP(ctx, hipMemcpyAsync(D + oLp, lp.data(), 4ull * (nFrag + 1), hipMemcpyHostToDevice, st));
@@ -347,24 +299,24 @@ int t1k_umi_collapse(t1k_ctx *ctx, uint32_t nFrag, const uint32_t *fragRow, cons
   a.molList = (uint32_t *)(D + oMolList); a.frac = (double *)(D + oFrac); a.uniq = (int32_t *)(D + oUniq); a.nb = (uint32_t)nb; a.counters = (uint32_t *)(D + oCnt);
   T1K_HIP(ctx, hipEventRecord(ctx->ev[0], st));
   // distinct UMIs
-  hipLaunchKernelGGL(k_umi_keys, dim3(umiGrid(ctx, nFrag)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_umi_keys, dim3(t1k_grid(ctx, nFrag, 256)), dim3(256), 0, st, a);
   T1K_HIP(ctx, hipGetLastError());
   if ((rc = t1k_sort_pairs(ctx, a.keyA, a.keyB, a.valA, a.valB, nFrag, 64))) return rc;
   uint32_t nU = 0, nKeys = 0, nRuns = 0;
-  if ((rc = umiRunTable(ctx, a, a.keyB, nFrag, 1, &nU))) return rc;
+  if ((rc = t1k_run_table(ctx, a.keyB, nFrag, &kNoUmi, a.flag, a.scan, a.runStart, a.runKey, &nU))) return rc;
   if (nU == 0 || nU > nFrag) return t1k_fail(ctx, T1K_ERR_INTERNAL, "t1k_umi_collapse: the distinct UMIs do not add up");
-  hipLaunchKernelGGL(k_umi_parent, dim3(umiGrid(ctx, nU)), dim3(256), 0, st, a, nU);
+  hipLaunchKernelGGL(k_umi_parent, dim3(t1k_grid(ctx, nU, 256)), dim3(256), 0, st, a, nU);
   T1K_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_umi_root, dim3(umiGrid(ctx, nU)), dim3(256), 0, st, a, nU);
+  hipLaunchKernelGGL(k_umi_root, dim3(t1k_grid(ctx, nU, 256)), dim3(256), 0, st, a, nU);
   T1K_HIP(ctx, hipGetLastError());
   // keys: the fragments by the root of their UMI
-  hipLaunchKernelGGL(k_umi_root_keys, dim3(umiGrid(ctx, nFrag)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_umi_root_keys, dim3(t1k_grid(ctx, nFrag, 256)), dim3(256), 0, st, a);
   T1K_HIP(ctx, hipGetLastError());
-  if ((rc = t1k_sort_pairs(ctx, a.keyA, a.keyB, a.valA, a.valB, nFrag, umiBits(nU - 1)))) return rc;
-  if ((rc = umiRunTable(ctx, a, a.keyB, nFrag, 0, &nKeys))) return rc;
+  if ((rc = t1k_sort_pairs(ctx, a.keyA, a.keyB, a.valA, a.valB, nFrag, t1k_bits(nU - 1)))) return rc;
+  if ((rc = t1k_run_table(ctx, a.keyB, nFrag, nullptr, a.flag, a.scan, a.runStart, a.runKey, &nKeys))) return rc;
   if (nKeys == 0 || nKeys > nU) return t1k_fail(ctx, T1K_ERR_INTERNAL, "t1k_umi_collapse: the keys do not add up");
   // molecules: size, place, write
-  hipLaunchKernelGGL(k_umi_mol<false>, dim3(umiGrid(ctx, nKeys)), dim3(256), 0, st, a, nKeys);
+  hipLaunchKernelGGL(k_umi_mol<false>, dim3(t1k_grid(ctx, nKeys, 256)), dim3(256), 0, st, a, nKeys);
   T1K_HIP(ctx, hipGetLastError());
   T1K_HIP(ctx, hipMemsetAsync(a.kMol + nKeys, 0, 4, st));
   T1K_HIP(ctx, hipMemsetAsync(a.kLen + nKeys, 0, 4, st));
@@ -375,16 +327,16 @@ int t1k_umi_collapse(t1k_ctx *ctx, uint32_t nFrag, const uint32_t *fragRow, cons
   T1K_HIP(ctx, hipMemcpyAsync(&nLen, a.kLen + nKeys, 4, hipMemcpyDeviceToHost, st));
   T1K_HIP(ctx, hipStreamSynchronize(st));
   if (nMol < nKeys || nMol > nFrag || nLen < nMol || nLen > nE) return t1k_fail(ctx, T1K_ERR_INTERNAL, "t1k_umi_collapse: the molecules exceed their upper bounds");
-  hipLaunchKernelGGL(k_umi_mol<true>, dim3(umiGrid(ctx, nKeys)), dim3(256), 0, st, a, nKeys);
+  hipLaunchKernelGGL(k_umi_mol<true>, dim3(t1k_grid(ctx, nKeys, 256)), dim3(256), 0, st, a, nKeys);
   T1K_HIP(ctx, hipGetLastError());
   T1K_HIP(ctx, hipMemcpyAsync(a.molStart + nMol, &nLen, 4, hipMemcpyHostToDevice, st));
   // the table
-  hipLaunchKernelGGL(k_umi_triples, dim3(umiGrid(ctx, nMol)), dim3(256), 0, st, a, nMol);
+  hipLaunchKernelGGL(k_umi_triples, dim3(t1k_grid(ctx, nMol, 256)), dim3(256), 0, st, a, nMol);
   T1K_HIP(ctx, hipGetLastError());
   if ((rc = t1k_sort_pairs(ctx, a.keyA, a.keyB, a.valA, a.valB, nLen, nb + cellBits))) return rc;  // (the values ride along unread)
-  if ((rc = umiRunTable(ctx, a, a.keyB, nLen, 0, &nRuns))) return rc;
+  if ((rc = t1k_run_table(ctx, a.keyB, nLen, nullptr, a.flag, a.scan, a.runStart, a.runKey, &nRuns))) return rc;
   if (nRuns == 0 || nRuns > nLen) return t1k_fail(ctx, T1K_ERR_INTERNAL, "t1k_umi_collapse: the table's runs do not add up");
-  hipLaunchKernelGGL(k_umi_table, dim3(umiGrid(ctx, nRuns)), dim3(256), 0, st, a, nRuns);
+  hipLaunchKernelGGL(k_umi_table, dim3(t1k_grid(ctx, nRuns, 256)), dim3(256), 0, st, a, nRuns);
   T1K_HIP(ctx, hipGetLastError());
   T1K_HIP(ctx, hipEventRecord(ctx->ev[1], st));
   // results

@@ -70,6 +70,43 @@ def test_no_sites_gives_no_runs(ctx, table):
     assert len(keys) == 0 and len(counts) == 0 and folds == 0
 
 
+# ---- the fold's run table and count differences at their edges -------------------------------------------------------------------------
+def _edge(books):
+    """one allele of 8 bases with a site at position 3; a record of five matches from position 0 per booking list (it hits the site once)"""
+    off = pileup_ref.offsets([8])
+    aln = np.array([(0, 0, 0, 0, 5, 0, 0, 0)] * len(books), t1k_amd.PILEUP_ALN_DTYPE)
+    ptr = np.concatenate([[0], np.cumsum([len(b) for b in books])]).astype(np.uint64)
+    book = np.array([e for b in books for e in b], np.uint32)
+    return (off, np.array([0], np.uint32), np.array([3], np.uint32), 3, aln, ptr, book, b"ACGTACGT", np.zeros(5, np.int8))
+
+
+def _edge_want(args):
+    off, sa, sp, _, aln, ptr, book, text, ops = args
+    return ref.restate(off, aln, ptr, book, text, ops, sa, sp)
+
+
+def test_fold_of_one_key(ctx):
+    args = _edge([[(2 << 1) | 1]])
+    keys, counts, _, folds = ctx.sitepile(*args)
+    assert len(keys) == 1 and counts.tolist() == [1] and folds == 1
+    assert ref.same(ref.from_runs(keys, counts, 1), _edge_want(args))
+
+
+def test_fold_of_one_run_of_256(ctx):
+    args = _edge([[(1 << 1) | 0] * 256])
+    keys, counts, _, folds = ctx.sitepile(*args)
+    assert len(keys) == 1 and counts.tolist() == [256] and folds == 1
+    assert ref.same(ref.from_runs(keys, counts, 1), _edge_want(args))
+
+
+def test_fold_merges_a_folded_count_with_pending_keys(ctx, monkeypatch):
+    monkeypatch.setenv("T1K_SITEPILE_PENDING", "1")           # a fold behind each of the two calls
+    args = _edge([[(1 << 1) | 0] * 256, [(1 << 1) | 0] * 256 + [(2 << 1) | 0]])
+    keys, counts, _, folds = ctx.sitepile(*args, cuts=(1,))
+    assert counts.tolist() == [512, 1] and folds == 2         # (count 256 + 256 pending keys) in one run, then a run of one
+    assert ref.same(ref.from_runs(keys, counts, 1), _edge_want(args))
+
+
 # ---- 2. argument errors --------------------------------------------------------------------------------------------------------------
 def test_argument_errors_emit_nothing(built):
     c = t1k_amd.Context()

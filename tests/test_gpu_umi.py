@@ -74,6 +74,45 @@ def test_slice_through_a_nonzero_offset(ctx):
     _same(got, w)
 
 
+# ---- the three run tables at their edges: one item, a block boundary, one long run, lone keys only -------------------------------------
+def _edge_tables():
+    """name -> (Table from the restatement's own builder, what the restatement must say of it for mismatch 1)"""
+    one_gene, two_genes = np.zeros(2, np.uint32), np.array([0, 1], np.uint32)
+    top = "T" * 16                                              # the largest code of the longest length: with the last row and gene, the largest real key
+    # (both rows hold a pair at distance 1 that mismatch 1 joins: T..TG into T..TT by count, ACGT into ACGA by the smaller code)
+    mix = [(1, top, [1]), (0, "ACGT", [0]), (1, None, [1]), (1, top, [1]), (0, "ACGA", [0, 1]), (1, None, [1]), (1, "T" * 15 + "G", [1]), (0, None, [0])]
+    return {
+        "one_umi": (ref.from_fragments([(0, "ACGT", [0])], 1, one_gene, 1), dict(distinct=1, keys=1, corrected=0, split=0, no_umi=0)),
+        "one_none": (ref.from_fragments([(0, None, [0])], 1, one_gene, 1), dict(distinct=0, keys=0, corrected=0, split=0, no_umi=1)),
+        "distinct_256": (ref.from_fragments([(i, "ACGT", [0]) for i in range(256)], 256, one_gene, 1), dict(distinct=256, keys=256, corrected=0, split=0, no_umi=0)),
+        "distinct_257": (ref.from_fragments([(i, "ACGT", [0]) for i in range(257)], 257, one_gene, 1), dict(distinct=257, keys=257, corrected=0, split=0, no_umi=0)),
+        "one_run_256": (ref.from_fragments([(0, "ACGT", [0])] * 256, 1, one_gene, 1), dict(distinct=1, keys=1, corrected=0, split=0, no_umi=0)),
+        "none_300": (ref.from_fragments([(0, None, [0, 1])] * 300, 1, one_gene, 1), dict(distinct=0, keys=0, corrected=0, split=0, no_umi=300)),
+        "none_behind_top_key": (ref.from_fragments(mix, 2, two_genes, 2), dict(distinct=4, keys=2, corrected=2, split=0, no_umi=3)),
+    }
+
+
+EDGES = _edge_tables()
+
+
+@pytest.mark.parametrize("mismatch", [0, 1])
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_run_table_edges_equal_restatement(ctx, name, mismatch):
+    t, stats1 = EDGES[name]
+    w = ref.restate(t, mismatch)
+    if mismatch == 1:
+        assert w.stats == stats1                                # the case is the one its name says
+    if name == "none_behind_top_key":
+        key = ((np.uint64(1 * 2 + 1) << np.uint64(4) | np.uint64(15)) << np.uint64(32)) | np.uint64(0xFFFFFFFF)
+        assert w.keys[-1] == key and w.counts[-1] == 2          # the run in front of the all-ones keys: real, low word all ones, two fragments
+        assert w.frag_mol[0] == w.frag_mol[3] and len({int(w.frag_mol[f]) for f in (2, 5, 7)}) == 3
+    if name == "none_300":
+        assert len(w.mol_row) == 300 and w.frac[0].tolist() == [150.0, 150.0]
+    if name == "one_run_256":
+        assert w.mol_frags.tolist() == [256]
+    _same(ctx.umi_collapse(*t.args(), mismatch=mismatch), w)
+
+
 def test_argument_errors(ctx):
     gene = np.array([0, 0, 1, 1], np.uint32)
     good = ref.from_fragments([(0, "ACGT", [0, 1]), (1, "ACGA", [1]), (1, None, [2, 3])], 2, gene, 2)
