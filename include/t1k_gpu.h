@@ -411,6 +411,31 @@ int t1k_sitepile_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap
 int t1k_sitepile_stats(t1k_ctx *ctx, uint64_t *keysEmitted, uint64_t *folds, double *foldMs);
 int t1k_sitepile_end(t1k_ctx *ctx);
 
+/* ---- read-backed phasing of site pairs (analyzer --phase) -----------------------------------------------------------
+ * Which states two sites show on one fragment.  Sites as for t1k_sitepile_begin, at most 2^28 of them (else T1K_ERR_CAPACITY); nSites = 0
+ * is legal (the table stays empty).  A record observes a site with the column of its edit string that consumes that allele position:
+ * ops 0 and 1 give the read base (state 0 .. 3 for A C G T, 4 = N for anything else), op 3 gives state 5 = del; insert columns observe
+ * nothing.  A booking is a fragment-assignment: bookRec[2b] = rec1, bookRec[2b + 1] = rec2, its mate on the same allele, or 0xFFFFFFFF
+ * for "no mate", and bookUniq[b] != 0 when its fragment has one assignment.  Its observations are the union of its records': a site both
+ * show in the same state counts once, a site they show in different states is dropped for this booking (a discordant site); rec1 == rec2
+ * gives that record's own list.  Every unordered pair of a booking's observed sites s < t in states x, y adds 1 to cell (s, t, x, y).
+ * The table is sparse: (key, count) runs ascending by key, key = (((s * nSites + t) * 36 + x * 6 + y) << 1) | (1 - uniq).  A uniq booking
+ * is stored once, under the even key: the reader forms plain = even + odd, _uniq = even.
+ * t1k_phase_add: records as for t1k_pileup_add (w_all / w_uniq are ignored).  Nothing is emitted unless the whole call is sound:
+ * T1K_ERR_ARG for an allele >= nAlleles, a record index >= n, mates on different alleles, an op outside 0 .. 3, a walk that leaves its
+ * allele, `text` or `ops`; T1K_ERR_CAPACITY when a call holds 2^31 observations or more, or the table and the call's keys exceed 2^31
+ * entries -- pairs grow with the square of a booking's observed sites -- or a counter would pass 2^31 - 1 (the table is as before the
+ * call); T1K_ERR_STATE for add / get / stats / end without begin, or begin while a table is open.  Pending keys are folded into runs
+ * whenever they reach 2^28 (env T1K_PHASE_PENDING) and at _get.
+ * t1k_phase_get: as t1k_sitepile_get.  t1k_phase_stats: observations of the records walked, bookings with two observed sites or more,
+ * keys emitted, discordant sites and folds so far, device time of the folds. */
+int t1k_phase_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff /* [nAlleles + 1] */, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos);
+int t1k_phase_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, uint32_t nBook, const uint32_t *bookRec /* [2 * nBook] */, const uint8_t *bookUniq /* [nBook] */,
+                  const char *text, uint64_t textBytes, const int8_t *ops, uint64_t opsBytes, double *kernelMs);
+int t1k_phase_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns);
+int t1k_phase_stats(t1k_ctx *ctx, uint64_t *observations, uint64_t *bookings, uint64_t *keysEmitted, uint64_t *discordant, uint64_t *folds, double *foldMs);
+int t1k_phase_end(t1k_ctx *ctx);
+
 /* ---- profiling counters of the last t1k_assign_batch (algorithmic-traffic terms of SURVEY.md 8d) --------------- */
 typedef struct {
   uint64_t read_ends, lookups, postings, hits, groups, candidates, extended, near_best, dp_calls, rows, batches;

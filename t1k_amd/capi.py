@@ -66,6 +66,8 @@ assert FRAG_ASG_DTYPE.itemsize == 136 and VARIANT_DTYPE.itemsize == 56
 # t1k_pileup_aln (per-base pileup) and the names of the 14 counter planes of its table
 PILEUP_ALN_DTYPE = np.dtype([("allele", "<u4"), ("seq_start", "<u4"), ("read_at", "<u8"), ("ops_at", "<u8"), ("n_ops", "<u4"), ("w_all", "<u4"), ("w_uniq", "<u4"),
                              ("reserved", "<u4")])
+PHASE_NO_MATE = 0xFFFFFFFF
+PHASE_STATES = ("A", "C", "G", "T", "N", "-")
 PILEUP_COUNTERS = ("A", "C", "G", "T", "N", "del", "ins", "A_uniq", "C_uniq", "G_uniq", "T_uniq", "N_uniq", "del_uniq", "ins_uniq")
 assert PILEUP_ALN_DTYPE.itemsize == 40
 
@@ -120,6 +122,11 @@ def lib():
     L.t1k_sitepile_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
     L.t1k_sitepile_stats.argtypes = [vp, u64p, u64p, C.POINTER(C.c_double)]
     L.t1k_sitepile_end.argtypes = [vp]
+    L.t1k_phase_begin.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp]
+    L.t1k_phase_add.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_double)]
+    L.t1k_phase_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
+    L.t1k_phase_stats.argtypes = [vp, u64p, u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]
+    L.t1k_phase_end.argtypes = [vp]
     L.t1k_extract_batch.argtypes = [vp, C.c_uint32, vp, vp]
     L.t1k_extractor_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_stats_get.argtypes = [vp, C.POINTER(Stats)]
@@ -603,6 +610,73 @@ class Context:
             return keys, counts, ms, self.sitepile_stats()[1]
         finally:
             self.sitepile_end()
+
+    # read-backed phasing of site pairs (t1k_phase_begin / _add / _get / _stats / _end); raw=True returns the status code instead of raising
+    def phase_begin(self, allele_off, site_allele, site_pos, raw=False):
+        off = np.ascontiguousarray(allele_off, np.uint64)
+        sa, sp = np.ascontiguousarray(site_allele, np.uint32), np.ascontiguousarray(site_pos, np.uint32)
+        assert len(sa) == len(sp)
+        rc = lib().t1k_phase_begin(self.h, max(len(off) - 1, 0), _ptr(off), len(sa), _ptr(sa), _ptr(sp))
+        if raw:
+            return rc
+        self._check(rc, "t1k_phase_begin")
+
+    def phase_add(self, aln, book_rec, book_uniq, text, ops, raw=False):
+        """aln: PILEUP_ALN_DTYPE records; booking b is the fragment-assignment of records book_rec[b] = (rec1, rec2 or PHASE_NO_MATE), both
+        indices into aln, with book_uniq[b] set when its fragment has one assignment; text / ops as for pileup_add.  Returns the kernels'
+        device time in ms"""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        br, bu = np.ascontiguousarray(book_rec, np.uint32).reshape(-1, 2), np.ascontiguousarray(book_uniq, np.uint8)
+        assert len(br) == len(bu)
+        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+        o = np.ascontiguousarray(ops, np.int8)
+        ms = C.c_double()
+        rc = lib().t1k_phase_add(self.h, _ptr(a), len(a), len(bu), _ptr(br), _ptr(bu), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
+        if raw:
+            return rc
+        self._check(rc, "t1k_phase_add")
+        return ms.value
+
+    def phase_get(self, raw=False):
+        """the table's runs, ascending: (keys uint64, counts int32); key = (((s * nSites + t) * 36 + x * 6 + y) << 1) | (1 - uniq)"""
+        n = C.c_uint64()
+        rc = lib().t1k_phase_get(self.h, None, None, 0, C.byref(n))
+        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
+        if rc == 0 and n.value:
+            rc = lib().t1k_phase_get(self.h, _ptr(keys), _ptr(counts), n.value, C.byref(n))
+        if raw:
+            return rc
+        self._check(rc, "t1k_phase_get")
+        return keys, counts
+
+    def phase_stats(self, raw=False):
+        """{observations, bookings (with two observed sites or more), keys, discordant, folds, fold_ms} of the open table"""
+        v = [C.c_uint64() for _ in range(5)]
+        ms = C.c_double()
+        rc = lib().t1k_phase_stats(self.h, *[C.byref(x) for x in v], C.byref(ms))
+        if raw:
+            return rc
+        self._check(rc, "t1k_phase_stats")
+        return dict(zip(("observations", "bookings", "keys", "discordant", "folds"), (x.value for x in v)), fold_ms=ms.value)
+
+    def phase_end(self, raw=False):
+        rc = lib().t1k_phase_end(self.h)
+        if raw:
+            return rc
+        self._check(rc, "t1k_phase_end")
+
+    def phase(self, allele_off, site_allele, site_pos, aln, book_rec, book_uniq, text, ops, cuts=()):
+        """begin, add, get, end: (keys, counts, kernels' ms, stats).  cuts: booking indices at which the bookings are split into several
+        calls; every call gets all the records"""
+        br, bu = np.ascontiguousarray(book_rec, np.uint32).reshape(-1, 2), np.ascontiguousarray(book_uniq, np.uint8)
+        self.phase_begin(allele_off, site_allele, site_pos)
+        try:
+            edges = [0] + [int(c) for c in cuts] + [len(bu)]
+            ms = sum(self.phase_add(aln, br[lo:hi], bu[lo:hi], text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
+            keys, counts = self.phase_get()
+            return keys, counts, ms, self.phase_stats()
+        finally:
+            self.phase_end()
 
 
 def pair_limits():

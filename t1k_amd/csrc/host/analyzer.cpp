@@ -51,20 +51,26 @@ static const char *kPileupHeader = "#allele\tpos\texon_pos\tref\tA\tC\tG\tT\tN\t
 // barcode << 1 | uniq per assignment overlap that points at the record); the edit strings stay in V.ops.  Retained host memory: roughly
 // the read text of the assigned fragments (once more for the read-ends with an overlap on the other strand) + 40 bytes per distinct
 // alignment + 4 bytes per assignment overlap.
+// --phase replays the same pieces through t1k_phase_add: its bookings are the assignments themselves, (record of mate 1,
+// record of mate 2 or none, uniq), 9 more bytes per assignment.  Either flag keeps the pieces; each keeps its own booking lists only.
 struct AnalyzerSitepile {
   struct Piece {
     std::vector<t1k_pileup_aln> recs;
     std::string pat;
-    std::vector<uint64_t> bookPtr;
+    std::vector<uint64_t> bookPtr;   // --barcodePileup
     std::vector<uint32_t> book;
+    std::vector<uint32_t> asgRec;    // --phase: two per assignment, 0xFFFFFFFF = no mate
+    std::vector<uint8_t> asgUniq;
     uint64_t ops0 = 0, ops1 = 0;   // the piece's edit strings: V.ops[ops0 .. ops1)
   };
-  const std::vector<int> *bcOf = nullptr;  // fragment -> barcode id
+  bool barcodes = false, phase = false;    // --barcodePileup, --phase
+  const std::vector<int> *bcOf = nullptr;  // fragment -> barcode id (--barcodePileup)
   std::vector<Piece> pieces;
   // extra sites of --sites (allele, 0-based position), and the lines of the file that name an allele which is not selected
   std::vector<std::pair<uint32_t, uint32_t>> fileSites;
   uint64_t fileSkipped = 0;
 };
+static const char *kPhaseHeader = "#allele\tpos1\tpos2\texon_pos1\texon_pos2\tref1\tref2\tvar1\tvar2\tobs1\tobs2\tcount\tcount_uniq\n";
 static const char *kBarcodePileupHeader = "#barcode\tallele\tpos\texon_pos\tref\tvar\tA\tC\tG\tT\tN\tdel\tins\tA_uniq\tC_uniq\tG_uniq\tT_uniq\tN_uniq\tdel_uniq\tins_uniq\n";
 
 // every fragment's raw row (the reference's list order): cnt[f] entries at rows[rowAt[f]]
@@ -389,17 +395,29 @@ static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerP
         if (sp) {
           // the same loop once more, now that every record's number of bookings (w_all) is known: its list, in fragment order
           AnalyzerSitepile::Piece pc;
-          pc.bookPtr.assign(nJ + 1, 0);
-          for (size_t j = 0; j < nJ; ++j) pc.bookPtr[j + 1] = pc.bookPtr[j] + recs[j].w_all;
-          pc.book.resize(pc.bookPtr[nJ]);
-          std::vector<uint64_t> fill(pc.bookPtr.begin(), pc.bookPtr.end() - 1);
+          std::vector<uint64_t> fill;
+          if (sp->barcodes) {
+            pc.bookPtr.assign(nJ + 1, 0);
+            for (size_t j = 0; j < nJ; ++j) pc.bookPtr[j + 1] = pc.bookPtr[j] + recs[j].w_all;
+            pc.book.resize(pc.bookPtr[nJ]);
+            fill.assign(pc.bookPtr.begin(), pc.bookPtr.end() - 1);
+          }
+          if (sp->phase) { pc.asgRec.reserve(2 * nAsg); pc.asgUniq.reserve(nAsg); }
           for (uint32_t f = f0; f < f1; ++f) {
             const uint32_t one = V.asgPtr[f + 1] - V.asgPtr[f] == 1 ? 1u : 0u;
-            for (uint64_t q = V.asgPtr[f]; q < V.asgPtr[f + 1]; ++q)
-              for (int m = 0; m < 2; ++m) {
-                const int64_t j = jobOfAsg[m][q - q0];
-                if (j >= 0) pc.book[fill[j]++] = ((uint32_t)(*sp->bcOf)[f] << 1) | one;
+            for (uint64_t q = V.asgPtr[f]; q < V.asgPtr[f + 1]; ++q) {
+              if (sp->barcodes)
+                for (int m = 0; m < 2; ++m) {
+                  const int64_t j = jobOfAsg[m][q - q0];
+                  if (j >= 0) pc.book[fill[j]++] = ((uint32_t)(*sp->bcOf)[f] << 1) | one;
+                }
+              if (sp->phase) {
+                const int64_t j1 = jobOfAsg[0][q - q0], j2 = jobOfAsg[1][q - q0];
+                pc.asgRec.push_back((uint32_t)j1);
+                pc.asgRec.push_back(j2 >= 0 ? (uint32_t)j2 : 0xFFFFFFFFu);
+                pc.asgUniq.push_back((uint8_t)one);
               }
+            }
           }
           pc.recs = std::move(recs);
           pc.pat = std::move(pat);
@@ -531,15 +549,21 @@ static bool analyzerReadSites(t1k_job *job, const std::string &path, AnalyzerSit
   return ok;
 }
 
-// <prefix>_barcode_pileup.tsv: the kept pieces through t1k_sitepile_add at the sites (the rows of _allele.vcf and those of --sites), the runs
-// that come back merged per (barcode, site) and written in barcode id order (the order of the lines of _barcode_expr.tsv), then allele, then pos
-static bool analyzerSitepile(t1k_job *job, const std::string &prefix, const AnalyzerVariants &V, AnalyzerSitepile &sp, const std::vector<std::string> &barcodeNames) {
-  const double t0 = nowMs();
+// the sites of --barcodePileup and --phase: the rows of _allele.vcf united with those of --sites, sorted and free of
+// duplicates; per site the called bases in VCF order and the columns both files print for it
+struct AnalyzerSiteList {
+  std::vector<std::pair<uint32_t, uint32_t>> sites;
+  std::map<std::pair<uint32_t, uint32_t>, std::string> varOf;
+  std::vector<uint32_t> siteAllele, sitePos;
+  std::vector<uint64_t> refOff;
+  std::vector<int> exonPos;   // exonic position (SeqSet::GetExonicPosition), 0 = not exonic
+
+  AnalyzerSiteList(t1k_job *job, const AnalyzerVariants &V, const AnalyzerSitepile &sp);
+};
+
+AnalyzerSiteList::AnalyzerSiteList(t1k_job *job, const AnalyzerVariants &V, const AnalyzerSitepile &sp) : sites(sp.fileSites) {
   const RefSet &R = job->ref;
   const size_t A = R.seqs.size();
-  // the sites, and per site the called bases in VCF order
-  std::vector<std::pair<uint32_t, uint32_t>> sites(sp.fileSites);
-  std::map<std::pair<uint32_t, uint32_t>, std::string> varOf;
   if (V.vc)
     for (const VariantRec &v : V.vc->variants) {
       const std::pair<uint32_t, uint32_t> k((uint32_t)v.allele, (uint32_t)v.refPos);
@@ -551,10 +575,32 @@ static bool analyzerSitepile(t1k_job *job, const std::string &prefix, const Anal
   std::sort(sites.begin(), sites.end());
   sites.erase(std::unique(sites.begin(), sites.end()), sites.end());
   const size_t nSites = sites.size();
-  std::vector<uint32_t> siteAllele(nSites), sitePos(nSites);
+  siteAllele.resize(nSites); sitePos.resize(nSites);
   for (size_t i = 0; i < nSites; ++i) { siteAllele[i] = sites[i].first; sitePos[i] = sites[i].second; }
-  std::vector<uint64_t> refOff(A + 1, 0);
+  refOff.assign(A + 1, 0);
   for (size_t a = 0; a < A; ++a) refOff[a + 1] = refOff[a] + R.seqs[a].size();
+  exonPos.assign(nSites, 0);  // one pass per allele
+  for (size_t i = 0; i < nSites;) {
+    const uint32_t a = siteAllele[i];
+    int exonic = 0;
+    uint32_t p = 0;
+    for (; i < nSites && siteAllele[i] == a; ++i) {
+      for (; p <= sitePos[i]; ++p) exonic += R.exon[a][p] ? 1 : 0;
+      exonPos[i] = R.exon[a][sitePos[i]] ? exonic : 0;
+    }
+  }
+}
+
+// <prefix>_barcode_pileup.tsv: the kept pieces through t1k_sitepile_add at the sites, the runs that come back merged per (barcode, site)
+// and written in barcode id order (the order of the lines of _barcode_expr.tsv), then allele, then pos
+static bool analyzerSitepile(t1k_job *job, const std::string &prefix, const AnalyzerVariants &V, const AnalyzerSitepile &sp, const AnalyzerSiteList &L,
+                             const std::vector<std::string> &barcodeNames) {
+  const double t0 = nowMs();
+  const RefSet &R = job->ref;
+  const size_t A = R.seqs.size(), nSites = L.sites.size();
+  const std::vector<uint32_t> &siteAllele = L.siteAllele, &sitePos = L.sitePos;
+  const std::vector<uint64_t> &refOff = L.refOff;
+  const std::vector<int> &exonPos = L.exonPos;
   t1k_ctx *ctx = job->ctx;
   auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
   int rc;
@@ -582,22 +628,10 @@ static bool analyzerSitepile(t1k_job *job, const std::string &prefix, const Anal
     if (rc != T1K_OK) { fail(rc); t1k_sitepile_end(ctx); return false; }
     if ((rc = t1k_sitepile_end(ctx)) != T1K_OK) return fail(rc);
   }
-  sp.pieces.clear();
   const double tw = nowMs();
   FILE *fp = fopen((prefix + "_barcode_pileup.tsv").c_str(), "w");
   if (!fp) { fprintf(stderr, "analyzer: cannot write %s_barcode_pileup.tsv\n", prefix.c_str()); return false; }
   fputs(kBarcodePileupHeader, fp);
-  // exonic position per site (SeqSet::GetExonicPosition), one pass per allele
-  std::vector<int> exonPos(nSites, 0);
-  for (size_t i = 0; i < nSites;) {
-    const uint32_t a = siteAllele[i];
-    int exonic = 0;
-    uint32_t p = 0;
-    for (; i < nSites && siteAllele[i] == a; ++i) {
-      for (; p <= sitePos[i]; ++p) exonic += R.exon[a][p] ? 1 : 0;
-      exonPos[i] = R.exon[a][sitePos[i]] ? exonic : 0;
-    }
-  }
   std::string out;
   char num[48];
   uint64_t cells = 0;
@@ -621,8 +655,8 @@ static bool analyzerSitepile(t1k_job *job, const std::string &prefix, const Anal
     out += '\t';
     out += R.seqs[a][pos];
     out += '\t';
-    auto it = varOf.find(sites[site]);
-    out += it == varOf.end() ? std::string(".") : it->second;
+    auto it = L.varOf.find(L.sites[site]);
+    out += it == L.varOf.end() ? std::string(".") : it->second;
     for (int k = 0; k < 14; ++k) { snprintf(num, sizeof num, "\t%d", c[k]); out += num; }
     out += '\n';
     if (out.size() >= (1u << 20)) { fwrite(out.data(), 1, out.size(), fp); out.clear(); }
@@ -633,6 +667,82 @@ static bool analyzerSitepile(t1k_job *job, const std::string &prefix, const Anal
     fprintf(stderr, "barcode pileup: %zu sites, %llu records, %llu keys emitted, %llu folds, %llu cells; upload %.1f ms, kernels %.1f ms, fold %.1f ms, write %.1f ms\n", nSites,
             (unsigned long long)nRecs, (unsigned long long)emitted, (unsigned long long)folds, (unsigned long long)cells, std::max(0.0, (tw - t0) - msKernels - msFold), msKernels, msFold,
             nowMs() - tw);
+  return true;
+}
+
+// <prefix>_allele_phase.tsv: the kept pieces through t1k_phase_add at the sites; one line per (site pair, state pair) with a
+// booking, in key order: the alleles of job->ref.al, then pos1, pos2, obs1, obs2 in state order
+static bool analyzerPhase(t1k_job *job, const std::string &prefix, const AnalyzerVariants &V, const AnalyzerSitepile &sp, const AnalyzerSiteList &L) {
+  const double t0 = nowMs();
+  const RefSet &R = job->ref;
+  const size_t A = R.seqs.size(), nSites = L.sites.size();
+  t1k_ctx *ctx = job->ctx;
+  auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
+  int rc;
+  double msKernels = 0, msFold = 0;
+  uint64_t nRecs = 0, nBook = 0, nRuns = 0, nObs = 0, nPaired = 0, emitted = 0, discordant = 0, folds = 0;
+  std::vector<uint64_t> keys;
+  std::vector<int32_t> counts;
+  if (nSites) {
+    if ((rc = t1k_phase_begin(ctx, (uint32_t)A, L.refOff.data(), nSites, L.siteAllele.data(), L.sitePos.data())) != T1K_OK) return fail(rc);
+    for (const AnalyzerSitepile::Piece &pc : sp.pieces) {
+      double ms = 0;
+      if ((rc = t1k_phase_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), (uint32_t)pc.asgUniq.size(), pc.asgRec.data(), pc.asgUniq.data(), pc.pat.data(), pc.pat.size(),
+                              V.ops.data() + pc.ops0, pc.ops1 - pc.ops0, &ms)) != T1K_OK) {
+        fail(rc);
+        t1k_phase_end(ctx);
+        return false;
+      }
+      msKernels += ms;
+      nRecs += pc.recs.size();
+      nBook += pc.asgUniq.size();
+    }
+    if ((rc = t1k_phase_get(ctx, nullptr, nullptr, 0, &nRuns)) == T1K_OK && nRuns) {
+      keys.resize(nRuns); counts.resize(nRuns);
+      rc = t1k_phase_get(ctx, keys.data(), counts.data(), nRuns, &nRuns);
+    }
+    if (rc == T1K_OK) rc = t1k_phase_stats(ctx, &nObs, &nPaired, &emitted, &discordant, &folds, &msFold);
+    if (rc != T1K_OK) { fail(rc); t1k_phase_end(ctx); return false; }
+    if ((rc = t1k_phase_end(ctx)) != T1K_OK) return fail(rc);
+  }
+  const double tw = nowMs();
+  FILE *fp = fopen((prefix + "_allele_phase.tsv").c_str(), "w");
+  if (!fp) { fprintf(stderr, "analyzer: cannot write %s_allele_phase.tsv\n", prefix.c_str()); return false; }
+  fputs(kPhaseHeader, fp);
+  static const char *kObs[6] = {"A", "C", "G", "T", "N", "-"};
+  std::string out;
+  uint64_t cells = 0;
+  for (size_t i = 0; i < keys.size();) {
+    const uint64_t cell = keys[i] >> 1;  // its uniq (even) run, then the other
+    int32_t all = 0, uniq = 0;
+    for (; i < keys.size() && (keys[i] >> 1) == cell; ++i) {
+      all += counts[i];                                       // a uniq booking counts in the plain counter as well
+      if ((keys[i] & 1) == 0) uniq += counts[i];
+    }
+    const uint64_t pair = cell / 36, s1 = pair / nSites, s2 = pair % nSites;
+    const uint32_t a = L.siteAllele[s1];
+    ++cells;
+    out += R.al[a].name;
+    for (uint64_t s : {s1, s2}) { out += '\t'; out += std::to_string(L.sitePos[s] + 1); }
+    for (uint64_t s : {s1, s2}) { out += '\t'; out += L.exonPos[s] ? std::to_string(L.exonPos[s]) : std::string("."); }
+    for (uint64_t s : {s1, s2}) { out += '\t'; out += R.seqs[a][L.sitePos[s]]; }
+    for (uint64_t s : {s1, s2}) {
+      auto it = L.varOf.find(L.sites[s]);
+      out += '\t';
+      out += it == L.varOf.end() ? std::string(".") : it->second;
+    }
+    out += '\t'; out += kObs[(cell % 36) / 6];
+    out += '\t'; out += kObs[cell % 6];
+    out += '\t' + std::to_string(all) + '\t' + std::to_string(uniq) + '\n';
+    if (out.size() >= (1u << 20)) { fwrite(out.data(), 1, out.size(), fp); out.clear(); }
+  }
+  fwrite(out.data(), 1, out.size(), fp);
+  fclose(fp);
+  if (getenv("T1K_DEBUG_PHASES"))
+    fprintf(stderr, "phase: %zu sites, %llu records, %llu bookings (%llu with two observed sites or more), %llu observations, %llu discordant, %llu keys emitted, %llu folds, %llu cells; "
+                    "upload %.1f ms, kernels %.1f ms, fold %.1f ms, write %.1f ms\n", nSites, (unsigned long long)nRecs, (unsigned long long)nBook, (unsigned long long)nPaired,
+            (unsigned long long)nObs, (unsigned long long)discordant, (unsigned long long)emitted, (unsigned long long)folds, (unsigned long long)cells,
+            std::max(0.0, (tw - t0) - msKernels - msFold), msKernels, msFold, nowMs() - tw);
   return true;
 }
 
@@ -884,7 +994,9 @@ static const char *kAnalyzerUsage =
     "\t\tthe variant pass holds, over all assignments and over those of fragments with one assignment (_uniq)\n"
     "\t--barcodePileup: also write prefix_barcode_pileup.tsv, the counters of --pileup per barcode at the positions of prefix_allele.vcf and of --sites,\n"
     "\t\tone line per (barcode, site) with a read (needs --barcode)\n"
-    "\t--sites FILE: more sites for --barcodePileup, one per line as allele_name<TAB>pos (1-based, the pos column of prefix_allele_pileup.tsv); '#' lines,\n"
+    "\t--phase: also write prefix_allele_phase.tsv, for every two of the positions of prefix_allele.vcf and of --sites on one allele the fragments that\n"
+    "\t\tshow both, by what they show there (A C G T N or - for a deletion): read-backed phasing of the variants\n"
+    "\t--sites FILE: more sites for --barcodePileup and --phase, one per line as allele_name<TAB>pos (1-based, the pos column of prefix_allele_pileup.tsv); '#' lines,\n"
     "\t\tblank lines and alleles that are not selected are skipped\n"
     "\t--relaxIntronAlign: allow one more mismatch in intronic alignment\n"
     "\t--alleleDigitUnits INT, --alleleDelimiter CHR: as in genotyper\n"
@@ -897,14 +1009,14 @@ int t1k_analyzer_main(int argc, char **argv) {
                                      {"alleleDelimiter", required_argument, 0, 10006}, {"varMaxGroup", required_argument, 0, 10007}, {"device", required_argument, 0, 10010},
                                      {"barcodeEM", no_argument, 0, 10011}, {"barcodeEMPrior", required_argument, 0, 10012}, {"umi", required_argument, 0, 10013},
                                      {"umiMismatch", required_argument, 0, 10014}, {"pileup", no_argument, 0, 10015}, {"barcodePileup", no_argument, 0, 10016},
-                                     {"sites", required_argument, 0, 10017}, {0, 0, 0, 0}};
+                                     {"sites", required_argument, 0, 10017}, {"phase", no_argument, 0, 10018}, {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
   std::string refFile, alleleFile, prefix = "t1k", barcode;
   std::vector<const char *> f1, f2, single;
   int varMaxGroup = 8;  // Analyzer.cpp:251
-  bool barcodeEM = false, pileup = false, barcodePileup = false;
+  bool barcodeEM = false, pileup = false, barcodePileup = false, phase = false;
   double emPrior = 0;
   const char *emPriorText = nullptr, *umiMismatchText = nullptr;
   std::string umiPath, sitesPath;
@@ -935,6 +1047,7 @@ int t1k_analyzer_main(int argc, char **argv) {
       case 10015: pileup = true; break;
       case 10016: barcodePileup = true; break;
       case 10017: sitesPath = optarg; break;
+      case 10018: phase = true; break;
       default: fprintf(stderr, "%s", kAnalyzerUsage); return EXIT_FAILURE;
     }
   }
@@ -950,7 +1063,7 @@ int t1k_analyzer_main(int argc, char **argv) {
   }
   if (!umiPath.empty() && barcode.empty()) { fprintf(stderr, "--umi needs --barcode.\n"); return EXIT_FAILURE; }
   if (barcodePileup && barcode.empty()) { fprintf(stderr, "--barcodePileup needs --barcode.\n"); return EXIT_FAILURE; }
-  if (!sitesPath.empty() && !barcodePileup) { fprintf(stderr, "--sites has no meaning without --barcodePileup: ignored.\n"); sitesPath.clear(); }
+  if (!sitesPath.empty() && !barcodePileup && !phase) { fprintf(stderr, "--sites has no meaning without --barcodePileup or --phase: ignored.\n"); sitesPath.clear(); }
   if (umiMismatchText) {
     if (strcmp(umiMismatchText, "0") && strcmp(umiMismatchText, "1")) { fprintf(stderr, "--umiMismatch needs 0 or 1.\n"); return EXIT_FAILURE; }
     umiMismatch = atoi(umiMismatchText);
@@ -1003,6 +1116,12 @@ int t1k_analyzer_main(int argc, char **argv) {
       fputs(kBarcodePileupHeader, fs);
       fclose(fs);
     }
+    if (phase) {
+      FILE *fs = fopen((prefix + "_allele_phase.tsv").c_str(), "w");
+      if (!fs) { fprintf(stderr, "analyzer: cannot write %s_allele_phase.tsv\n", prefix.c_str()); return EXIT_FAILURE; }
+      fputs(kPhaseHeader, fs);
+      fclose(fs);
+    }
     logLine("Post analysis finishes.");
     return 0;
   }
@@ -1014,7 +1133,8 @@ int t1k_analyzer_main(int argc, char **argv) {
     return EXIT_FAILURE;
   }
   job->analyzer = true;
-  std::unique_ptr<AnalyzerSitepile> sp(barcodePileup ? new AnalyzerSitepile : nullptr);
+  std::unique_ptr<AnalyzerSitepile> sp(barcodePileup || phase ? new AnalyzerSitepile : nullptr);
+  if (sp) { sp->barcodes = barcodePileup; sp->phase = phase; }
   if (sp && !sitesPath.empty() && !analyzerReadSites(job, sitesPath, *sp)) { t1k_job_destroy(job); return EXIT_FAILURE; }
   const bool paired = !f2.empty();
   const std::vector<const char *> &first = !f1.empty() ? f1 : single;
@@ -1045,7 +1165,7 @@ int t1k_analyzer_main(int argc, char **argv) {
       bcOf[f] = it->second;
     }
   }
-  if (sp && !in.hasBarcode) { fprintf(stderr, "analyzer: --barcodePileup: the barcode file gave no barcodes\n"); t1k_job_destroy(job); return EXIT_FAILURE; }
+  if (barcodePileup && !in.hasBarcode) { fprintf(stderr, "analyzer: --barcodePileup: the barcode file gave no barcodes\n"); t1k_job_destroy(job); return EXIT_FAILURE; }
   if (sp) sp->bcOf = &bcOf;
   AnalyzerVariants V;
   std::unique_ptr<AnalyzerPileup> pile(pileup ? new AnalyzerPileup : nullptr);
@@ -1055,7 +1175,7 @@ int t1k_analyzer_main(int argc, char **argv) {
     logLine("Finish allele quantification in %d EM iterations.", V.emIterations);
   } else if (pileup || (sp && !sp->fileSites.empty())) {
     // no variant is called, but the pileup is of the alignments of steps (1) - (3): they run, VariantCaller does not (V.vc stays empty: the
-    // VCF is the empty file and the per-barcode table counts the raw lists).  --barcodePileup without sites of its own has nothing to book.
+    // VCF is the empty file and the per-barcode table counts the raw lists).  --barcodePileup and --phase without sites of their own have nothing to book.
     rc = analyzerAlignAssignments(job, V, pile.get(), sp.get());
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
   } else if (barcodeEM && emPrior > 0) {
@@ -1079,7 +1199,9 @@ int t1k_analyzer_main(int argc, char **argv) {
     pile.reset();
   }
   if (sp) {
-    if (!analyzerSitepile(job, prefix, V, *sp, names)) { t1k_job_destroy(job); return EXIT_FAILURE; }
+    const AnalyzerSiteList siteList(job, V, *sp);
+    if (barcodePileup && !analyzerSitepile(job, prefix, V, *sp, siteList, names)) { t1k_job_destroy(job); return EXIT_FAILURE; }
+    if (phase && !analyzerPhase(job, prefix, V, *sp, siteList)) { t1k_job_destroy(job); return EXIT_FAILURE; }
     sp.reset();
   }
   if (in.hasBarcode) {

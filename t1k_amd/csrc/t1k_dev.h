@@ -752,6 +752,23 @@ struct T1kDevBuf {
   size_t bytes = 0;
 };
 
+// what the sparse analyzer stages keep between their _begin and _end (t1k_table.h)
+// a set of sites: one device block [site bitmap | rank directory | alleleOff], its pieces at `at`; off: alleleOff on the host
+struct T1kSiteMap {
+  T1kDevBuf buf;
+  size_t at[3] = {0, 0, 0};
+  uint64_t nSites = 0;
+  std::vector<uint64_t> off;
+};
+// a sparse count table: `runs` folded (key, count) pairs, then `pending` keys of count 1, room for `cap`; the fold's scratch; the pending
+// keys that start a fold; keys taken and folds run so far, the folds' device time; the bits of the largest possible key
+struct T1kCountTable {
+  T1kDevBuf keys, vals, work;
+  uint64_t runs = 0, pending = 0, cap = 0, bound = 0, emitted = 0, folds = 0;
+  int endBit = 64;
+  double foldMs = 0;
+};
+
 struct t1k_ctx {
   int device = 0;
   std::vector<unsigned long long> hRaw;  // last fetched counter block (control | statistics stripes | arena cursors)
@@ -838,16 +855,20 @@ struct t1k_ctx {
   T1kDevBuf bPileup, bPileupIn;
   bool pileupOpen = false;
   std::vector<uint64_t> pileupOff, pileupLoad;
-  // per-barcode pileup at sites (t1k_sitepile.hip), open from t1k_sitepile_begin to _end: [site bitmap | rank directory | alleleOff] (pieces at
-  // spSiteAt), the table -- spRuns folded (key, count) pairs, then spPending keys of count 1, room for spCap -- the fold's scratch and the
-  // staging block of one _add call
-  T1kDevBuf bSpSites, bSpKeys, bSpVals, bSpWork, bSpIn;
+  // per-barcode pileup at sites (t1k_sitepile.hip), open from t1k_sitepile_begin to _end: its sites, its table of (barcode, site, plane,
+  // uniq) cells and the staging block of one _add call
+  T1kSiteMap spMap;
+  T1kCountTable spTab;
+  T1kDevBuf bSpIn;
   bool spOpen = false;
-  std::vector<uint64_t> spOff;
-  size_t spSiteAt[3] = {0, 0, 0};
-  uint64_t spSites = 0, spBarcodes = 0, spRuns = 0, spPending = 0, spCap = 0, spBound = 0, spEmitted = 0, spFolds = 0;
-  int spEndBit = 64;
-  double spFoldMs = 0;
+  uint64_t spBarcodes = 0;
+  // read-backed phasing of site pairs (t1k_phase.hip), open from t1k_phase_begin to _end: its sites, its table of (site pair, state pair,
+  // uniq) cells, the staging block of one _add call, that call's observation words and merge arena, and what _stats reports
+  T1kSiteMap phMap;
+  T1kCountTable phTab;
+  T1kDevBuf bPhIn, bPhObs, bPhArena;
+  bool phOpen = false;
+  uint64_t phObs = 0, phBookings = 0, phDiscordant = 0;
   t1k_stats stats{};
 };
 
