@@ -302,6 +302,11 @@ int t1k_extract_batch(t1k_ctx *ctx, uint32_t endsPerFragment, uint8_t *good, uin
 /* production match-count routine (exact <=3-mismatch fast path + banded forward sweep) on equal-length jobs: nMatch only */
 int t1k_align_count_batch(t1k_ctx *ctx, const char *text, const uint32_t *tOff, const char *pat, const uint32_t *pOff, const uint32_t *len, uint32_t nJobs,
                           int32_t *nMatch);
+/* the gap alignment of the dense DP phase itself (no fast path), one lane per job, for |tLen - pLen| <= 4: nMatch only.  Job i's text is
+ * text[tOff[i] .. + tLen[i]) and lies at position tOff[i] of ONE packed stream made of text[0 .. max(tOff + tLen)) (likewise the patterns), so the
+ * caller decides where a window falls against the stream's 32-base words; a text without N is read without its N mask. */
+int t1k_gap_count_batch(t1k_ctx *ctx, const char *text, const uint32_t *tOff, const uint32_t *tLen, const char *pat, const uint32_t *pOff,
+                        const uint32_t *pLen, uint32_t nJobs, int32_t *nMatch);
 int t1k_align_batch(t1k_ctx *ctx, const char *text, const uint32_t *tOff, const uint32_t *tLen, const char *pat, const uint32_t *pOff,
                     const uint32_t *pLen, uint32_t nJobs, int32_t *score, int32_t *nMatch, int32_t *nMismatch, int32_t *nIndel, int8_t *ops,
                     const uint32_t *opsOff, uint32_t *nOps);

@@ -105,6 +105,7 @@ def lib():
     L.t1k_coverage_absorb.argtypes = [vp, vp]
     L.t1k_align_batch.argtypes = [vp, C.c_char_p, vp, vp, C.c_char_p, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
     L.t1k_align_count_batch.argtypes = [vp, C.c_char_p, vp, C.c_char_p, vp, vp, C.c_uint32, vp]
+    L.t1k_gap_count_batch.argtypes = [vp, C.c_char_p, vp, vp, C.c_char_p, vp, vp, C.c_uint32, vp]
     L.t1k_em_setup.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, ALLREDUCE_FN, vp]
     L.t1k_em_update.argtypes = [vp, vp, vp, vp, vp]
     L.t1k_em_shard.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
@@ -402,6 +403,20 @@ class Context:
         out = np.zeros(n, np.int32)
         self._check(lib().t1k_align_count_batch(self.h, tb, _ptr(toff[:-1].astype(np.uint32)), pb, _ptr(poff[:-1].astype(np.uint32)), _ptr(ln), n,
                                                 _ptr(out)), "t1k_align_count_batch")
+        return out
+
+    def gap_count_batch(self, texts, pats, lead=""):
+        """the routine of the dense DP phase (gapAlign: no fast path), one lane per job, |len(text) - len(pat)| <= 4.  The texts lie back to back in one
+        packed stream behind `lead` (which shifts them against the stream's word boundaries), the patterns back to back in another; a stream of
+        texts without N is read without its N mask, as a reference without N is"""
+        n = len(texts)
+        tb, toff = _concat([lead] + list(texts))
+        pb, poff = _concat(pats)
+        tlen = np.array([len(t) for t in texts], dtype=np.uint32)
+        plen = np.array([len(p) for p in pats], dtype=np.uint32)
+        out = np.zeros(n, np.int32)
+        self._check(lib().t1k_gap_count_batch(self.h, tb, _ptr(toff[1:-1].astype(np.uint32)), _ptr(tlen), pb, _ptr(poff[:-1].astype(np.uint32)), _ptr(plen), n,
+                                              _ptr(out)), "t1k_gap_count_batch")
         return out
 
     def em_setup(self, row_ptr, ec_idx, count, ec_len, allreduce=None, raw=False):

@@ -53,12 +53,12 @@ struct CandOut {  // packed candidates: 3 u32 each (+ 3 u32 of memo references w
 // seed-chain match count of one gap (SeqSet.hpp:1710-1752 / 1794-1824)
 __device__ inline int gapMatches(const ReadCtx &c, int ra, int ga, int lp, int lt, int *gaScratch, int gaMax, unsigned int *dpCounter, unsigned long long *errFlags,
                                  bool *needScratch) {
-  if (lp == lt) return t1k_ga_matches_window(c.rb, c.rn, ra, c.gb, c.gn, c.goff + ga, lp, dpCounter);
+  if (lp == lt) return t1k_ga_matches_window(c.rb, c.rn, ra, c.gb, c.gn, c.goff + ga, lp, dpCounter, c.refN);
   if (lt == 0 || lp == 0) return 0;
   if (dpCounter) ++*dpCounter;
-  T1kSeqView T{c.gb, c.gn, c.goff + ga}, P{c.rb, c.rn, ra};
+  T1kSeqView T{c.gb, c.gn, c.goff + ga, c.refN}, P{c.rb, c.rn, ra};
   const int diff = lt > lp ? lt - lp : lp - lt;
-  if (diff <= 4) return t1k_ga_band<4, false>(T, lt, P, lp, nullptr, 0);  // band in registers
+  if (diff <= 4) return t1k_ga_count(T, lt, P, lp);  // band in registers
   if (!gaScratch) { *needScratch = true; return 0; }
   int nm = 0;
   if (lt > gaMax) { atomicOr(errFlags, (unsigned long long)ERR_BIGGROUP); return 0; }
@@ -558,8 +558,8 @@ __global__ __launch_bounds__(WG) void k_dp_dense(ChainArgs P, const uint32_t *jo
     const unsigned long long e = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int sb = (int)(e & 1), d = (int)((e >> 1) & 0xF) - 4, lp = (int)((e >> 5) & 0x1FF), readPos = (int)((e >> 14) & 0x7FF);
     const int S = P.reads.S;
-    ReadCtx c{P.reads.bases + ((uint64_t)re * 2 + sb) * S, P.reads.nmask + ((uint64_t)re * 2 + sb) * S, 0, P.ref.bases, P.ref.nmask, 0, 0, true};
-    const int m = gapAlign(c, readPos, GAP_GPOS(e), lp, lp + d);
+    ReadCtx c{P.reads.bases + ((uint64_t)re * 2 + sb) * S, P.reads.nmask + ((uint64_t)re * 2 + sb) * S, 0, P.ref.bases, P.ref.nmask, 0, 0, P.ref.anyN != 0};
+    const int m = gapAlign<true>(c, readPos, GAP_GPOS(e), lp, lp + d);  // (lengths as gapMatchesCached registered them)
     ++dpLocal;
     __hip_atomic_store(slot, (e & ~(GAP_PENDING << 25)) | ((unsigned long long)m << 25), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }

@@ -239,6 +239,7 @@ __device__ inline bool t1k_same_window(const uint64_t *gb, const uint64_t *gn, i
 struct T1kSeqView {
   const uint64_t *b, *n;
   int64_t pos;
+  bool anyN = true;  // false: the caller knows that n holds no set bit (T1kRefDev::anyN == 0); the one-word routines then do not load it
   __device__ __forceinline__ int code(int i) const {  // 0..3, or 4 for N
     int64_t p = pos + i;
     return t1k_bit(n, p) ? 4 : t1k_base(b, p);
@@ -400,7 +401,7 @@ __device__ inline void t1k_ga_equal_traced(const T1kSeqView &T, const T1kSeqView
 //   TRACE = true : stores one 64-bit word of 4-bit decisions per row (b0 diagonal reproduces m, b1 f >= e, b2 e opened from
 //                  m, b3 f opened from m) at trace[i * stride]; whether two bases compare equal is re-derived by the walker.
 template <int DMAX, bool TRACE>
-__device__ inline int t1k_ga_band(const T1kSeqView &T, int lent, const T1kSeqView &P, int lenp, uint64_t *trace, size_t stride) {
+__device__ inline int t1k_ga_band(const T1kSeqView &T, int lent, const T1kSeqView &P, int lenp, uint64_t *trace, size_t stride, int *scoreOut = nullptr) {
   constexpr int NS = 13 + DMAX;
   const int LB = 5 + (lenp > lent ? lenp - lent : 0), RB = 5 + (lent > lenp ? lent - lenp : 0);
   const int last = LB + RB + 2;  // right fence slot
@@ -463,26 +464,179 @@ __device__ inline int t1k_ga_band(const T1kSeqView &T, int lent, const T1kSeqVie
   int res = 0;
 #pragma unroll
   for (int s = 0; s < NS; ++s)
-    if (s == lent - lenp + LB + 1) res = cm[s];
+    if (s == lent - lenp + LB + 1) { res = cm[s]; if (scoreOut) *scoreOut = m[s]; }
   return res;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The same two forward sweeps (t1k_ga_matches_equal, t1k_ga_band<DMAX, false>) with ONE signed word per DP state:
+//   word = score * 2048 + prio * 512 + count        (count: 9 bits, prio: 2 bits, score: the upper 21 bits)
+// The traceback's choice at a cell is a max with a fixed tie order (e and f: the source from m wins a tie; m: the diagonal
+// wins, then f if f >= e, then e).  With the tie order written into `prio` of the candidates, one integer max selects
+// score, tie-break and the count that travels with the winner at once; prio is cleared again before a word is kept.  The
+// counts need no arrays and no selects of their own.  m is kept as mo = m + T1K_GAW_OPEN (m - 5 with prio 1): that is the
+// candidate the cell hands to the e of the cell below and to the f of the cell to its right, and the diagonal's constants
+// take the offset back out.
+// Range: count <= min(lent, lenp) must stay below 512, and the smallest value ever formed, negInf - 5 with
+// negInf = -4 (lent + 1)(lenp + 1) (a fence cell's m - 5; nothing real lies below negInf, real cells being bounded by
+// -4 - 6 max(lent, lenp) - 5, and a fence is set to negInf anew in every row, so nothing drifts further), must fit the
+// score field: 4 (lent + 1)(lenp + 1) + 5 <= 2^20, i.e. (lent + 1)(lenp + 1) <= 262142 -- equal lengths up to 510, which
+// also keeps the count below 512 (512 x 512 cells are beyond it).  t1k_ga_word_ok() is that test; beyond it the callers
+// take the int32 band sweep above (t1k_ga_count).  Scores never exceed 2 * 511 + the row-0 values left of column 0 (< 64).
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int T1K_GAW_ONE = 1 << 11;                           // one unit of score
+constexpr int T1K_GAW_PRIO = 1 << 9;                           // one step of tie priority
+constexpr int T1K_GAW_CLEAR = ~(3 << 9);
+constexpr int T1K_GAW_OPEN = -5 * T1K_GAW_ONE + T1K_GAW_PRIO;  // gap opened from m: beats the extended gap (-1, prio 0) on a tie
+constexpr int T1K_GAW_DIAG_EQ = 2 * T1K_GAW_ONE + 1 + 2 * T1K_GAW_PRIO - T1K_GAW_OPEN;  // applied to mo: score + 2, count + 1, highest priority
+constexpr int T1K_GAW_DIAG_NE = -2 * T1K_GAW_ONE + 2 * T1K_GAW_PRIO - T1K_GAW_OPEN;
+constexpr int T1K_GAW_MAX_CELLS = 262142;                      // largest (lent + 1)(lenp + 1)
+static_assert((4ll * T1K_GAW_MAX_CELLS + 5) * T1K_GAW_ONE <= (1ll << 31), "negInf - 5 must fit the score field");
+static_assert((4ll * (T1K_GAW_MAX_CELLS + 1) + 5) * T1K_GAW_ONE > (1ll << 31), "the bound is the exact one");
+static_assert(511ll * 511 <= T1K_GAW_MAX_CELLS && 513ll * 513 > T1K_GAW_MAX_CELLS, "memoisable jobs (lengths <= 510) fit, counts of 512 cannot occur");
+__device__ __forceinline__ bool t1k_ga_word_ok(int lent, int lenp) { return (int64_t)(lent + 1) * (lenp + 1) <= T1K_GAW_MAX_CELLS; }
+
+// The text bases under the band, kept in registers: 32 positions from `base` on serve the rows until the band's `need` columns run
+// past them (every 32 - need + 1 rows) instead of two lane-private 16-byte loads per row.  eq(): bit 2c = text position tw + c
+// compares equal to the pattern base (an N on either side matches anything), for c = 0 .. need - 1; tw may be negative in the
+// first rows (bits of positions before the text are not looked at: those cells are boundary cells).
+struct T1kTextWin {
+  uint64_t b = 0, n = 0;
+  int base = -64;
+  __device__ __forceinline__ uint32_t eq(const T1kSeqView &T, int tw, int need, int pc, bool pIsN, bool inside = false) {  // inside: the caller knows tw >= 0
+    const int t0 = tw > 0 ? tw : 0;
+    if (t0 + need > base + 32) { b = t1k_get32(T.b, T.pos + t0); n = T.anyN ? t1k_get32(T.n, T.pos + t0) : 0; base = t0; }
+    const int sh = 2 * (tw - base);  // -2 (need - 1) .. 2 (32 - need)
+    const uint32_t wb = (uint32_t)(inside || sh >= 0 ? b >> sh : b << -sh), wn = (uint32_t)(inside || sh >= 0 ? n >> sh : n << -sh);
+    const uint32_t x = wb ^ ((uint32_t)(pc & 3) * (uint32_t)T1K_EVEN);
+    return pIsN ? ~0u : (~(x | (x >> 1)) | wn);
+  }
+};
+
+__device__ inline int t1k_ga_matches_equal_w(const T1kSeqView &T, const T1kSeqView &P, int L, int *scoreOut) {
+  const int NEG = (L + 1) * (L + 1) * -4 * T1K_GAW_ONE;
+  int mo[13], e[13];
+#pragma unroll
+  for (int s = 0; s < 13; ++s) {  // row 0
+    int j = s - 6;
+    if (j == 0) { mo[s] = T1K_GAW_OPEN; e[s] = 0; }
+    else { mo[s] = (-4 - 4 * j) * T1K_GAW_ONE + T1K_GAW_OPEN; e[s] = (-4 - 4 * (L + 1)) * T1K_GAW_ONE; }
+  }
+  uint64_t pwB = 0, pwN = 0;
+  T1kTextWin W;
+  auto row = [&](int i, auto interiorTag) {  // the three row classes of t1k_ga_matches_equal
+    constexpr bool INTERIOR = decltype(interiorTag)::value;
+    if (((i - 1) & 31) == 0) { pwB = t1k_get32(P.b, P.pos + i - 1); pwN = t1k_get32(P.n, P.pos + i - 1); }
+    const int pq = ((i - 1) & 31) * 2;
+    const bool pIsN = (pwN >> pq) & 1;
+    const uint32_t eqm = W.eq(T, i - 6, 11, (int)((pwB >> pq) & 3), pIsN, INTERIOR);  // bit 2(s-1): slot s, text position i + s - 7
+    int fLeft = NEG, moLeft = NEG + T1K_GAW_OPEN;
+#pragma unroll
+    for (int s = 0; s < 13; ++s) {
+      int j = i + s - 6;
+      int nm, ne, nf;
+      if (!INTERIOR && j < 0) { nm = ne = nf = NEG; }
+      else if (!INTERIOR && j == 0) { nm = (-4 - 4 * i) * T1K_GAW_ONE; ne = (-4 - i) * T1K_GAW_ONE; nf = nm; }
+      else if (s == 0 || s == 12 || (!INTERIOR && j > L)) { nm = ne = nf = NEG; }
+      else {
+        const int eu = e[s + 1] - T1K_GAW_ONE, fl = fLeft - T1K_GAW_ONE;
+        ne = (eu > mo[s + 1] ? eu : mo[s + 1]) & T1K_GAW_CLEAR;
+        nf = (fl > moLeft ? fl : moLeft) & T1K_GAW_CLEAR;
+        const int dg = mo[s] + (((eqm >> (2 * (s - 1))) & 1) ? T1K_GAW_DIAG_EQ : T1K_GAW_DIAG_NE), fp = nf + T1K_GAW_PRIO;
+        nm = dg > fp ? dg : fp;
+        nm = (nm > ne ? nm : ne) & T1K_GAW_CLEAR;
+      }
+      mo[s] = nm + T1K_GAW_OPEN; e[s] = ne;
+      fLeft = nf; moLeft = mo[s];
+    }
+  };
+  int i = 1;
+#pragma nounroll
+  for (; i <= L && i < 7; ++i) row(i, std::false_type{});
+#pragma nounroll
+  for (; i <= L - 5; ++i) row(i, std::true_type{});
+#pragma nounroll
+  for (; i <= L; ++i) row(i, std::false_type{});
+  const int m = mo[6] - T1K_GAW_OPEN;
+  if (scoreOut) *scoreOut = m >> 11;
+  return m & 511;
+}
+
+template <int DMAX>
+__device__ inline int t1k_ga_band_w(const T1kSeqView &T, int lent, const T1kSeqView &P, int lenp, int *scoreOut) {
+  constexpr int NS = 13 + DMAX;
+  static_assert(2 * (NS - 3) <= 32, "the band's columns must fit the 32-bit comparison word");
+  const int LB = 5 + (lenp > lent ? lenp - lent : 0), RB = 5 + (lent > lenp ? lent - lenp : 0);
+  const int last = LB + RB + 2;
+  const int NEG = (lent + 1) * (lenp + 1) * -4 * T1K_GAW_ONE;
+  int mo[NS], e[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {  // row 0
+    int j = s - (LB + 1);
+    if (j == 0) { mo[s] = T1K_GAW_OPEN; e[s] = 0; }
+    else { mo[s] = (-4 - 4 * j) * T1K_GAW_ONE + T1K_GAW_OPEN; e[s] = (-4 - 4 * (lenp + 1)) * T1K_GAW_ONE; }
+  }
+  uint64_t pwB = 0, pwN = 0;
+  T1kTextWin W;
+#pragma nounroll
+  for (int i = 1; i <= lenp; ++i) {
+    if (((i - 1) & 31) == 0) { pwB = t1k_get32(P.b, P.pos + i - 1); pwN = t1k_get32(P.n, P.pos + i - 1); }
+    const int pq = ((i - 1) & 31) * 2;
+    const uint32_t eqm = W.eq(T, i - LB - 1, LB + RB + 1, (int)((pwB >> pq) & 3), (pwN >> pq) & 1);  // bit 2(s-1): slot s, text position i + s - LB - 2
+    int fLeft = NEG, moLeft = NEG + T1K_GAW_OPEN;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      int j = i + s - (LB + 1);
+      int nm, ne, nf;
+      if (s > last || j < 0) { nm = ne = nf = NEG; }
+      else if (j == 0) { nm = (-4 - 4 * i) * T1K_GAW_ONE; ne = (-4 - i) * T1K_GAW_ONE; nf = nm; }
+      else if (j > lent || s == 0 || s == last) { nm = ne = nf = NEG; }
+      else {
+        const int up = s + 1 < NS ? s + 1 : s;  // s + 1 <= last < NS whenever this branch is live
+        const int eu = e[up] - T1K_GAW_ONE, fl = fLeft - T1K_GAW_ONE;
+        ne = (eu > mo[up] ? eu : mo[up]) & T1K_GAW_CLEAR;
+        nf = (fl > moLeft ? fl : moLeft) & T1K_GAW_CLEAR;
+        const int dg = mo[s] + (((eqm >> (2 * (s > 0 ? s - 1 : 0))) & 1) ? T1K_GAW_DIAG_EQ : T1K_GAW_DIAG_NE), fp = nf + T1K_GAW_PRIO;
+        nm = dg > fp ? dg : fp;
+        nm = (nm > ne ? nm : ne) & T1K_GAW_CLEAR;
+      }
+      mo[s] = nm + T1K_GAW_OPEN; e[s] = ne;
+      fLeft = nf; moLeft = mo[s];
+    }
+  }
+  int m = 0;
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+    if (s == lent - lenp + LB + 1) m = mo[s] - T1K_GAW_OPEN;
+  if (scoreOut) *scoreOut = m >> 11;
+  return m & 511;
+}
+
+// number of MATCH columns of GlobalAlignment for |lent - lenp| <= 4: the one-word sweeps within their range, the int32 sweep beyond it (lengths above
+// 509: reads of the long-read windows only).  The way out is t1k_ga_band<4, false> for equal lengths too -- it computes what t1k_ga_matches_equal does,
+// cell by cell -- so that a kernel carries ONE int32 band inline next to the one-word ones: with both int32 forms behind this test k_chain_general and
+// k_chain_wave were allocated 248 VGPRs and more scratch (183 and 104 before).
+__device__ __forceinline__ int t1k_ga_count(const T1kSeqView &T, int lent, const T1kSeqView &P, int lenp, int *scoreOut = nullptr) {
+  if (t1k_ga_word_ok(lent, lenp)) return lent == lenp ? t1k_ga_matches_equal_w(T, P, lenp, scoreOut) : t1k_ga_band_w<4>(T, lent, P, lenp, scoreOut);
+  return t1k_ga_band<4, false>(T, lent, P, lenp, nullptr, 0, scoreOut);
 }
 
 // Exact fast path for equal lengths: with x <= 3 mismatches the ungapped alignment is optimal and is the one the
 // traceback returns (any gapped alignment of equal-length strings scores <= 2L-12 <= 2L-4x, ties go to the diagonal).
 __device__ __forceinline__ int t1k_ga_matches_window(const uint64_t *rb, const uint64_t *rn, int64_t rpos, const uint64_t *gb, const uint64_t *gn,
-                                                      int64_t gpos, int L, unsigned int *dpCounter) {
+                                                      int64_t gpos, int L, unsigned int *dpCounter, bool refN = true) {
   if (L <= 0) return 0;
   int x = t1k_hamming(rb, rn, rpos, gb, gn, gpos, L);
   if (x <= 3) return L - x;
   if (dpCounter) ++*dpCounter;  // thread-local tally, flushed once per workgroup by the caller
-  T1kSeqView T{gb, gn, gpos}, P{rb, rn, rpos};
+  T1kSeqView T{gb, gn, gpos, refN}, P{rb, rn, rpos};
 #ifdef T1K_PHASE_TIMERS
   long long t0_ = clock64();
-  int r_ = t1k_ga_matches_equal(T, P, L, nullptr);
+  int r_ = t1k_ga_count(T, L, P, L);
   if (dpCounter) { dpCounter[1] += (unsigned int)((clock64() - t0_) >> 6); dpCounter[2] += (unsigned int)L; }
   return r_;
 #else
-  return t1k_ga_matches_equal(T, P, L, nullptr);
+  return t1k_ga_count(T, L, P, L);
 #endif
 }
 

@@ -19,6 +19,7 @@
 #include <cstring>
 #include "t1k_dev.h"
 #include "t1k_launch.h"
+#include "t1k_memo.h"
 
 // The two step sizes of the ordered sums (t1k_em_limits reports them): an ordered piece is one wavefront of operands; the class pass takes
 // EM_K pieces per step.
@@ -190,6 +191,28 @@ __global__ void k_align_count(const uint64_t *tb, const uint64_t *tn, const uint
   nMatch[q] = t1k_ga_matches_window(pb, pn, (int64_t)pPos[q], tb, tn, (int64_t)tPos[q], (int)len[q], nullptr);
 }
 
+// the routine of k_dp_dense (gapAlign, t1k_memo.h: the one-word sweeps; beyond their range, where the memo takes no job, the int32 way out of the inline
+// callers), one lane per job, on sequences that lie where the caller put them in two packed streams
+__global__ void k_gap_count(const uint64_t *tb, const uint64_t *tn, const uint64_t *pb, const uint64_t *pn, const uint32_t *tPos, const uint32_t *pPos,
+                            const uint32_t *tLen, const uint32_t *pLen, uint32_t nJobs, bool textN, int32_t *nMatch) {
+  uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nJobs) return;
+  const ReadCtx c{pb, pn, 0, tb, tn, 0, 0, textN};
+  nMatch[q] = gapAlign(c, (int)pPos[q], (int64_t)tPos[q], (int)pLen[q], (int)tLen[q]);
+}
+
+// the first `total` characters of s as ONE packed stream (character i at position i); returns whether it holds anything but ACGT
+static bool packWhole(const char *s, uint64_t total, std::vector<uint64_t> &b, std::vector<uint64_t> &nm) {
+  b.assign(total / 32 + 4, 0); nm.assign(total / 32 + 4, 0);
+  bool anyN = false;
+  for (uint64_t p = 0; p < total; ++p) {
+    const char c = s[p];
+    const int code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4;
+    if (code == 4) { nm[p >> 5] |= 1ull << ((p & 31) * 2); anyN = true; } else b[p >> 5] |= (uint64_t)code << ((p & 31) * 2);
+  }
+  return anyN;
+}
+
 static void packStream(const char *s, const uint32_t *off, const uint32_t *len, uint32_t n, std::vector<uint64_t> &b, std::vector<uint64_t> &nm,
                        std::vector<uint64_t> &pos) {
   uint64_t total = 0;
@@ -291,6 +314,38 @@ int t1k_align_count_batch(t1k_ctx *ctx, const char *text, const uint32_t *tOff, 
   if ((rc = t1k_ensure(ctx, B[9], (size_t)nJobs * 4 + 64))) return rc;
   hipLaunchKernelGGL(k_align_count, dim3((nJobs + 255) / 256), dim3(256), 0, ctx->stream, (uint64_t *)B[0].p, (uint64_t *)B[1].p, (uint64_t *)B[2].p,
                      (uint64_t *)B[3].p, (uint64_t *)B[4].p, (uint64_t *)B[5].p, (uint32_t *)B[6].p, nJobs, (int32_t *)B[9].p);
+  T1K_HIP(ctx, hipMemcpyAsync(nMatch, B[9].p, (size_t)nJobs * 4, hipMemcpyDeviceToHost, ctx->stream));
+  T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return T1K_OK;
+}
+
+int t1k_gap_count_batch(t1k_ctx *ctx, const char *text, const uint32_t *tOff, const uint32_t *tLen, const char *pat, const uint32_t *pOff, const uint32_t *pLen,
+                        uint32_t nJobs, int32_t *nMatch) {
+  if (!ctx || !text || !pat || !tOff || !pOff || !tLen || !pLen || !nMatch) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_gap_count_batch: bad arguments");
+  if (nJobs == 0) return T1K_OK;
+  uint64_t tTotal = 0, pTotal = 0;
+  for (uint32_t i = 0; i < nJobs; ++i) {
+    const int64_t d = (int64_t)tLen[i] - (int64_t)pLen[i];
+    if (d < -4 || d > 4 || tLen[i] == 0 || pLen[i] == 0 || (d == 0 && tLen[i] < 2) || tLen[i] > 2048 || pLen[i] > 2048)
+      return t1k_fail(ctx, T1K_ERR_ARG, "t1k_gap_count_batch: lengths must be 1 .. 2048 (2 .. when equal) and differ by at most 4");
+    tTotal = std::max<uint64_t>(tTotal, (uint64_t)tOff[i] + tLen[i]);
+    pTotal = std::max<uint64_t>(pTotal, (uint64_t)pOff[i] + pLen[i]);
+  }
+  if (tTotal >= (1ull << 30) || pTotal >= (1ull << 30)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_gap_count_batch: streams of 2^30 bases or more");
+  T1K_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<uint64_t> tb, tn, pb, pn;
+  const bool textN = packWhole(text, tTotal, tb, tn);  // no N in the text: the routine does not load the text's N mask (a reference without N)
+  packWhole(pat, pTotal, pb, pn);
+  T1kDevBuf *B = ctx->bAlign;
+  int rc;
+  std::vector<uint32_t> to(tOff, tOff + nJobs), po(pOff, pOff + nJobs), tl(tLen, tLen + nJobs), pl(pLen, pLen + nJobs);
+  if ((rc = up(ctx, B[0], tb)) || (rc = up(ctx, B[1], tn)) || (rc = up(ctx, B[2], pb)) || (rc = up(ctx, B[3], pn)) || (rc = up(ctx, B[4], to)) ||
+      (rc = up(ctx, B[5], po)) || (rc = up(ctx, B[6], tl)) || (rc = up(ctx, B[7], pl)))
+    return rc;
+  if ((rc = t1k_ensure(ctx, B[9], (size_t)nJobs * 4 + 64))) return rc;
+  hipLaunchKernelGGL(k_gap_count, dim3((nJobs + 255) / 256), dim3(256), 0, ctx->stream, (const uint64_t *)B[0].p, (const uint64_t *)B[1].p, (const uint64_t *)B[2].p,
+                     (const uint64_t *)B[3].p, (const uint32_t *)B[4].p, (const uint32_t *)B[5].p, (const uint32_t *)B[6].p, (const uint32_t *)B[7].p, nJobs, textN,
+                     (int32_t *)B[9].p);
   T1K_HIP(ctx, hipMemcpyAsync(nMatch, B[9].p, (size_t)nJobs * 4, hipMemcpyDeviceToHost, ctx->stream));
   T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return T1K_OK;

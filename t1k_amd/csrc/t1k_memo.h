@@ -36,11 +36,17 @@ struct GapSink {  // where deferred alignments are registered
   int arena;
 };
 
-// the alignment itself: lp read positions from readPos against lt allele positions from gpos, |lt - lp| <= 4
+// longest side of a job the memo takes: 9 bits of an entry hold the length and the match count (511 = GAP_PENDING), and every such job lies
+// within the range of the one-word sweeps (t1k_ga_word_ok)
+#define GAP_MEMO_MAXLEN 510
+static_assert((GAP_MEMO_MAXLEN + 1) * (GAP_MEMO_MAXLEN + 1) <= T1K_GAW_MAX_CELLS, "a memoised job must fit the one-word sweeps");
+// the alignment itself: lp read positions from readPos against lt allele positions from gpos, |lt - lp| <= 4.  MEMO: the job comes out of the memo
+// (both sides <= GAP_MEMO_MAXLEN, gapMatchesCached registers nothing longer), so the int32 way out of t1k_ga_count is not compiled in
+template <bool MEMO = false>
 __device__ __forceinline__ int gapAlign(const ReadCtx &c, int readPos, int64_t gpos, int lp, int lt) {
-  T1kSeqView T{c.gb, c.gn, gpos}, P{c.rb, c.rn, (int64_t)readPos};
-  if (lp == lt) return t1k_ga_matches_equal(T, P, lp, nullptr);
-  return t1k_ga_band<4, false>(T, lt, P, lp, nullptr, 0);
+  T1kSeqView T{c.gb, c.gn, gpos, c.refN}, P{c.rb, c.rn, (int64_t)readPos};
+  if (MEMO) return lp == lt ? t1k_ga_matches_equal_w(T, P, lp, nullptr) : t1k_ga_band_w<4>(T, lt, P, lp, nullptr);
+  return t1k_ga_count(T, lt, P, lp);
 }
 
 // DEFER = true : never run a DP here.  A miss claims a memo slot (CAS) with the PENDING marker and appends the slot to the
@@ -67,7 +73,7 @@ __device__ inline int gapMatchesCached(const ReadCtx &c, int readPos, int64_t gp
     hsh ^= hsh >> 32;
   }
   if (d == 0 && x <= 3) return lp - x;  // exact fast path (see t1k_ga_matches_window)
-  if (lp > 510 || lt > 510 || readPos > 2047 || gpos >= (1ll << 30)) {
+  if (lp > GAP_MEMO_MAXLEN || lt > GAP_MEMO_MAXLEN || readPos > 2047 || gpos >= (1ll << 30)) {
     if (DEFER) return -2;  // not memoisable
     if (dpCounter) ++*dpCounter;
     return gapAlign(c, readPos, gpos, lp, lt);
@@ -116,7 +122,7 @@ __device__ inline int gapMatchesCached(const ReadCtx &c, int readPos, int64_t gp
     return -2;  // all probe slots taken by other jobs
   }
   if (dpCounter) ++*dpCounter;
-  const int m = gapAlign(c, readPos, gpos, lp, lt);
+  const int m = gapAlign<true>(c, readPos, gpos, lp, lt);  // (memoisable: checked above)
   if (!pendingSeen) {
     unsigned long long ne = ((unsigned long long)gpos << 34) | ((unsigned long long)m << 25) | idBits;
     unsigned long long cur = __hip_atomic_load(&cache[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
