@@ -445,7 +445,9 @@ int t1k_phase_end(t1k_ctx *ctx);
 typedef struct {
   uint64_t read_ends, lookups, postings, hits, groups, candidates, extended, near_best, dp_calls, rows, batches;
   /* kernel time (HIP events on the launch stream), summed over the batches of the last run:
-     ms_seed = k_seed_groups, ms_chain = the remaining chain kernels, ms_fullalign = k_fullalign + DP kernels + k_truncate */
+     ms_seed = k_seed_groups, ms_chain = the remaining chain kernels, ms_fullalign = k_fullalign + DP kernels + k_truncate (near zero for a
+     range whose lists k_select finishes itself: deferred coverage without relax_intron_align); extended = the overlaps the selection
+     emitted, before lists of more than 1000 are cut */
   double ms_seed, ms_chain, ms_extend, ms_select, ms_fullalign, ms_pair, ms_em, ms_total;
   /* job level (t1k_job_stats): read_ends above counts the DISTINCT read-ends the kernels ran on, read_ends_total all of them;
      pair_overlaps = overlap records read by mate pairing; dp_cells = cell updates of the traced alignment kernels;

@@ -10,6 +10,8 @@
 //   k_fullalign    one lane per kept overlap: near-best full alignment -> relaxedMatchCnt + base coverage as a
 //                  difference array (2188-2285); alignments that need a real DP traceback go to a queue (k_fullalign_slow)
 //   k_truncate     >1000 overlaps: re-sort and cut at similarity < best - 0.1 (2290-2298)
+// With the coverage deferred and no --relaxIntronAlign nothing runs between the selection and the cut: k_select's packed form does the cut
+// itself and writes the kept records to the overlap store (k_fullalign, k_truncate and the store's pack / publish kernels are not launched).
 #include "t1k_dev.h"
 #include "t1k_launch.h"
 #include "t1k_memo.h"
@@ -454,7 +456,10 @@ __device__ inline bool candBeforeFull(const T1kCand &a, const T1kCand &b) {
 #ifndef T1K_SELECT_SMALL_WAVES
 #define T1K_SELECT_SMALL_WAVES 7
 #endif
-template <int SELECT_LDS_CAP, int NT, bool XL>
+// PK, the packed form (no --relaxIntronAlign, coverage deferred: nothing reads the records between the selection and the cut): the lists
+// are finished here.  A list of more than 1000 emitted overlaps is put into _overlap::operator< order on the extended records and cut
+// (SeqSet.hpp:2290-2298) before anything is written, and the kept records go to the store in their 16-byte form, once.
+template <int SELECT_LDS_CAP, int NT, bool XL, bool PK>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_CAP == SELECT_SMALL ? T1K_SELECT_SMALL_WAVES : 8))) void k_select(SelectArgs P) {
   extern __shared__ uint64_t dynLds[];
   uint64_t *sKey = dynLds;
@@ -465,6 +470,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
   __shared__ uint16_t sCnt[256 * (NT / 64)];
   const int tid = threadIdx.x;
   unsigned int nbTotal = 0;
+  unsigned long long emitTotal = 0;  // (thread 0, PK) emitted overlaps before the cut: counters[1] counts the kept ones
+  // a read-end's list in the tables: where it starts in the range's records, its length; PK: also in the read set's list table
+  auto publish = [&](uint32_t re, uint32_t start, uint32_t count) {
+    P.ovlStart[re] = start; P.ovlCount[re] = count;
+    if (PK && !(P.reads.skip && P.reads.skip[re])) { P.listPtr[re] = (unsigned long long)(P.store + start); P.listCount[re] = count; }  // (a skipped entry comes from an earlier window: t1k_xwin_resolve)
+  };
   // read-ends are handed out one at a time (a device counter per launch): their cost is uneven, and a workgroup of this shape that waits
   // for a free CU would otherwise hold up its whole fixed share of them.  (Alone the kernels are 20 - 35 % faster for it; under three
   // pipelines the step is not: what one kernel gives back the others take.  64 at a time with the counts pre-read was slower.)
@@ -482,7 +493,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
     if (re >= P.reads.nReadEnds) break;
     const uint32_t n = P.candCount[re], c0 = P.candStart[re];
     if (n == 0) {
-      if (tid == 0 && SELECT_LDS_CAP == SELECT_SMALL) { P.ovlStart[re] = 0; P.ovlCount[re] = 0; }
+      if (tid == 0 && SELECT_LDS_CAP == SELECT_SMALL) publish(re, 0, 0);
       continue;
     }
     // every candidate of the list is sorted (the ones that failed the similarity filter were left out by k_collect; until round 4 this
@@ -492,7 +503,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
     if ((n > SELECT_SMALL) != (SELECT_LDS_CAP == SELECT_LARGE)) continue;  // the other instantiation's read-end
     const uint32_t live = n;
     if (live == 0) {
-      if (tid == 0) { P.ovlStart[re] = 0; P.ovlCount[re] = 0; }
+      if (tid == 0) publish(re, 0, 0);
       continue;
     }
     uint32_t np2 = 8;
@@ -501,7 +512,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
     if (np2 <= SELECT_LDS_CAP) key = sKey;
     else if (np2 <= P.sortCap) key = P.sortScratch + (uint64_t)blockIdx.x * P.sortCap * 6;
     else {
-      if (tid == 0) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); P.ovlStart[re] = 0; P.ovlCount[re] = 0; }
+      if (tid == 0) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); publish(re, 0, 0); }
       continue;
     }
     // key: matchCnt desc, similarity desc (== readSpan+seqSpan asc at equal matchCnt), readSpan desc, allele asc; payload: candidate
@@ -599,40 +610,145 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
     atomicMax(&sBest, myBest);
     uint32_t tot;
     t1k_block_scan_exclusive_n<NT / 64>(mine, warpSums, &tot);
+    // the overlap record of candidate ci (near-best against the list's best extended match count)
+    auto makeOvl = [&](uint32_t ci, int bestMatch) {
+      const T1kCand c = P.cand[ci];
+      const T1kExt x = P.ext[ci];
+      T1kOvl o;
+      o.allele = c.allele & 0x7FFFFFFFu;
+      o.seqStart = x.seqStart; o.seqEnd = x.seqEnd; o.readStart = x.readStart; o.readEnd = x.readEnd;
+      o.matchCnt = x.matchCnt; o.leftClip = x.leftClip; o.rightClip = x.rightClip; o.re = re;
+      o.flags = ((int)x.matchCnt >= bestMatch - 10 ? 1u : 0u) | ((c.allele >> 31) ? 0u : 2u);  // SeqSet.hpp:2200
+      // without --relaxIntronAlign the relaxed count is the match count of a near-best overlap and 0 otherwise (SeqSet.hpp:2247-2250, 2282):
+      // known here, whether or not the full alignments run; with it the alignment kernels fill it in
+      o.relaxed = (!P.relax && (o.flags & 1)) ? x.matchCnt : (uint16_t)0;
+      return o;
+    };
+    auto storePacked = [&](uint64_t at, const T1kOvl &o) {
+      T1kOvlP p;
+      if (!t1k_ovl_pack(o, p)) atomicOr(&P.counters[2], 1024ull);
+      P.store[at] = p;
+    };
+    uint32_t keep = tot;  // records of the list that are written
+    const bool cutList = PK && tot > 1000;
+    if (cutList) {
+      // More than 1000 emitted: order them by (extended match count desc, span sum incl. clips asc, read span desc, allele asc) and cut at
+      // the first one whose similarity lies more than 0.1 below the first one's.  The select keys are dead: the emit marks go into a bitmap
+      // by candidate index (in sCnt, which the counting pass takes over afterwards), and the new keys are built in candidate order -- the
+      // allele order k_collect left -- so that one stable class pass orders them, and compacted into the key array.
+      __syncthreads();  // (sBest is complete)
+      const int bestMatch = sBest;
+      uint32_t *emitBits = (uint32_t *)sCnt;  // n <= sortCap = 2^15 candidates: 4 KB of the 1024-thread shape's 8, 256 bytes of the 256-thread shape's 2 KB
+      for (uint32_t q = tid; q < (n + 31) / 32; q += NT) emitBits[q] = 0;
+      __syncthreads();
+      for (uint32_t i = tid; i < live; i += NT)
+        if (key[i] >> 63) { const uint32_t ix = idxOf(key[i]); atomicOr(&emitBits[ix >> 5], 1u << (ix & 31)); }
+      __syncthreads();
+      const KeyW TW = truncWidths<XL>((int)P.reads.len[re]);
+      uint32_t done = 0;
+      for (uint32_t i0 = 0; i0 < n; i0 += NT) {
+        const uint32_t i = i0 + tid;
+        const bool flag = i < n && ((emitBits[i >> 5] >> (i & 31)) & 1u);
+        uint64_t kk = 0;
+        if (flag) {
+          const T1kExt x = P.ext[c0 + i];
+          const int rspan = x.readEnd - x.readStart;
+          const int d = rspan + 1 + x.seqEnd - x.seqStart + 1 + 2 * x.leftClip + 2 * x.rightClip;  // similarity desc == d asc at equal matchCnt
+          if (!packSortKey(TW, (int)x.matchCnt, d, rspan, P.cand[c0 + i].allele & 0x7FFFFFFFu, i, P.alleleBits, iBits, &kk)) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); kk = i; }
+          if ((int)x.matchCnt >= bestMatch - 10) ++nbLocal;  // (the near-best statistic counts the emitted overlaps, before the cut)
+        }
+        uint32_t t2;
+        const uint32_t off = t1k_block_scan_exclusive_n<NT / 64>(flag ? 1u : 0u, warpSums, &t2);
+        if (flag) key[done + off] = kk;
+        done += t2;
+      }
+      uint32_t np2t = 8;
+      while (np2t < tot) np2t <<= 1;
+      for (uint32_t i = tot + tid; i < np2t; i += NT) key[i] = ~0ull;
+      __syncthreads();
+      // lists with more than 256 classes and the ones in HBM scratch: the bitonic network on the whole key (the index is the candidate's)
+      if (key != sKey || !ldsClassRanks<NT>(key, tot, P.alleleBits + iBits, sCs)) bitonicSort(key, np2t);
+      else ldsCountingPass<NT>(key, tot, sCnt, warpSums, [&](uint64_t kk) { return csRankOf(sCs, (uint32_t)(kk >> (P.alleleBits + iBits))); });
+      if (tid == 0) { sTie = 0; sLatch = (int)tot; }
+      __syncthreads();
+      for (uint32_t i = 1 + tid; i < tot; i += NT)
+        if ((key[i] >> iBits) == (key[i - 1] >> iBits)) sTie = 1;
+      __syncthreads();
+      if (sTie && tid == 0) {
+        // equal class and allele (rare): _overlap::operator<'s remaining fields on the extended coordinates; what ties there too keeps the
+        // order the selection gave it -- its class on the seed coordinates, candBeforeFull, candidate index
+        auto before = [&](uint32_t ia, uint32_t ib) {
+          const T1kExt xa = P.ext[c0 + ia], xb = P.ext[c0 + ib];
+          if (xa.readStart != xb.readStart) return xa.readStart < xb.readStart;
+          if (xa.readEnd != xb.readEnd) return xa.readEnd < xb.readEnd;
+          if (xa.seqStart != xb.seqStart) return xa.seqStart < xb.seqStart;
+          if (xa.seqEnd != xb.seqEnd) return xa.seqEnd < xb.seqEnd;
+          const T1kCand a = P.cand[c0 + ia], b = P.cand[c0 + ib];
+          const int ma = (int)(a.match >> 16), mb = (int)(b.match >> 16);
+          if (ma != mb) return ma > mb;
+          const int ra = (int)(a.readSE >> 16) - (int)(a.readSE & 0xFFFF), rb = (int)(b.readSE >> 16) - (int)(b.readSE & 0xFFFF);
+          const int da = ra + 1 + a.seqEnd - a.seqStart + 1, db = rb + 1 + b.seqEnd - b.seqStart + 1;
+          if (da != db) return da < db;
+          if (ra != rb) return ra > rb;
+          if (candBeforeFull(a, b)) return true;
+          if (candBeforeFull(b, a)) return false;
+          return ia < ib;
+        };
+        for (uint32_t i = 1; i < tot; ++i) {
+          if ((key[i] >> iBits) != (key[i - 1] >> iBits)) continue;
+          uint32_t j = i;
+          while (j > 0 && (key[j - 1] >> iBits) == (key[j] >> iBits) && before((uint32_t)(key[j] & iMask), (uint32_t)(key[j - 1] & iMask))) {
+            uint64_t t = key[j]; key[j] = key[j - 1]; key[j - 1] = t;
+            --j;
+          }
+        }
+      }
+      __syncthreads();
+      {
+        // first j >= 1 whose similarity falls more than 0.1 below the best one (SeqSet.hpp:2294-2297): match count over span sum, both
+        // fields of the key -- the integers ovlSimilarity divides
+        const int tmMax = (1 << TW.MB) - 1, tdMax = (1 << TW.DB) - 1, dShift = TW.RB + P.alleleBits + iBits;
+        auto simOf = [&](uint64_t kk) { return (double)(tmMax - (int)((kk >> (dShift + TW.DB)) & (uint64_t)tmMax)) / (double)(int)((kk >> dShift) & (uint64_t)tdMax); };
+        const double s0 = simOf(key[0]);
+        uint32_t first = tot;
+        for (uint32_t j = 1 + tid; j < tot; j += NT)
+          if (simOf(key[j]) < s0 - 0.1) { first = j; break; }
+        if (first < tot) atomicMin(&sLatch, (int)first);
+      }
+      __syncthreads();
+      keep = (uint32_t)sLatch;
+    }
     if (tid == 0) {
-      unsigned long long b = atomicAdd(&P.counters[1], (unsigned long long)tot);
-      if (b + tot > P.ovlCap) { atomicOr(&P.counters[2], (unsigned long long)ERR_OVLCAP); sBase = 0xFFFFFFFFu; P.ovlStart[re] = 0; P.ovlCount[re] = 0; }
-      else { sBase = (uint32_t)b; P.ovlStart[re] = (uint32_t)b; P.ovlCount[re] = tot; }
+      unsigned long long b = atomicAdd(&P.counters[1], (unsigned long long)keep);
+      emitTotal += tot;
+      if (b + keep > P.ovlCap) { atomicOr(&P.counters[2], (unsigned long long)ERR_OVLCAP); sBase = 0xFFFFFFFFu; publish(re, 0, 0); }
+      else { sBase = (uint32_t)b; publish(re, (uint32_t)b, keep); }
     }
     __syncthreads();
     const int bestMatch = sBest;
     if (sBase != 0xFFFFFFFFu) {
-      for (uint32_t i0 = 0; i0 < live; i0 += NT) {
-        uint32_t i = i0 + tid;
-        uint32_t flag = (i < live && (key[i] >> 63)) ? 1u : 0u;
-        uint32_t t2;
-        uint32_t off = t1k_block_scan_exclusive_n<NT / 64>(flag, warpSums, &t2);
-        if (flag) {
-          uint32_t ci = c0 + idxOf(key[i]);
-          const T1kCand c = P.cand[ci];
-          const T1kExt x = P.ext[ci];
-          T1kOvl o;
-          o.allele = c.allele & 0x7FFFFFFFu;
-          o.seqStart = x.seqStart; o.seqEnd = x.seqEnd; o.readStart = x.readStart; o.readEnd = x.readEnd;
-          o.matchCnt = x.matchCnt; o.leftClip = x.leftClip; o.rightClip = x.rightClip; o.re = re;
-          o.flags = ((int)x.matchCnt >= bestMatch - 10 ? 1u : 0u) | ((c.allele >> 31) ? 0u : 2u);  // SeqSet.hpp:2200
-          // without --relaxIntronAlign the relaxed count is the match count of a near-best overlap and 0 otherwise (SeqSet.hpp:2247-2250, 2282):
-          // known here, whether or not the full alignments run; with it the alignment kernels fill it in
-          o.relaxed = (!P.relax && (o.flags & 1)) ? x.matchCnt : (uint16_t)0;
-          if (o.flags & 1) ++nbLocal;
-          P.ovl[(uint64_t)sBase + written + off] = o;
+      if (cutList) {
+        for (uint32_t i = tid; i < keep; i += NT) storePacked((uint64_t)sBase + i, makeOvl(c0 + (uint32_t)(key[i] & iMask), bestMatch));
+      } else {
+        for (uint32_t i0 = 0; i0 < live; i0 += NT) {
+          uint32_t i = i0 + tid;
+          uint32_t flag = (i < live && (key[i] >> 63)) ? 1u : 0u;
+          uint32_t t2;
+          uint32_t off = t1k_block_scan_exclusive_n<NT / 64>(flag, warpSums, &t2);
+          if (flag) {
+            const T1kOvl o = makeOvl(c0 + idxOf(key[i]), bestMatch);
+            if (o.flags & 1) ++nbLocal;
+            if (PK) storePacked((uint64_t)sBase + written + off, o);
+            else P.ovl[(uint64_t)sBase + written + off] = o;
+          }
+          written += t2;
         }
-        written += t2;
       }
     }
     nbTotal += nbLocal;
     __syncthreads();
   }
+  if (PK && tid == 0 && emitTotal) atomicAdd(&P.counters[21], emitTotal);
   t1k_stat_add(P.counters, T1K_STAT_NEARBEST, nbTotal);
 }
 
@@ -1168,16 +1284,16 @@ void t1k_launch_extend_retry_dev(t1k_ctx *ctx, const ExtendArgs &a, const uint32
   const unsigned long long *nDev = (const unsigned long long *)ctx->bCounters.p + T1K_TOTAL_BASE + arena;
   hipLaunchKernelGGL(k_extend_retry, dim3((unsigned)std::max<uint64_t>(1, (est + WG - 1) / WG)), dim3(WG), 0, ctx->stream, a, list, 0u, nDev);
 }
-void t1k_launch_select(t1k_ctx *ctx, const SelectArgs &a, int nWg) {
-  if (a.xl) {  // a window with reads beyond T1K_MAX_READ_LEN: wider key fields
-    hipFuncSetAttribute((const void *)k_select<SELECT_LARGE, 1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SELECT_LARGE * 8);
-    hipLaunchKernelGGL((k_select<SELECT_SMALL, 256, true>), dim3(nWg), dim3(256), SELECT_SMALL * 8, ctx->stream, a);
-    hipLaunchKernelGGL((k_select<SELECT_LARGE, 1024, true>), dim3(std::min(nWg, 512)), dim3(1024), SELECT_LARGE * 8, ctx->stream, a);
-    return;
-  }
-  hipFuncSetAttribute((const void *)k_select<SELECT_LARGE, 1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SELECT_LARGE * 8);
-  hipLaunchKernelGGL((k_select<SELECT_SMALL, 256, false>), dim3(nWg), dim3(256), SELECT_SMALL * 8, ctx->stream, a);
-  hipLaunchKernelGGL((k_select<SELECT_LARGE, 1024, false>), dim3(std::min(nWg, 512)), dim3(1024), SELECT_LARGE * 8, ctx->stream, a);
+template <bool XL, bool PK>
+static void launchSelect(t1k_ctx *ctx, const SelectArgs &a, int nWg) {
+  hipFuncSetAttribute((const void *)k_select<SELECT_LARGE, 1024, XL, PK>, hipFuncAttributeMaxDynamicSharedMemorySize, SELECT_LARGE * 8);
+  hipLaunchKernelGGL((k_select<SELECT_SMALL, 256, XL, PK>), dim3(nWg), dim3(256), SELECT_SMALL * 8, ctx->stream, a);
+  hipLaunchKernelGGL((k_select<SELECT_LARGE, 1024, XL, PK>), dim3(std::min(nWg, 512)), dim3(1024), SELECT_LARGE * 8, ctx->stream, a);
+}
+void t1k_launch_select(t1k_ctx *ctx, const SelectArgs &a, int nWg, bool packed) {
+  // xl: a window with reads beyond T1K_MAX_READ_LEN (wider key fields); packed: the lists are cut and stored in the 16-byte form here
+  if (a.xl) { if (packed) launchSelect<true, true>(ctx, a, nWg); else launchSelect<true, false>(ctx, a, nWg); }
+  else { if (packed) launchSelect<false, true>(ctx, a, nWg); else launchSelect<false, false>(ctx, a, nWg); }
 }
 void t1k_launch_fullalign(t1k_ctx *ctx, const FullArgs &a) {
   if (!a.nOvl) return;

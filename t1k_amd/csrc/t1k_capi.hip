@@ -888,6 +888,19 @@ int t1k_assign_range(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   }
 }
 
+// the statistics of a finished range from its last counter fetch; `emitted`: the overlaps the selection emitted (before lists are cut)
+static int finishRangeStats(t1k_ctx *ctx, uint32_t n, const unsigned long long *hc, unsigned long long emitted, double t0) {
+  t1k_stats &st = ctx->stats;
+  st.read_ends = n; st.lookups = hc[3]; st.postings = hc[4]; st.hits = hc[5]; st.groups = hc[6]; st.candidates = hc[0]; st.extended = emitted;
+  st.dp_calls = hc[7] + hc[14]; st.near_best = hc[10]; st.dp_cells = hc[24];
+  float ms[4] = {0, 0, 0, 0}, msSeed = 0;  // kernel durations from HIP events on the launch stream
+  for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ms[i], ctx->ev[i], ctx->ev[i + 1]);
+  (void)hipEventElapsedTime(&msSeed, ctx->ev[0], ctx->ev[8]);
+  st.ms_seed = msSeed; st.ms_chain = ms[0] - msSeed; st.ms_extend = ms[1]; st.ms_select = ms[2]; st.ms_fullalign = ms[3]; st.ms_total = nowMs() - t0;
+  st.batches = 1;
+  return T1K_OK;
+}
+
 static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   const uint32_t n = count;
   ctx->covCommitted = false;
@@ -941,8 +954,12 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
     }
     ctx->storeBase = (T1kOvlP *)chunks[ctx->storeChunk[sl]].p + ctx->storeUsed[sl];
   }
-  if ((rc = t1k_ensure(ctx, ctx->bOvlWork, (size_t)ctx->wOvl * sizeof(T1kOvl)))) return rc;
-  ctx->ovlBase = (T1kOvl *)ctx->bOvlWork.p;
+  // Without --relaxIntronAlign and with the coverage deferred nothing reads the records between the selection and the cut: k_select
+  // finishes the lists itself and writes them to the store in the packed form (no working records, no k_truncate, no k_pack_overlaps)
+  const bool packedSelect = !ctx->prm.relax_intron_align && ctx->covMode == 1;
+  if (!packedSelect && (rc = t1k_ensure(ctx, ctx->bOvlWork, (size_t)ctx->wOvl * sizeof(T1kOvl)))) return rc;
+  ctx->ovlBase = packedSelect ? nullptr : (T1kOvl *)ctx->bOvlWork.p;
+  ctx->ovlPacked = packedSelect;
   // (n + 1 entries each: the two counts are cleared one entry past the range.  Since round 1 the blocks were asked for n entries and cleared for n + 1 --
   // inside the block's slack of an eighth + 256 bytes except when a LATER range of the context had exactly that many more read-ends than its first:
   // 29 read-ends first, 96 later -> 386 bytes held, 388 cleared, "hipMemsetAsync: invalid argument".  Found by the fuzz file under 96-read-end ranges, round 6)
@@ -1017,8 +1034,22 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   s.sortScratch = (uint64_t *)ctx->bSortScratch.p; s.sortCap = sortCap; s.counters = a.counters;
   s.alleleBits = 1; s.relax = relaxFlag; s.xl = ctx->batchMaxLen > T1K_MAX_READ_LEN ? 1 : 0;
   while ((1u << s.alleleBits) < ctx->ref.nAlleles) ++s.alleleBits;
-  t1k_launch_select(ctx, s, nWg);
+  s.store = ctx->storeBase; s.listPtr = rd.listPtr + first; s.listCount = rd.listCount + first;
+  t1k_launch_select(ctx, s, nWg, packedSelect);
   T1K_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+  if (packedSelect) {
+    // the lists are final, in the store and in the read set's table: one fetch ends the range (error word, kept and emitted records,
+    // the extension's arena counts, the statistics)
+    T1K_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((rc = fetchCounters(ctx, hc))) return rc;
+    if (hc[2]) return capacityError(ctx, hc[2]);
+    t1k_arena_estimate_set(ctx, T1K_AR_EXTJOBS, t1k_arena_counts(ctx, T1K_AR_EXTJOBS, e.jobSegCap).total, n);
+    t1k_arena_estimate_set(ctx, T1K_AR_EXTRETRY, t1k_arena_counts(ctx, T1K_AR_EXTRETRY, e.retrySegCap).total, n);
+    ctx->nOvl = hc[1];  // the records kept: the store advances by them
+    ctx->storeUsed[ctx->storeSlot] += ctx->nOvl;
+    if (getenv("T1K_DEBUG_PHASES")) fprintf(stderr, "[t1k] packed selection: cand %llu emitted %llu kept %llu\n", hc[0], hc[21], hc[1]);
+    return finishRangeStats(ctx, n, hc, hc[21], t0);
+  }
   if ((rc = fetchCounters(ctx, hc))) return rc;
   double t3 = nowMs();
   if (hc[2]) return capacityError(ctx, hc[2]);
@@ -1062,16 +1093,8 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
     fprintf(stderr, "[t1k] gap walk classes: exact without a DP %llu, pruned by the per-gap bound %llu, memo / DP %llu\n", hc[40], hc[41], hc[42]);
 #endif
   }
-  t1k_stats &st = ctx->stats;
-  st.read_ends = n; st.lookups = hc[3]; st.postings = hc[4]; st.hits = hc[5]; st.groups = hc[6]; st.candidates = hc[0]; st.extended = hc[1];
-  st.dp_calls = hc[7] + hc[14]; st.near_best = hc[10]; st.dp_cells = hc[24];
-  float ms[4] = {0, 0, 0, 0}, msSeed = 0;  // kernel durations from HIP events on the launch stream
-  for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ms[i], ctx->ev[i], ctx->ev[i + 1]);
-  (void)hipEventElapsedTime(&msSeed, ctx->ev[0], ctx->ev[8]);
-  (void)t1; (void)t2; (void)t3;
-  st.ms_seed = msSeed; st.ms_chain = ms[0] - msSeed; st.ms_extend = ms[1]; st.ms_select = ms[2]; st.ms_fullalign = ms[3]; st.ms_total = t4 - t0;
-  st.batches = 1;
-  return T1K_OK;
+  (void)t1; (void)t2; (void)t3; (void)t4;
+  return finishRangeStats(ctx, n, hc, hc[1], t0);
 }
 
 int t1k_overlaps_download(t1k_ctx *ctx, uint32_t *counts, t1k_overlap *out, uint64_t cap, uint64_t *total) {
@@ -1090,7 +1113,11 @@ int t1k_overlaps_download(t1k_ctx *ctx, uint32_t *counts, t1k_overlap *out, uint
   if (!out) return T1K_OK;
   if (cap < tot) return t1k_fail(ctx, T1K_ERR_ARG, "overlap buffer too small");
   std::vector<T1kOvl> h(ctx->nOvl);
-  if (ctx->nOvl) T1K_HIP(ctx, hipMemcpy(h.data(), ctx->ovlBase, ctx->nOvl * sizeof(T1kOvl), hipMemcpyDeviceToHost));
+  if (ctx->ovlPacked) {  // the last range went to the store packed (every field reported here is in that form)
+    std::vector<T1kOvlP> hp(ctx->nOvl);
+    if (ctx->nOvl) T1K_HIP(ctx, hipMemcpy(hp.data(), ctx->storeBase, ctx->nOvl * sizeof(T1kOvlP), hipMemcpyDeviceToHost));
+    for (uint64_t g = 0; g < ctx->nOvl; ++g) h[g] = t1k_ovl_unpack(hp[g]);
+  } else if (ctx->nOvl) T1K_HIP(ctx, hipMemcpy(h.data(), ctx->ovlBase, ctx->nOvl * sizeof(T1kOvl), hipMemcpyDeviceToHost));
   uint64_t w = 0;
   for (uint32_t i = 0; i < n; ++i) {
     for (uint32_t j = 0; j < cnt[i]; ++j) {

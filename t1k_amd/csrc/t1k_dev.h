@@ -957,6 +957,7 @@ struct t1k_ctx {
   uint64_t storeUsed[2] = {0, 0};  // records used in it
   T1kOvl *ovlBase = nullptr;       // where the last t1k_assign_range wrote its lists (32-byte working records: t1k_overlaps_download)
   T1kDevBuf bOvlWork;              // the working records of one range (the store keeps the packed form)
+  bool ovlPacked = false;          // the last range had no working records: k_select wrote its lists to the store (storeBase) packed
   T1kDevBuf bOvlUpload;            // packed lists handed in by the host (t1k_overlaps_upload: tests of the pairing stage)
   T1kOvlP *storeBase = nullptr;    // where the running range's packed lists go
   // working capacities of the batch arenas (t1k_assign_range grows them on demand up to the limits in prm) and the demand the last

@@ -55,6 +55,11 @@ struct SelectArgs {
   const uint32_t *candStart, *candCount;
   T1kOvl *ovl; uint64_t ovlCap;
   uint32_t *ovlStart, *ovlCount;
+  // the packed form (k_select<.., PK = true>: deferred coverage without --relaxIntronAlign) finishes the lists itself: records cut and
+  // packed into the store, the read set's list table written for the range (entries of this range's first read-end; reads.skip honoured)
+  T1kOvlP *store;
+  unsigned long long *listPtr;
+  uint32_t *listCount;
   uint64_t *sortScratch;   // [wg][sortCap] packed keys (per-workgroup stride: sortCap * 6 words, shared with k_truncate)
   uint32_t sortCap;
   int alleleBits;          // bits of an allele index
@@ -185,7 +190,7 @@ int t1k_chain_used_u32(int maxK);
 int t1k_launch_seed(t1k_ctx *ctx, const ChainArgs &a, bool longReads, bool xlong);  // t1k_seed.hip: k_seed_groups (+ k_seed_long when xlong)
 int t1k_run_chain(t1k_ctx *ctx, const ChainArgs &a, int nWg, int bigBlocks, bool longReads, unsigned long long *hc);
 void t1k_launch_extend(t1k_ctx *ctx, const ExtendArgs &a);
-void t1k_launch_select(t1k_ctx *ctx, const SelectArgs &a, int nWg);
+void t1k_launch_select(t1k_ctx *ctx, const SelectArgs &a, int nWg, bool packed);
 void t1k_launch_fullalign(t1k_ctx *ctx, const FullArgs &a);
 void t1k_launch_fullalign_slow(t1k_ctx *ctx, const SlowArgs &a, int nBlocks);
 void t1k_launch_align_flags(t1k_ctx *ctx, const SlowArgs &a, uint32_t *flags);
