@@ -128,6 +128,10 @@ int t1k_overlaps_upload(t1k_ctx *ctx, const uint32_t *counts, const t1k_overlap 
  * the per-workgroup tables in device memory), out[1] = overlaps of both mates the first launch takes (more: the second launch),
  * out[2] = row entries per tile of the rowset form's rank sort, out[3] = list records per round of the streamed passes. */
 void t1k_pair_limits(uint32_t out[4]);
+/* TEST-ONLY: the allele numbers (largest - smallest + 1) the two lists of a fragment may span to be joined through the in-LDS table
+ * indexed by allele offset when they hold more than out[0] of t1k_pair_limits together (shorter ones: the hash table); wider fragments
+ * take the device-memory tables.  T1K_PAIR_DIRECT=0 turns the route off. */
+uint32_t t1k_pair_direct_cap(void);
 
 /* One kept (fragment, allele) assignment: Genotyper::_readAssignment (Genotyper.hpp:44-56). 24 bytes. */
 typedef struct {

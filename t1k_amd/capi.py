@@ -199,6 +199,8 @@ def lib():
     L.t1k_overlaps_upload.argtypes = [vp, vp, vp]
     L.t1k_pair_limits.argtypes = [vp]
     L.t1k_pair_limits.restype = None
+    L.t1k_pair_direct_cap.argtypes = []
+    L.t1k_pair_direct_cap.restype = C.c_uint32
     L.t1k_rowset_create.argtypes = [vp, C.c_uint64, vp, C.POINTER(vp)]
     L.t1k_rowset_destroy.argtypes = [vp]
     L.t1k_rowset_destroy.restype = None
@@ -699,6 +701,11 @@ def pair_limits():
     out = np.zeros(4, dtype=np.uint32)
     lib().t1k_pair_limits(_ptr(out))
     return tuple(int(x) for x in out)
+
+
+def pair_direct_cap():
+    """allele numbers a fragment's lists may span to take the pairing kernel's LDS table indexed by allele offset"""
+    return int(lib().t1k_pair_direct_cap())
 
 
 class Rowset:

@@ -7,9 +7,12 @@
 // Two output forms: t1k_pair_batch keeps the rows of one call in the context (fragment order, list order inside a row);
 // t1k_pair_into appends them to a t1k_rowset -- all rows of a job resident in HBM, each row ordered by allele index with a
 // 128-bit pattern hash per fragment -- which t1k_rowset_coalesce (t1k_coalesce.hip) turns into read groups.
-// Mates are joined through a per-workgroup direct-address table (allele -> index in the mate's list, stamped with a
-// fragment epoch so it never needs clearing).  If an allele occurs twice in a list (several diagonal runs on one
-// allele -- rare) lane 0 replays the reference's sequential algorithm instead.
+// Mates are joined through one of three tables (JoinTab): short lists (both together at most LJ_CAP records: most fragments) through a hash
+// table in LDS; longer ones (a seventh of the fragments of a real sample, two thirds of its records) through an LDS table indexed by
+// allele - smallest allele of the fragment where the fragment's alleles span at most DIRECT_CAP numbers (the alleles of a gene are
+// neighbours); else through a per-workgroup table in HBM with an entry per allele of the reference (allele -> index in the mate's list,
+// stamped with a fragment epoch so it never needs clearing).  If an allele occurs twice in a list (several diagonal runs on one allele -- rare)
+// lane 0 replays the reference's sequential algorithm on the HBM tables instead.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -20,6 +23,14 @@
 #define PP(i) do { if (tid == 0) { const uint64_t tn_ = __builtin_amdgcn_s_memtime(); tp_[i] += tn_ - tl_; tl_ = tn_; } } while (0)
 #else
 #define PP(i) do { } while (0)
+#endif
+// -DT1K_PAIR_ROUTES: fragments and list records per join route and launch, counted in counters[40 .. 52) and summed per process (a
+// measurement build: thread 0 pays two atomics per fragment)
+#ifdef T1K_PAIR_ROUTES
+#define T1K_ROUTE_COUNT() do { if (tid == 0) { const int r_ = 2 * ((jt.direct() ? 2 : jt.lds() ? 0 : 1) + (P.only ? 3 : 0)); \
+  atomicAdd(&P.counters[40 + r_], 1ull); atomicAdd(&P.counters[41 + r_], (unsigned long long)(n1 + n2)); } } while (0)
+#else
+#define T1K_ROUTE_COUNT() do { } while (0)
 #endif
 #define SORT_TILE 2048
 // Join table of one fragment in LDS: allele -> (index in list 1 + 1) | membership bit 15 | (index in list 2 + 1) << 16.  Open addressing,
@@ -53,6 +64,64 @@ __device__ __forceinline__ int ljFind(const uint32_t *hKey, uint32_t allele) {  
     h = (h + 1) & (LJ_SLOTS - 1);
   }
 }
+
+// The same 32 KB seen as one table indexed by allele - (smallest allele of the fragment): DIRECT_CAP words of the value format above, no keys.
+// The alleles of a gene are neighbours in the reference, so a fragment's alleles span a few thousand numbers however long its lists are.
+constexpr uint32_t directCapacity(uint32_t slots) { return 2 * slots; }
+// It serves the fragments whose lists exceed the hash table's capacity (for every fragment whose range fits it measured no faster, DESIGN
+// 9.0 item 14).  T1K_PAIR_DIRECT=0, read once per process, turns it off (A/B on one build, parity aid).
+static int pairDirectOn() {
+  static const int on = [] { const char *e = getenv("T1K_PAIR_DIRECT"); return e && !strcmp(e, "0") ? 0 : 1; }();
+  return on;
+}
+
+// The join table of one fragment, whichever of the three it is: the LDS hash table, the LDS table indexed by allele offset, or the workgroup's
+// stamped tables in HBM.  Set up once per fragment; a repeated allele (toHbm) moves the fragment to the HBM tables.
+enum { JT_HASH = 0, JT_DIRECT = 1, JT_HBM = 2, JT_HBM_DUP = 3 };
+template <int LJ_SLOTS>
+struct JoinTab {
+  uint32_t *mem;            // LDS: hKey = mem[0 .. LJ_SLOTS), hVal = mem[LJ_SLOTS .. 2 * LJ_SLOTS); or dir = mem[0 .. range)
+  uint64_t *tab2, *tabSlot; // HBM: [nAlleles] of (epoch << 32 | value)
+  uint32_t ep;              // this fragment's epoch
+  uint32_t lo, range;       // direct: smallest allele of both lists, alleles spanned
+  int kind;                 // JT_HASH, JT_DIRECT (both in LDS), JT_HBM, JT_HBM_DUP (a list repeats an allele: the replay's tables)
+  __device__ __forceinline__ bool lds() const { return kind <= JT_DIRECT; }
+  __device__ __forceinline__ bool direct() const { return kind == JT_DIRECT; }
+  __device__ __forceinline__ uint32_t words() const { return direct() ? range : 2u * LJ_SLOTS; }  // what a fragment clears before its inserts
+  __device__ __forceinline__ void toHbm(bool dup) { kind = dup ? JT_HBM_DUP : JT_HBM; }
+  __device__ __forceinline__ bool stamped(uint64_t e) const { return (uint32_t)(e >> 32) == ep; }
+  // LDS word of an allele's value, -1 if the table does not hold it
+  __device__ __forceinline__ int word(uint32_t allele) const {
+    if (direct()) { const uint32_t d = allele - lo; return d < range ? (int)d : -1; }
+    const int s = ljFind<LJ_SLOTS>(mem, allele);
+    return s >= 0 ? LJ_SLOTS + s : -1;
+  }
+  // the two inserts: true if the list already had a record on this allele
+  __device__ __forceinline__ bool insert1(uint32_t allele, uint32_t i) {
+    if (!lds()) return stamped(atomicExch((unsigned long long *)&tabSlot[allele], (unsigned long long)((uint64_t)ep << 32 | i)));
+    const uint32_t w = direct() ? allele - lo : LJ_SLOTS + ljInsert<LJ_SLOTS>(mem, allele);
+    return (atomicOr(&mem[w], i + 1) & 0x7FFFu) != 0;
+  }
+  __device__ __forceinline__ bool insert2(uint32_t allele, uint32_t j) {
+    if (!lds()) return stamped(atomicExch((unsigned long long *)&tab2[allele], (unsigned long long)((uint64_t)ep << 32 | j)));
+    const uint32_t w = direct() ? allele - lo : LJ_SLOTS + ljInsert<LJ_SLOTS>(mem, allele);
+    return (atomicOr(&mem[w], (j + 1) << 16) >> 16) != 0;
+  }
+  // index in list 2 of the record on this allele, -1 if none; w: the allele's LDS word, for mark()
+  __device__ __forceinline__ int mate(uint32_t allele, int &w) const {
+    if (lds()) { w = word(allele); return w >= 0 ? (int)(mem[w] >> 16) - 1 : -1; }
+    const uint64_t e = tab2[allele];
+    return stamped(e) ? (int)(e & 0x3FFFFFFFu) : -1;
+  }
+  __device__ __forceinline__ int mate(uint32_t allele) const { int w = -1; return mate(allele, w); }
+  // "this allele has a fragment" (seqIdxToOverlapIdx membership); w as mate() gave it
+  __device__ __forceinline__ void mark(int w, uint32_t allele) { if (lds()) atomicOr(&mem[w], 0x8000u); else tab2[allele] |= 0x80000000ull; }
+  __device__ __forceinline__ bool member(uint32_t allele) const {
+    if (lds()) { const int w = word(allele); return w >= 0 && (mem[w] & 0x8000u) != 0; }
+    if (kind != JT_HBM_DUP) { const uint64_t e = tab2[allele]; return stamped(e) && (e & 0x80000000ull); }
+    const uint64_t e = tabSlot[allele]; return stamped(e) && (e & 0x40000000ull);  // the replay's slot table
+  }
+};
 
 // contribution of the allele at sorted position r to a fragment's pattern hash (summed over the row: order of evaluation is free)
 __device__ __forceinline__ unsigned long long t1k_pattern_mix(uint32_t allele, uint32_t r, unsigned long long k) {
@@ -103,6 +172,7 @@ struct PairArgs {
   const uint32_t *only;
   Frag *bigFrags; uint32_t *bigKeep; uint64_t bigCap;
   uint32_t *overflowList;          // first pass: fragments with more than fragCap overlaps are listed here instead of failing
+  int direct;                      // pairDirectOn()
   const uint8_t *whitelist;        // [nAlleles] or NULL: alleles outside it are left out of the rows (Genotyper.hpp:822-823)
   int listForm;                    // T1K_PAIR_LIST=1: the joined fragments are materialised as in round 3 (A/B and parity aid)
   int rawKept;                     // rows = the fragment assignment list itself (what ReadAssignmentToFragmentAssignment returns), without
@@ -215,11 +285,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
   constexpr int NWAVE = WG / 64;
   constexpr int PU = T1K_PAIR_UNROLL;  // records of a list a lane requests before it looks at the first (the streamed passes)
   constexpr uint32_t LJ_CAP = ljCapacity(LJ_SLOTS);
+  constexpr uint32_t DIRECT_CAP = directCapacity(LJ_SLOTS);
+  static_assert(DIRECT_CAP <= 32766, "a list of the direct route numbers its records in 15 bits");
   __shared__ uint32_t warpSums[NWAVE];
   __shared__ int sDup, sFail, sBestM, sBestIdx, sAnySep, sNotOne;
   __shared__ double sBestSim;
   __shared__ uint32_t sN, sBase;
-  __shared__ uint32_t hKey[LJ_SLOTS], hVal[LJ_SLOTS];
+  __shared__ uint32_t sLo, sHi;
+  __shared__ uint32_t ljMem[2 * LJ_SLOTS];
   const int tid = threadIdx.x;
   const uint32_t A = P.ref.nAlleles;
   uint64_t *tab2 = P.tab2 + (uint64_t)blockIdx.x * A;
@@ -237,16 +310,17 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
   // "overlap records read" and "row entries" statistics -- 260 k atomics per launch of 65 536 fragments into two cache lines, on a part whose
   // returning atomics on one word saturate near 88 M/s ("striped allocation"): at 1.4 ms a launch the kernel sat at half of that rate on
   // each word.  The hand-out now takes T1K_PAIR_HANDOUT fragments at a time (their cost is uneven: no more than a few), the two statistics are
-  // summed per workgroup (thread 0's registers) and flushed once.
+  // summed per workgroup (by thread 0) and flushed once.
   __shared__ uint32_t sItem;
   uint32_t hoNext = 0, hoLeft = 0;                         // thread 0: the fragments it holds from its last hand-out
-  unsigned long long statOvl = 0, statRows = 0;            // thread 0
+  __shared__ unsigned long long sStatOvl, sStatRows;       // thread 0's sums for the whole launch (in LDS: the registers go to the sweeps)
+  if (tid == 0) { sStatOvl = 0; sStatRows = 0; }
   unsigned long long rowNext = 0; uint32_t rowLeft = 0;    // thread 0: what is left of its last reservation in the rowset's chunk
   for (;;) {
     if (tid == 0) {
       if (hoLeft == 0) { hoNext = (uint32_t)atomicAdd(&P.counters[P.only ? 26 : 25], (unsigned long long)T1K_PAIR_HANDOUT); hoLeft = T1K_PAIR_HANDOUT; }
       sItem = hoNext++; --hoLeft;
-      sDup = 0; sFail = 0; sBestM = -1; sBestIdx = 0x7FFFFFFF; sAnySep = 0; sNotOne = 0; sN = 0;
+      sDup = 0; sFail = 0; sBestM = -1; sBestIdx = 0x7FFFFFFF; sAnySep = 0; sNotOne = 0; sN = 0; sLo = 0xFFFFFFFFu; sHi = 0;
     }
     __syncthreads();
     const uint32_t it = sItem;
@@ -289,14 +363,42 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
       __syncthreads();
       continue;
     }
-    if (tid == 0) statOvl += n1 + n2;  // statistics: overlap records read (by the launch that pairs the fragment)
+    if (tid == 0) sStatOvl += n1 + n2;  // statistics: overlap records read (by the launch that pairs the fragment)
     // ---- duplicate detection + join table --------------------------------------------------------------------------
-    bool lds = n1 + n2 <= LJ_CAP;
-    if (lds) {
-      for (uint32_t q = tid; q < LJ_SLOTS; q += WG) { hKey[q] = 0; hVal[q] = 0; }
+    JoinTab<LJ_SLOTS> jt{ljMem, tab2, tabSlot, (uint32_t)(epoch >> 32), 0u, 0u, n1 + n2 <= LJ_CAP ? JT_HASH : JT_HBM};
+    if (P.direct && !jt.lds()) {  // (lists beyond the hash table only)
+      // the allele range of both lists: one sweep over their allele words (four loads in flight, as the inserts below), reduced over the
+      // wavefront by shuffles and over the workgroup by one LDS atomic pair per wavefront
+      uint32_t lo = 0xFFFFFFFFu, hi = 0;
+      for (uint32_t i0 = tid; i0 < n1; i0 += 4 * WG) {
+        uint32_t al[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) al[r] = i0 + r * WG < n1 ? (uint32_t)(L1.p[i0 + r * WG].lo & 0xFFFFFFu) : 0u;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (i0 + r * WG < n1) { lo = min(lo, al[r]); hi = max(hi, al[r]); }
+      }
+      for (uint32_t j0 = tid; j0 < n2; j0 += 4 * WG) {
+        uint32_t al[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) al[r] = j0 + r * WG < n2 ? (uint32_t)(L2.p[j0 + r * WG].lo & 0xFFFFFFu) : 0u;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (j0 + r * WG < n2) { lo = min(lo, al[r]); hi = max(hi, al[r]); }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64)); hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64)); }
+      if ((tid & 63) == 0 && lo <= hi) { atomicMin(&sLo, lo); atomicMax(&sHi, hi); }
       __syncthreads();
-      // (this is the first touch of the two lists: four records' allele words are requested together before the dependent LDS inserts --
-      // one after the other, each insert's atomic kept the next record's load from being issued)
+      lo = sLo; hi = sHi;
+      // (a list longer than the range repeats an allele: it keeps the route it had, where its record numbers have room)
+      if (lo <= hi && hi - lo < DIRECT_CAP && n1 <= hi - lo + 1 && n2 <= hi - lo + 1) { jt.kind = JT_DIRECT; jt.lo = lo; jt.range = hi - lo + 1; }
+    }
+    if (jt.lds()) {
+      for (uint32_t q = tid, nq = jt.words(); q < nq; q += WG) ljMem[q] = 0;
+      __syncthreads();
+      // (this is the first touch of the two lists on the hash route: four records' allele words are requested together before the dependent
+      // LDS inserts -- one after the other, each insert's atomic kept the next record's load from being issued)
       for (uint32_t i0 = tid; i0 < n1; i0 += 4 * WG) {
         uint32_t al[4];
 #pragma unroll
@@ -304,7 +406,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const uint32_t i = i0 + r * WG;
-          if (i < n1) { const uint32_t old = atomicOr(&hVal[ljInsert<LJ_SLOTS>(hKey, al[r])], i + 1); if (old & 0x7FFFu) sDup = 1; }
+          if (i < n1 && jt.insert1(al[r], i)) sDup = 1;
         }
       }
       for (uint32_t j0 = tid; j0 < n2; j0 += 4 * WG) {
@@ -314,24 +416,22 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const uint32_t j = j0 + r * WG;
-          if (j < n2) { const uint32_t old = atomicOr(&hVal[ljInsert<LJ_SLOTS>(hKey, al[r])], (j + 1) << 16); if (old >> 16) sDup = 1; }
+          if (j < n2 && jt.insert2(al[r], j)) sDup = 1;
         }
       }
       __syncthreads();
-      if (sDup) lds = false;  // a repeated allele: the sequential replay below works on the HBM tables
+      if (sDup) jt.toHbm(true);  // a repeated allele: the sequential replay below works on the HBM tables
     }
-    if (!lds) {
-      for (uint32_t i = tid; i < n1; i += WG) {
-        unsigned long long old = atomicExch((unsigned long long *)&tabSlot[L1[i].allele], (unsigned long long)(epoch | i));
-        if ((old >> 32) == (epoch >> 32)) sDup = 1;
-      }
-      for (uint32_t j = tid; j < n2; j += WG) {
-        unsigned long long old = atomicExch((unsigned long long *)&tab2[L2[j].allele], (unsigned long long)(epoch | j));
-        if ((old >> 32) == (epoch >> 32)) sDup = 1;
-      }
+    T1K_ROUTE_COUNT();
+    if (!jt.lds()) {
+      for (uint32_t i = tid; i < n1; i += WG)
+        if (jt.insert1(L1[i].allele, i)) sDup = 1;
+      for (uint32_t j = tid; j < n2; j += WG)
+        if (jt.insert2(L2[j].allele, j)) sDup = 1;
       __syncthreads();
     }
     const bool dup = sDup != 0;
+    if (dup) jt.toHbm(true);
     int tbM = -1, tbI = 0x7FFFFFFF;  // best fragment seen by this lane while it built the list (paired fast path only)
     double tbS = 0;
     bool tracked = false;
@@ -359,11 +459,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
         for (int u = 0; u < PU; ++u) {
           const uint32_t i = i0 + u * WG;
           jv[u] = -1; slotv[u] = -1;
-          if (i < n1 && s1 != s2) {
-            const uint32_t al = (uint32_t)(pa[u].lo & 0xFFFFFFu);
-            if (lds) { slotv[u] = ljFind<LJ_SLOTS>(hKey, al); jv[u] = slotv[u] >= 0 ? (int)(hVal[slotv[u]] >> 16) - 1 : -1; }
-            else { const uint64_t e = tab2[al]; if ((e >> 32) == (epoch >> 32)) jv[u] = (int)(e & 0x3FFFFFFFu); }
-          }
+          if (i < n1 && s1 != s2) jv[u] = jt.mate((uint32_t)(pa[u].lo & 0xFFFFFFu), slotv[u]);
         }
 #pragma unroll
         for (int u = 0; u < PU; ++u) pb[u] = jv[u] >= 0 ? L2.p[jv[u]] : T1kOvlP{0ull, 0ull};
@@ -377,7 +473,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
           makeFrag(fr, &oa, (int)i, &ob, jv[u]);
           ++nPairs;
           if (fr.matchCnt > tbM || (fr.matchCnt == tbM && fr.sim > tbS)) { tbM = fr.matchCnt; tbS = fr.sim; tbI = (int)i; }  // (a lane's i ascend: its first maximum stays)
-          if (lds) atomicOr(&hVal[slotv[u]], 0x8000u); else tab2[oa.allele] |= 0x80000000ull;   // the mate's allele has a fragment (seqIdxToOverlapIdx membership)
+          jt.mark(slotv[u], oa.allele);   // the mate's allele has a fragment (seqIdxToOverlapIdx membership)
         }
       }
       nFrag = nPairs;  // (this lane's share: only "any at all" is asked below, through sBestM)
@@ -397,14 +493,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
           int j = -1;
           int slot = -1;
           if (i < n1 && s1 != s2) {
-            int jj = -1;
-            if (lds) {
-              slot = ljFind<LJ_SLOTS>(hKey, L1[i].allele);
-              jj = (int)(hVal[slot] >> 16) - 1;
-            } else {
-              uint64_t e = tab2[L1[i].allele];
-              if ((e >> 32) == (epoch >> 32)) jj = (int)(e & 0x7FFFFFFFu);
-            }
+            const int jj = jt.mate(L1[i].allele, slot);
             if (jj >= 0 && ((s1 == 1 && L1[i].seqStart < L2[jj].seqStart) || (s1 == -1 && L1[i].seqStart > L2[jj].seqStart))) j = jj;  // 2369-2380
           }
           uint32_t tot;
@@ -417,7 +506,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
             // this lane's best fragment so far (its fragments come in list order: the first maximal one stays)
             if (fr.matchCnt > tbM || (fr.matchCnt == tbM && fr.sim > tbS)) { tbM = fr.matchCnt; tbS = fr.sim; tbI = (int)(nFrag + off); }
             // the mate's allele has a fragment (seqIdxToOverlapIdx membership)
-            if (lds) atomicOr(&hVal[slot], 0x8000u); else tab2[L1[i].allele] |= 0x80000000ull;
+            jt.mark(slot, oa.allele);
           }
           nFrag += tot;
         }
@@ -535,8 +624,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
     if (stream) {
       if (bestM >= 0) {  // the best fragment again, from its two records (every lane computes the same)
         const T1kOvl oa = L1[sBestIdx];
-        int jj;
-        if (lds) jj = (int)(hVal[ljFind<LJ_SLOTS>(hKey, oa.allele)] >> 16) - 1; else jj = (int)(tab2[oa.allele] & 0x3FFFFFFFu);
+        const int jj = jt.mate(oa.allele);
         bestRelaxed = oa.relaxed + L2[jj].relaxed;
       }
     } else bestRelaxed = nFrag ? frags[sBestIdx].relaxed : 0;
@@ -555,11 +643,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
           for (int u = 0; u < PU; ++u) {
             const uint32_t i = i0 + u * WG + tid;
             jv[u] = -1;
-            if (i < n1 && s1 != s2) {
-              const uint32_t al = (uint32_t)(pa[u].lo & 0xFFFFFFu);
-              if (lds) { const int sl = ljFind<LJ_SLOTS>(hKey, al); jv[u] = sl >= 0 ? (int)((hVal[sl] >> 16) & 0xFFFFu) - 1 : -1; }
-              else { const uint64_t e = tab2[al]; if ((e >> 32) == (epoch >> 32)) jv[u] = (int)(e & 0x3FFFFFFFu); }
-            }
+            if (i < n1 && s1 != s2) jv[u] = jt.mate((uint32_t)(pa[u].lo & 0xFFFFFFu));
           }
 #pragma unroll
           for (int u = 0; u < PU; ++u) pb[u] = jv[u] >= 0 ? L2.p[jv[u]] : T1kOvlP{0ull, 0ull};
@@ -645,12 +729,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
         const T1kOvl o = t1k_ovl_unpack(pv[u]);
         double os = ovlSim(o);
         const bool tie = o.matchCnt == r1.matchCnt && os > r1s;
-        bool inSlot = false;
-        if (tie) {
-          if (lds) inSlot = (hVal[ljFind<LJ_SLOTS>(hKey, o.allele)] & 0x8000u) != 0;
-          else if (!dup) { uint64_t e = tab2[o.allele]; inSlot = (e >> 32) == (epoch >> 32) && (e & 0x80000000ull); }
-          else { uint64_t e = tabSlot[o.allele]; inSlot = (e >> 32) == (epoch >> 32) && (e & 0x40000000ull); }
-        }
+        const bool inSlot = tie && jt.member(o.allele);
         if (o.matchCnt > r1.matchCnt || (tie && !inSlot)) {
           if (truncatedMate(P.ref, o, r1, r2)) sFail = 1;
           else if (os > r2s + 0.1) sFail = 1;
@@ -667,12 +746,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
         const T1kOvl o = t1k_ovl_unpack(pv[u]);
         double os = ovlSim(o);
         const bool tie = o.matchCnt == r2.matchCnt && os > r2s;
-        bool inSlot = false;
-        if (tie) {
-          if (lds) inSlot = (hVal[ljFind<LJ_SLOTS>(hKey, o.allele)] & 0x8000u) != 0;
-          else if (!dup) { uint64_t e = tab2[o.allele]; inSlot = (e >> 32) == (epoch >> 32) && (e & 0x80000000ull); }
-          else { uint64_t e = tabSlot[o.allele]; inSlot = (e >> 32) == (epoch >> 32) && (e & 0x40000000ull); }
-        }
+        const bool inSlot = tie && jt.member(o.allele);
         if (o.matchCnt > r2.matchCnt || (tie && !inSlot)) {
           if (truncatedMate(P.ref, o, r2, r1)) sFail = 1;
           else if (os > r1s + 0.1) sFail = 1;
@@ -738,9 +812,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
     // ---- rowset form: the row ordered by allele index (the order of a coalesced group's entries, Genotyper.hpp:847-853), its place
     // in the list kept in the `qual` slot (all assignment qualities are 1), and a 128-bit hash of the allele pattern ---------------
     __shared__ unsigned long long sRowBase;
-    uint32_t *sAllele = hKey;  // [SORT_TILE]: the join table is done with by now (the barriers of the phases above lie between); 8 KB less
-                               // LDS lets a fourth workgroup onto the CU
-    static_assert(SORT_TILE <= LJ_SLOTS, "the rank-sort tile lives in the join table's keys");
+    uint32_t *sAllele = ljMem;  // [SORT_TILE]: the join table is done with by now (the barriers of the phases above lie between); 8 KB less
+                                // LDS lets a fourth workgroup onto the CU
+    static_assert(SORT_TILE <= LJ_SLOTS, "the rank-sort tile lives in the join table's first words");
     __shared__ unsigned long long sHash[2][NWAVE];
     if (tid == 0) {
       // (the row cursor: T1K_ROW_RESERVE > 0 takes that many entries at a time -- a row holds ~14 -- and serves the workgroup's next rows from what is
@@ -756,7 +830,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
         }
       }
       if (!fitsChunk) { atomicOr(&P.counters[2], 128ull); sRowBase = ~0ull; }
-      else { sRowBase = b; statRows += nRow; }
+      else { sRowBase = b; sStatRows += nRow; }
     }
     // rank of every entry among the row's (distinct) alleles
     for (uint32_t q = tid; q < nRow; q += WG) frags[keep[q]].slot = 0;
@@ -810,8 +884,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
     PP(7);
   }
   if (tid == 0) {  // the workgroup's statistics, once
-    if (statOvl) atomicAdd(&P.counters[22], statOvl);
-    if (statRows) atomicAdd(&P.counters[9], statRows);
+    if (sStatOvl) atomicAdd(&P.counters[22], sStatOvl);
+    if (sStatRows) atomicAdd(&P.counters[9], sStatRows);
   }
 #ifdef T1K_PAIR_PROFILE
   if (tid == 0) for (int i = 0; i < 8; ++i) atomicAdd(&P.counters[32 + i], (unsigned long long)tp_[i]);
@@ -894,11 +968,15 @@ static int pairLaunch(t1k_ctx *ctx, t1k_rowset *rs, const uint32_t *end1, const 
   p.counters = (unsigned long long *)ctx->bCounters.p;
   p.whitelist = dWhitelist;
   { static const int lf = getenv("T1K_PAIR_LIST") ? 1 : 0; p.listForm = lf; }
+  p.direct = pairDirectOn();
   if (getenv("T1K_DEBUG_TRACE")) fprintf(stderr, "[t1k trace] pair %u fragments%s\n", n, rs ? " into the rowset" : "");
   for (int attempt = 0;; ++attempt) {
     T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + 2 * 8, 0, 8, ctx->stream));
     T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + 9 * 8, 0, 8, ctx->stream));
     T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + 22 * 8, 0, 40, ctx->stream));  // [22] overlaps read, [23] long fragments, [24] their arena cursor, [25] / [26] next fragment of the two launches
+#ifdef T1K_PAIR_ROUTES
+    T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + 40 * 8, 0, 12 * 8, ctx->stream));
+#endif
     size_t chunk = 0;
     if (rs) {
       if ((rc = t1k_rowset_chunk(rs, ctx, &chunk, &p.rsRows, &p.rsCap, &p.rsCursor))) return rc;
@@ -942,6 +1020,17 @@ static int pairLaunch(t1k_ctx *ctx, t1k_rowset *rs, const uint32_t *end1, const 
     if (hc[2]) return t1k_fail(ctx, T1K_ERR_CAPACITY, "device arena overflow: row_cap / fragment scratch");
     if (!rs) ctx->nRows = hc[9];
     ctx->stats.rows = hc[9]; ctx->stats.pair_overlaps = hc[22];
+#ifdef T1K_PAIR_ROUTES
+    {
+      static unsigned long long sum[12];
+      static const int once = atexit([] {
+        static const char *name[6] = {"hash, first launch", "HBM, first launch", "direct, first launch", "hash, second launch", "HBM, second launch", "direct, second launch"};
+        for (int r = 0; r < 6; ++r) fprintf(stderr, "[t1k] pair routes (direct route %d): %-22s %12llu fragments %14llu records\n", pairDirectOn(), name[r], sum[2 * r], sum[2 * r + 1]);
+      });
+      (void)once;
+      for (int r = 0; r < 12; ++r) __atomic_fetch_add(&sum[r], hc[40 + r], __ATOMIC_RELAXED);
+    }
+#endif
 #ifdef T1K_PAIR_PROFILE
     fprintf(stderr, "[t1k] pair phases (ticks, thread 0 of every workgroup): tables %llu join %llu best %llu keep %llu rules %llu setreads %llu rank %llu rows+hash %llu\n", hc[32], hc[33], hc[34], hc[35], hc[36], hc[37], hc[38], hc[39]);
 #endif
@@ -970,6 +1059,9 @@ void t1k_pair_limits(uint32_t out[4]) {
   out[2] = SORT_TILE;
   out[3] = PAIR_WG * T1K_PAIR_UNROLL; // list records one round of the streamed passes covers
 }
+
+// TEST-ONLY: allele numbers a fragment's two lists may span to be joined through the LDS table indexed by allele offset (the kernel's DIRECT_CAP)
+uint32_t t1k_pair_direct_cap(void) { return directCapacity(PAIR_LJ_SLOTS); }
 
 int t1k_rows_download(t1k_ctx *ctx, uint32_t *rowCounts, uint8_t *fragAssigned, t1k_row_entry *rows, uint64_t cap, uint64_t *total) {
   if (!ctx) return T1K_ERR_ARG;
