@@ -445,6 +445,36 @@ int t1k_phase_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, u
 int t1k_phase_stats(t1k_ctx *ctx, uint64_t *observations, uint64_t *bookings, uint64_t *keysEmitted, uint64_t *discordant, uint64_t *folds, double *foldMs);
 int t1k_phase_end(t1k_ctx *ctx);
 
+/* ---- CIGAR, MD:Z and NM:i of alignments (analyzer --sam) -----------------------------------------------------------------
+ * Stateless.  Records as for t1k_pileup_add; read_at, w_all and w_uniq are ignored (no read text is read).  alleleText holds the alleles'
+ * bases back to back, allele a at alleleText[alleleOff[a] .. alleleOff[a + 1]).  For record i, its edit string walked from allele position
+ * seq_start:
+ *   cigar[cigarPtr[i] .. cigarPtr[i + 1]): <front>S when clip[2i] > 0, then <length><letter> per maximal run of columns of one class in
+ *     column order (ops 0 and 1: M, op 2: I, op 3: D), then <back>S when clip[2i + 1] > 0.  Decimal, no padding, no terminator; runs are
+ *     literal (a string that begins or ends with I or D stays so).  clip = NULL: no clips.
+ *   md[mdPtr[i] .. mdPtr[i + 1]): the value of MD:Z: as samtools calmd writes it -- a number, then items, each followed by a number.  An
+ *     op-1 column is the item <allele base>; a maximal run of op-3 columns that are consecutive in the edit string is ^<allele bases>
+ *     (op-2 columns are invisible but end a deletion run: 3 2 3 gives 0^A0^C0); the number is the count of op-0 columns since the item
+ *     before, 0 when there are none.  Allele bases are copied as they stand.
+ *   nm[i]: the columns with op 1, 2 or 3.  refSpan[i]: the columns with op 0, 1 or 3.
+ * cigarPtr[0] = mdPtr[0] = 0; both arenas are packed in record order.  What the caller's arenas have to hold, per record:
+ *   CIGAR <= 2 * n_ops + 22 bytes: a run of L columns costs digits(L) + 1 <= L + 1 bytes and there are at most n_ops runs whose lengths
+ *     add up to n_ops, 2 * n_ops in all; a clip costs at most 10 digits + S = 11 bytes, and there are two.
+ *   MD <= 3 * n_ops + 11 bytes: the most expensive column is a one-column deletion behind no match, 0^C = 3 bytes; a number of d > 1
+ *     digits stands for >= 10^(d-1) >= d match columns that cost nothing themselves; the final number has at most 10 digits (11 leaves
+ *     one spare).
+ * The CIGAR bound is attained: a string whose class alternates every column costs 2 * n_ops, two clips of ten digits 22.  The MD bound is
+ * not tight: deletion runs need a column between them, and the dearest such column is a mismatch (0A, 2 bytes), so the worst string
+ * alternates ops 3 and 1 at 2.5 * n_ops + 2 bytes; a lone deletion column (0^C0) costs 3 * n_ops + 1.
+ * T1K_ERR_ARG: an allele >= nAlleles, n_ops == 0, an op outside 0 .. 3, a string that leaves `ops`, a walk that leaves its allele,
+ * alleleOff not starting at 0 or decreasing; T1K_ERR_CAPACITY: an arena too small (the message names it and the bytes it needs).  A
+ * failing call leaves every output array as it was.  n == 0: T1K_OK, only cigarPtr[0] and mdPtr[0] are written.  kernelMs (may be
+ * NULL): device time from the first kernel to the last. */
+int t1k_cigar_batch(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const uint32_t *clip /* [2 * n]: front, back soft clip of record i; NULL = none */,
+                    const int8_t *ops, uint64_t opsBytes, uint32_t nAlleles, const uint64_t *alleleOff /* [nAlleles + 1] */, const char *alleleText /* [alleleOff[nAlleles]] */,
+                    uint64_t *cigarPtr /* [n + 1] */, char *cigar, uint64_t cigarCap, uint64_t *mdPtr /* [n + 1] */, char *md, uint64_t mdCap,
+                    uint32_t *nm /* [n] */, uint32_t *refSpan /* [n] */, double *kernelMs /* may be NULL */);
+
 /* ---- profiling counters of the last t1k_assign_batch (algorithmic-traffic terms of SURVEY.md 8d) --------------- */
 typedef struct {
   uint64_t read_ends, lookups, postings, hits, groups, candidates, extended, near_best, dp_calls, rows, batches;

@@ -70,6 +70,7 @@ PHASE_NO_MATE = 0xFFFFFFFF
 PHASE_STATES = ("A", "C", "G", "T", "N", "-")
 PILEUP_COUNTERS = ("A", "C", "G", "T", "N", "del", "ins", "A_uniq", "C_uniq", "G_uniq", "T_uniq", "N_uniq", "del_uniq", "ins_uniq")
 assert PILEUP_ALN_DTYPE.itemsize == 40
+CIGAR_FILL = 0xAB  # what Context.cigar_batch fills its output arrays with before the call
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_void_p)
 
@@ -128,6 +129,7 @@ def lib():
     L.t1k_phase_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
     L.t1k_phase_stats.argtypes = [vp, u64p, u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]
     L.t1k_phase_end.argtypes = [vp]
+    L.t1k_cigar_batch.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.POINTER(C.c_double)]
     L.t1k_extract_batch.argtypes = [vp, C.c_uint32, vp, vp]
     L.t1k_extractor_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_stats_get.argtypes = [vp, C.POINTER(Stats)]
@@ -565,6 +567,39 @@ class Context:
             return self.pileup_get(), ms
         finally:
             self.pileup_end()
+
+    # CIGAR / MD / NM of alignments (t1k_cigar_batch)
+    def cigar_batch(self, aln, ops, allele_off, allele_text, clip=None, cigar_cap=None, md_cap=None, raw=False):
+        """aln: PILEUP_ALN_DTYPE records (read_at and the weights are ignored); ops: int8 edit columns; allele_text: the alleles' bases back
+        to back (bytes or uint8 array); clip: uint32 [n, 2] front / back soft clips or None.  The arenas hold cigar_cap / md_cap bytes
+        (default: the header's bounds, 2 * n_ops + 22 and 3 * n_ops + 11 per record).  -> dict(cigar_ptr, cigar, md_ptr, md, nm, ref_span,
+        ms): uint64 [n + 1] offsets into the uint8 arenas, uint32 [n] counts, the kernels' device time.  raw=True: (status code, the same
+        dict) without raising; every output array is filled with CIGAR_FILL bytes before the call."""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        n = len(a)
+        o = np.ascontiguousarray(ops, np.int8)
+        off = np.ascontiguousarray(allele_off, np.uint64)
+        t = np.frombuffer(allele_text, np.uint8) if isinstance(allele_text, (bytes, bytearray)) else np.ascontiguousarray(allele_text, np.uint8)
+        c = None if clip is None else np.ascontiguousarray(clip, np.uint32).reshape(-1)
+        assert c is None or len(c) == 2 * n
+        n_ops = a["n_ops"].astype(np.int64)
+        cigar_cap = int((2 * n_ops + 22).sum()) if cigar_cap is None else int(cigar_cap)
+        md_cap = int((3 * n_ops + 11).sum()) if md_cap is None else int(md_cap)
+        out = dict(cigar_ptr=np.empty(n + 1, np.uint64), cigar=np.empty(cigar_cap, np.uint8), md_ptr=np.empty(n + 1, np.uint64), md=np.empty(md_cap, np.uint8),
+                   nm=np.empty(n, np.uint32), ref_span=np.empty(n, np.uint32))
+        for v in out.values():
+            v.view(np.uint8)[:] = CIGAR_FILL
+        ms = C.c_double()
+        rc = lib().t1k_cigar_batch(self.h, _ptr(a), n, None if c is None else _ptr(c), _ptr(o), len(o), max(len(off) - 1, 0), _ptr(off), _ptr(t),
+                                   _ptr(out["cigar_ptr"]), _ptr(out["cigar"]), cigar_cap, _ptr(out["md_ptr"]), _ptr(out["md"]), md_cap, _ptr(out["nm"]), _ptr(out["ref_span"]),
+                                   C.byref(ms))
+        out["ms"] = ms.value
+        if raw:
+            return rc, out
+        self._check(rc, "t1k_cigar_batch")
+        out["cigar"] = out["cigar"][:int(out["cigar_ptr"][n])]
+        out["md"] = out["md"][:int(out["md_ptr"][n])]
+        return out
 
     # per-barcode pileup at sites (t1k_sitepile_begin / _add / _get / _end; DESIGN §11.4); raw=True returns the status code instead of raising
     def sitepile_begin(self, allele_off, site_allele, site_pos, n_barcodes, raw=False):

@@ -70,6 +70,16 @@ struct AnalyzerSitepile {
   std::vector<std::pair<uint32_t, uint32_t>> fileSites;
   uint64_t fileSkipped = 0;
 };
+// --sam: <prefix>_aligned.sam, written piece by piece inside the loop of analyzerAlignAssignments -- CIGAR, MD and NM of a
+// piece's distinct alignments come from one t1k_cigar_batch, the lines are formatted per assignment behind it; nothing is retained
+struct AnalyzerSam {
+  FILE *fp = nullptr;
+  std::string path;
+  uint64_t nAln = 0, nLines = 0, cigarBytes = 0, mdBytes = 0;  // alignments encoded, lines written, bytes of the two arenas
+  double msCalls = 0, msKernels = 0, msWrite = 0;
+  ~AnalyzerSam() { if (fp) fclose(fp); }
+};
+
 static const char *kPhaseHeader = "#allele\tpos1\tpos2\texon_pos1\texon_pos2\tref1\tref2\tvar1\tvar2\tobs1\tobs2\tcount\tcount_uniq\n";
 static const char *kBarcodePileupHeader = "#barcode\tallele\tpos\texon_pos\tref\tvar\tA\tC\tG\tT\tN\tdel\tins\tA_uniq\tC_uniq\tG_uniq\tT_uniq\tN_uniq\tdel_uniq\tins_uniq\n";
 
@@ -124,8 +134,9 @@ static int analyzerPooledEM(t1k_job *job, const std::vector<uint32_t> &cnt, cons
 }
 
 // steps (1) - (3): V.asgPtr / V.asg / V.ops and V.abundance; with `pile`, every piece's alignments go through t1k_pileup_add as well; with `sp`,
-// every piece's records, pattern text and booking lists are kept for analyzerSitepile
-static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerPileup *pile, AnalyzerSitepile *sp = nullptr) {
+// every piece's records, pattern text and booking lists are kept for analyzerSitepile; with `sam`, every piece's alignments go through
+// t1k_cigar_batch and its assignments' lines into the open file
+static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerPileup *pile, AnalyzerSitepile *sp = nullptr, AnalyzerSam *sam = nullptr) {
   const double tv0 = nowMs();
   double &msAssign = V.msAssign, &msDetails = V.msDetails, &msAlign = V.msAlign;
   uint64_t &nEnds = V.nEnds, &nJobs = V.nJobs, &nFast = V.nFast;
@@ -361,14 +372,89 @@ static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerP
         if (a.has_mate_pair) { a.ops2 = opsAtOfJob[j2]; a.n_ops2 = nOpsOfJob[j2]; }
       }
       msAlign += nowMs() - tc;
-      if ((pile || sp) && nJ) {
-        // one record per alignment job; its weights = the assignments that point at it, and those of them whose fragment keeps one assignment
-        const double tp = nowMs();
-        std::vector<t1k_pileup_aln> recs(nJ);
+      // one record per alignment job, for --sam and for the pileups (which count its weights below)
+      std::vector<t1k_pileup_aln> recs((pile || sp || sam) ? nJ : 0);
+      for (size_t j = 0; j < recs.size(); ++j) {
+        const t1k_overlap &o = lists[listAt[jobs[j].end] + jobs[j].idx];
+        recs[j] = t1k_pileup_aln{(uint32_t)o.seq_idx, (uint32_t)o.seq_start, jP[j], opsAtOfJob[j] - pieceOps0, nOpsOfJob[j], 0, 0, 0};
+      }
+      if (sam && nJ) {
+        // every job's clips from its read window; then one line per assignment overlap, in fragment order
+        const double ts = nowMs();
+        std::vector<uint32_t> clip(2 * nJ);
+        uint64_t cigarCap = 0, mdCap = 0;
         for (size_t j = 0; j < nJ; ++j) {
           const t1k_overlap &o = lists[listAt[jobs[j].end] + jobs[j].idx];
-          recs[j] = t1k_pileup_aln{(uint32_t)o.seq_idx, (uint32_t)o.seq_start, jP[j], opsAtOfJob[j] - pieceOps0, nOpsOfJob[j], 0, 0, 0};
+          clip[2 * j] = (uint32_t)o.read_start;
+          clip[2 * j + 1] = ends[jobs[j].end].second - 1u - (uint32_t)o.read_end;
+          cigarCap += 2ull * nOpsOfJob[j] + 22;  // the bounds of t1k_cigar_batch (include/t1k_gpu.h)
+          mdCap += 3ull * nOpsOfJob[j] + 11;
         }
+        std::vector<uint64_t> cigarPtr(nJ + 1), mdPtr(nJ + 1);
+        std::vector<char> cigar(cigarCap), md(mdCap);
+        std::vector<uint32_t> nm(nJ), span(nJ);
+        double kernelMs = 0;
+        if ((rc = t1k_cigar_batch(vctx, recs.data(), (uint32_t)nJ, clip.data(), V.ops.data() + pieceOps0, V.ops.size() - pieceOps0, (uint32_t)R.seqs.size(), refOff.data(), refText.data(),
+                                  cigarPtr.data(), cigar.data(), cigarCap, mdPtr.data(), md.data(), mdCap, nm.data(), span.data(), &kernelMs)) != T1K_OK)
+          return jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(vctx));
+        const double tw = nowMs();
+        sam->nAln += nJ; sam->cigarBytes += cigarPtr[nJ]; sam->mdBytes += mdPtr[nJ];
+        sam->msKernels += kernelMs; sam->msCalls += tw - ts;
+        std::string out;
+        char num[96];
+        bool wrote = true;
+        for (uint32_t f = f0; f < f1; ++f) {
+          const uint64_t k = V.asgPtr[f + 1] - V.asgPtr[f];
+          const int mapq = k == 1 ? 60 : k == 2 ? 3 : k <= 4 ? 1 : 0;
+          const uint32_t r = in.frag[f];
+          for (uint64_t q = V.asgPtr[f]; q < V.asgPtr[f + 1]; ++q) {
+            const t1k_frag_assignment &a = V.asg[q];
+            const int64_t js[2] = {jobOfAsg[0][q - q0], jobOfAsg[1][q - q0]};
+            for (int m = 0; m < 2; ++m) {
+              const int64_t j = js[m];
+              if (j < 0) continue;
+              const t1k_overlap &o = lists[listAt[jobs[j].end] + jobs[j].idx];
+              const bool second = m == 1 || (a.o1_from_r2 && !a.has_mate_pair);  // the line's read-end is read 2
+              int flag = (paired ? 0x1 : 0) | (o.strand == -1 ? 0x10 : 0) | (q > V.asgPtr[f] ? 0x100 : 0);
+              long long pnext = 0, tlen = 0;
+              if (a.has_mate_pair) {
+                const int64_t jm = js[1 - m];
+                const t1k_overlap &om = lists[listAt[jobs[jm].end] + jobs[jm].idx];
+                flag |= 0x2 | (m == 0 ? 0x40 : 0x80) | (om.strand == -1 ? 0x20 : 0);
+                pnext = (long long)om.seq_start + 1;
+                const long long left = std::min<long long>(o.seq_start, om.seq_start);
+                const long long right = std::max<long long>((long long)o.seq_start + span[j], (long long)om.seq_start + span[jm]);  // one behind the rightmost mapped base
+                tlen = right - left;
+                if (o.seq_start > om.seq_start || (o.seq_start == om.seq_start && m == 1)) tlen = -tlen;
+              } else if (paired) flag |= 0x8 | (second ? 0x80 : 0x40);
+              if (in.noIds) { snprintf(num, sizeof num, "r%u", f); out += num; }
+              else out.append(in.side[0].idP[r], in.side[0].idL[r]);
+              snprintf(num, sizeof num, "\t%d\t", flag);
+              out += num;
+              out += R.al[o.seq_idx].name;
+              snprintf(num, sizeof num, "\t%lld\t%d\t", (long long)o.seq_start + 1, mapq);
+              out += num;
+              out.append(cigar.data() + cigarPtr[j], cigarPtr[j + 1] - cigarPtr[j]);
+              snprintf(num, sizeof num, a.has_mate_pair ? "\t=\t%lld\t%lld\t" : "\t*\t%lld\t%lld\t", pnext, tlen);
+              out += num;
+              out.append(pat.data() + (o.strand == -1 ? rcAt[jobs[j].end] : off[jobs[j].end]), ends[jobs[j].end].second);  // the whole read-end, strand-corrected
+              snprintf(num, sizeof num, "\t*\tNM:i:%u\tMD:Z:", nm[j]);
+              out += num;
+              out.append(md.data() + mdPtr[j], mdPtr[j + 1] - mdPtr[j]);
+              snprintf(num, sizeof num, "\tNH:i:%llu\tHI:i:%llu\n", (unsigned long long)k, (unsigned long long)(q - V.asgPtr[f] + 1));
+              out += num;
+              ++sam->nLines;
+            }
+          }
+          if (out.size() >= (1u << 20)) { wrote = wrote && fwrite(out.data(), 1, out.size(), sam->fp) == out.size(); out.clear(); }
+        }
+        wrote = wrote && fwrite(out.data(), 1, out.size(), sam->fp) == out.size();
+        if (!wrote) return jobFail(job, T1K_ERR_IO, "analyzer: cannot write " + sam->path);
+        sam->msWrite += nowMs() - tw;
+      }
+      if ((pile || sp) && nJ) {
+        // a record's weights = the assignments that point at it, and those of them whose fragment keeps one assignment
+        const double tp = nowMs();
         for (uint32_t f = f0; f < f1; ++f) {
           const bool one = V.asgPtr[f + 1] - V.asgPtr[f] == 1;
           for (uint64_t q = V.asgPtr[f]; q < V.asgPtr[f + 1]; ++q) {
@@ -438,10 +524,10 @@ static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerP
   return T1K_OK;
 }
 
-static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants &V, AnalyzerPileup *pile, AnalyzerSitepile *sp) {
+static int analyzerCallVariants(t1k_job *job, int varMaxGroup, AnalyzerVariants &V, AnalyzerPileup *pile, AnalyzerSitepile *sp, AnalyzerSam *sam) {
   const double tv0 = nowMs();
   int rc;
-  if ((rc = analyzerAlignAssignments(job, V, pile, sp)) != T1K_OK) return rc;
+  if ((rc = analyzerAlignAssignments(job, V, pile, sp, sam)) != T1K_OK) return rc;
   const ReadInput &in = *job->in;
   const RefSet &R = job->ref;
   const uint32_t F = (uint32_t)in.nFrag();
@@ -972,6 +1058,31 @@ static int analyzerUmiCollapse(t1k_job *job, const BarcodeLists &L, uint32_t nRo
   return T1K_OK;
 }
 
+// <prefix>_aligned.sam opened and its header written: @HD, one @SQ per selected allele in job->ref.al order (the order of
+// <prefix>_allele_pileup.tsv), @PG.  job == NULL: no allele is selected, no @SQ line
+static bool analyzerSamOpen(t1k_job *job, const std::string &prefix, AnalyzerSam &sam) {
+  sam.path = prefix + "_aligned.sam";
+  sam.fp = fopen(sam.path.c_str(), "w");
+  if (!sam.fp) { fprintf(stderr, "analyzer: cannot write %s\n", sam.path.c_str()); return false; }
+  fputs("@HD\tVN:1.6\tSO:unsorted\tGO:query\n", sam.fp);
+  if (job)
+    for (size_t a = 0; a < job->ref.seqs.size(); ++a) fprintf(sam.fp, "@SQ\tSN:%s\tLN:%zu\n", job->ref.al[a].name.c_str(), job->ref.seqs[a].size());
+  fputs("@PG\tID:t1k-analyzer\tPN:analyzer\n", sam.fp);
+  return true;
+}
+
+// closes the file; T1K_DEBUG_PHASES: what the SAM output took
+static bool analyzerSamClose(AnalyzerSam &sam) {
+  const double t0 = nowMs();
+  const bool ok = fclose(sam.fp) == 0;
+  sam.fp = nullptr;
+  if (!ok) { fprintf(stderr, "analyzer: cannot write %s\n", sam.path.c_str()); return false; }
+  if (getenv("T1K_DEBUG_PHASES"))
+    fprintf(stderr, "sam: %llu alignments encoded, %llu lines written, %llu CIGAR bytes, %llu MD bytes; calls %.1f ms, kernels %.1f ms, format + write %.1f ms\n", (unsigned long long)sam.nAln,
+            (unsigned long long)sam.nLines, (unsigned long long)sam.cigarBytes, (unsigned long long)sam.mdBytes, sam.msCalls, sam.msKernels, sam.msWrite + (nowMs() - t0));
+  return true;
+}
+
 static const char *kAnalyzerUsage =
     "./analyzer [OPTIONS]:   (MI355X build of the T1K post-analysis stage: re-assignment, novel variants, per-barcode summary)\n"
     "Required:\n"
@@ -996,6 +1107,8 @@ static const char *kAnalyzerUsage =
     "\t\tone line per (barcode, site) with a read (needs --barcode)\n"
     "\t--phase: also write prefix_allele_phase.tsv, for every two of the positions of prefix_allele.vcf and of --sites on one allele the fragments that\n"
     "\t\tshow both, by what they show there (A C G T N or - for a deletion): read-backed phasing of the variants\n"
+    "\t--sam: also write prefix_aligned.sam, the alignments the variant pass holds as SAM records on the selected alleles (CIGAR, NM, MD, NH, HI), one line per\n"
+    "\t\taligned read-end of every assignment of every assigned fragment (no counterpart in the reference)\n"
     "\t--sites FILE: more sites for --barcodePileup and --phase, one per line as allele_name<TAB>pos (1-based, the pos column of prefix_allele_pileup.tsv); '#' lines,\n"
     "\t\tblank lines and alleles that are not selected are skipped\n"
     "\t--relaxIntronAlign: allow one more mismatch in intronic alignment\n"
@@ -1009,14 +1122,14 @@ int t1k_analyzer_main(int argc, char **argv) {
                                      {"alleleDelimiter", required_argument, 0, 10006}, {"varMaxGroup", required_argument, 0, 10007}, {"device", required_argument, 0, 10010},
                                      {"barcodeEM", no_argument, 0, 10011}, {"barcodeEMPrior", required_argument, 0, 10012}, {"umi", required_argument, 0, 10013},
                                      {"umiMismatch", required_argument, 0, 10014}, {"pileup", no_argument, 0, 10015}, {"barcodePileup", no_argument, 0, 10016},
-                                     {"sites", required_argument, 0, 10017}, {"phase", no_argument, 0, 10018}, {0, 0, 0, 0}};
+                                     {"sites", required_argument, 0, 10017}, {"phase", no_argument, 0, 10018}, {"sam", no_argument, 0, 10019}, {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
   std::string refFile, alleleFile, prefix = "t1k", barcode;
   std::vector<const char *> f1, f2, single;
   int varMaxGroup = 8;  // Analyzer.cpp:251
-  bool barcodeEM = false, pileup = false, barcodePileup = false, phase = false;
+  bool barcodeEM = false, pileup = false, barcodePileup = false, phase = false, samOut = false;
   double emPrior = 0;
   const char *emPriorText = nullptr, *umiMismatchText = nullptr;
   std::string umiPath, sitesPath;
@@ -1048,6 +1161,7 @@ int t1k_analyzer_main(int argc, char **argv) {
       case 10016: barcodePileup = true; break;
       case 10017: sitesPath = optarg; break;
       case 10018: phase = true; break;
+      case 10019: samOut = true; break;
       default: fprintf(stderr, "%s", kAnalyzerUsage); return EXIT_FAILURE;
     }
   }
@@ -1122,6 +1236,10 @@ int t1k_analyzer_main(int argc, char **argv) {
       fputs(kPhaseHeader, fs);
       fclose(fs);
     }
+    if (samOut) {
+      AnalyzerSam sam;
+      if (!analyzerSamOpen(nullptr, prefix, sam) || !analyzerSamClose(sam)) return EXIT_FAILURE;
+    }
     logLine("Post analysis finishes.");
     return 0;
   }
@@ -1169,14 +1287,16 @@ int t1k_analyzer_main(int argc, char **argv) {
   if (sp) sp->bcOf = &bcOf;
   AnalyzerVariants V;
   std::unique_ptr<AnalyzerPileup> pile(pileup ? new AnalyzerPileup : nullptr);
+  std::unique_ptr<AnalyzerSam> sam(samOut ? new AnalyzerSam : nullptr);
+  if (sam && !analyzerSamOpen(job, prefix, *sam)) { t1k_job_destroy(job); return EXIT_FAILURE; }
   if (varMaxGroup != 0) {  // (0: VariantCaller::ComputeVariant returns before it looks at a read, VariantCaller.hpp:980-981)
-    rc = analyzerCallVariants(job, varMaxGroup, V, pile.get(), sp.get());
+    rc = analyzerCallVariants(job, varMaxGroup, V, pile.get(), sp.get(), sam.get());
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
     logLine("Finish allele quantification in %d EM iterations.", V.emIterations);
-  } else if (pileup || (sp && !sp->fileSites.empty())) {
+  } else if (pileup || sam || (sp && !sp->fileSites.empty())) {
     // no variant is called, but the pileup is of the alignments of steps (1) - (3): they run, VariantCaller does not (V.vc stays empty: the
     // VCF is the empty file and the per-barcode table counts the raw lists).  --barcodePileup and --phase without sites of their own have nothing to book.
-    rc = analyzerAlignAssignments(job, V, pile.get(), sp.get());
+    rc = analyzerAlignAssignments(job, V, pile.get(), sp.get(), sam.get());
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
   } else if (barcodeEM && emPrior > 0) {
     // the per-barcode EM's prior is the pooled EM's abundances: step (1) of the variant pass on its own (its outputs are not written)
@@ -1187,6 +1307,10 @@ int t1k_analyzer_main(int argc, char **argv) {
     rc = analyzerRows(job, cnt, rowAt, rows);
     if (rc == T1K_OK) rc = analyzerPooledEM(job, cnt, rowAt, rows, &it);
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
+  }
+  if (sam) {
+    if (!analyzerSamClose(*sam)) { t1k_job_destroy(job); return EXIT_FAILURE; }
+    sam.reset();
   }
   {
     FILE *fp = fopen((prefix + "_allele.vcf").c_str(), "w");  // VariantCaller::OutputAlleleVCF (1202-1227)

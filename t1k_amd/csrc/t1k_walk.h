@@ -1,5 +1,5 @@
-// t1k_amd/csrc/t1k_walk.h -- internal: what k_pileup (t1k_pileup.hip), k_sitepile (t1k_sitepile.hip) and k_phase_obs (t1k_phase.hip) share, on both
-// sides of the launch.
+// t1k_amd/csrc/t1k_walk.h -- internal: what k_pileup (t1k_pileup.hip), k_sitepile (t1k_sitepile.hip), k_phase_obs (t1k_phase.hip) and k_cigar_size /
+// k_cigar_emit (t1k_cigar.hip) share, on both sides of the launch.
 // Device: the record header of a wave (pileupLoadRec), the edit-string walk of one alignment by one wave64 (pileupWalk) and the verdict on
 // where it ended (pileupWalkVerdict).  64 edit columns per step.  A lane's allele coordinate is seq_start + the non-insert ops before it, its
 // read coordinate the non-delete ops before it: a ballot, a population count below the lane, and wave-uniform running totals -- no lane
