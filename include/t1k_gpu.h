@@ -445,6 +445,37 @@ int t1k_phase_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, u
 int t1k_phase_stats(t1k_ctx *ctx, uint64_t *observations, uint64_t *bookings, uint64_t *keysEmitted, uint64_t *discordant, uint64_t *folds, double *foldMs);
 int t1k_phase_end(t1k_ctx *ctx);
 
+/* ---- strand, mate, read-end distance and template support at sites (analyzer --siteSupport) ----------------------------
+ * What t1k_pileup_* counts, restricted to sites as for t1k_sitepile_begin (at most 2^28 of them, else T1K_ERR_CAPACITY; nSites = 0 is
+ * legal) and split by the evidence behind a booking.  Records as for t1k_pileup_add (w_all / w_uniq / reserved are ignored and stay
+ * untouched); rec[i] describes the read-end record i is a window of: its length read_len (1 .. 65535), the bases clip_front in front of
+ * the window in the strand-corrected read-end, and strand (0: the read-end lies on the allele's forward strand, 1: reverse).  Record i
+ * books once per entry of book[bookPtr[i] .. bookPtr[i + 1]); an entry's flags are bit 0 uniq (its fragment has one assignment), bit 1
+ * mate (the read-end comes from file 2), bit 2 orient (of its template), and t_start <= t_end < the allele's length are the template's
+ * first and last allele position.
+ * A column of state 0 .. 6 (A C G T N del ins) that books at site s, at allele position pos, has c = clip_front + the read bases of the
+ * window in front of it and the end distance d = min(c, read_len - 1 - c) where it consumes base c (ops 0, 1, 2), d = min(c, read_len - c)
+ * for op 3, which lies between bases c - 1 and c; d is stored saturated at 511.  With every booking the column adds 1 under two keys of ONE
+ * sparse table of (key, count) runs, ascending by key:
+ *   family A, the support:   ((((s * 7 + state) * 2 + strand) * 2 + mate) * 512 + d) * 2 + (1 - uniq), below 2^57.  A uniq booking is
+ *                            stored once, under the even key, as in t1k_sitepile_*: plain = even + odd, _uniq = even;
+ *   family B, the templates: 2^57 | (((s * 7 + state) * 2 + orient) << 24) | (dStart << 12) | dEnd with dStart = min(pos - t_start, 4095)
+ *                            and dEnd = min(t_end - pos, 4095), each clamped below at 0; below 2^58.  The reader counts the RUNS of a
+ *                            (site, state) and ignores their counts: templates that differ only beyond 4095 bases from the site are one.
+ * Nothing is emitted unless the whole call is sound: T1K_ERR_ARG for what t1k_sitepile_add refuses (allele, ops, walks, bookPtr), a
+ * strand > 1, read_len == 0 or > 65535, a read window that leaves its read (clip_front + the read bases the walk consumes > read_len),
+ * flags >= 8, t_start > t_end, t_end >= the length of the record's allele; T1K_ERR_CAPACITY and T1K_ERR_STATE as t1k_sitepile_*.  Pending
+ * keys are folded into runs whenever they reach 2^28 (env T1K_SUPPORT_PENDING) and at _get.  t1k_support_get / _stats: as t1k_sitepile_get /
+ * _stats. */
+typedef struct { uint32_t read_len, clip_front, strand; } t1k_support_rec;   /* per record; strand: 0 forward, 1 reverse */
+typedef struct { uint32_t flags, t_start, t_end; } t1k_support_book;         /* per booking; flags: bit 0 uniq, bit 1 mate (file 2), bit 2 orient */
+int t1k_support_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff /* [nAlleles + 1] */, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos);
+int t1k_support_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const t1k_support_rec *rec /* [n] */, const uint64_t *bookPtr /* [n + 1] */,
+                    const t1k_support_book *book, const char *text, uint64_t textBytes, const int8_t *ops, uint64_t opsBytes, double *kernelMs);
+int t1k_support_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns);
+int t1k_support_stats(t1k_ctx *ctx, uint64_t *keysEmitted, uint64_t *folds, double *foldMs);
+int t1k_support_end(t1k_ctx *ctx);
+
 /* ---- CIGAR, MD:Z and NM:i of alignments (analyzer --sam) -----------------------------------------------------------------
  * Stateless.  Records as for t1k_pileup_add; read_at, w_all and w_uniq are ignored (no read text is read).  alleleText holds the alleles'
  * bases back to back, allele a at alleleText[alleleOff[a] .. alleleOff[a + 1]).  For record i, its edit string walked from allele position

@@ -70,6 +70,12 @@ PHASE_NO_MATE = 0xFFFFFFFF
 PHASE_STATES = ("A", "C", "G", "T", "N", "-")
 PILEUP_COUNTERS = ("A", "C", "G", "T", "N", "del", "ins", "A_uniq", "C_uniq", "G_uniq", "T_uniq", "N_uniq", "del_uniq", "ins_uniq")
 assert PILEUP_ALN_DTYPE.itemsize == 40
+# t1k_support_rec / t1k_support_book (support at sites), the states of its lines, and where its second key family begins
+SUPPORT_REC_DTYPE = np.dtype([("read_len", "<u4"), ("clip_front", "<u4"), ("strand", "<u4")])
+SUPPORT_BOOK_DTYPE = np.dtype([("flags", "<u4"), ("t_start", "<u4"), ("t_end", "<u4")])
+SUPPORT_STATES = ("A", "C", "G", "T", "N", "-", "+")
+SUPPORT_FAMILY_B = 1 << 57
+assert SUPPORT_REC_DTYPE.itemsize == 12 and SUPPORT_BOOK_DTYPE.itemsize == 12
 CIGAR_FILL = 0xAB  # what Context.cigar_batch fills its output arrays with before the call
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_void_p)
@@ -124,6 +130,11 @@ def lib():
     L.t1k_sitepile_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
     L.t1k_sitepile_stats.argtypes = [vp, u64p, u64p, C.POINTER(C.c_double)]
     L.t1k_sitepile_end.argtypes = [vp]
+    L.t1k_support_begin.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp]
+    L.t1k_support_add.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_double)]
+    L.t1k_support_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
+    L.t1k_support_stats.argtypes = [vp, u64p, u64p, C.POINTER(C.c_double)]
+    L.t1k_support_end.argtypes = [vp]
     L.t1k_phase_begin.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp]
     L.t1k_phase_add.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_double)]
     L.t1k_phase_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
@@ -662,6 +673,74 @@ class Context:
             return keys, counts, ms, self.sitepile_stats()[1]
         finally:
             self.sitepile_end()
+
+    # strand / mate / end-distance / template support at sites (t1k_support_begin / _add / _get / _stats / _end); raw=True returns the status
+    # code instead of raising
+    def support_begin(self, allele_off, site_allele, site_pos, raw=False):
+        off = np.ascontiguousarray(allele_off, np.uint64)
+        sa, sp = np.ascontiguousarray(site_allele, np.uint32), np.ascontiguousarray(site_pos, np.uint32)
+        assert len(sa) == len(sp)
+        rc = lib().t1k_support_begin(self.h, max(len(off) - 1, 0), _ptr(off), len(sa), _ptr(sa), _ptr(sp))
+        if raw:
+            return rc
+        self._check(rc, "t1k_support_begin")
+
+    def support_add(self, aln, rec, book_ptr, book, text, ops, raw=False):
+        """aln: PILEUP_ALN_DTYPE records; rec: one SUPPORT_REC_DTYPE per record (its read-end's length, the bases in front of the window, the
+        strand); record i books once per entry of book[book_ptr[i]:book_ptr[i + 1]] (SUPPORT_BOOK_DTYPE: flags = uniq | mate << 1 |
+        orient << 2, the template's extent); text / ops as for pileup_add.  Returns the kernels' device time in ms"""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        rc_ = np.ascontiguousarray(rec, SUPPORT_REC_DTYPE)
+        bp, bk = np.ascontiguousarray(book_ptr, np.uint64), np.ascontiguousarray(book, SUPPORT_BOOK_DTYPE)
+        assert len(bp) == len(a) + 1 and len(rc_) == len(a)
+        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+        o = np.ascontiguousarray(ops, np.int8)
+        ms = C.c_double()
+        rc = lib().t1k_support_add(self.h, _ptr(a), len(a), _ptr(rc_), _ptr(bp), _ptr(bk), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
+        if raw:
+            return rc
+        self._check(rc, "t1k_support_add")
+        return ms.value
+
+    def support_get(self, raw=False):
+        """the table's runs, ascending: (keys uint64, counts int32).  Below SUPPORT_FAMILY_B: key = ((((site * 7 + state) * 2 + strand) * 2 + mate)
+        * 512 + d) * 2 + (1 - uniq); from there on: SUPPORT_FAMILY_B | ((site * 7 + state) * 2 + orient) << 24 | dStart << 12 | dEnd, one run per
+        distinct template"""
+        n = C.c_uint64()
+        rc = lib().t1k_support_get(self.h, None, None, 0, C.byref(n))
+        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
+        if rc == 0 and n.value:
+            rc = lib().t1k_support_get(self.h, _ptr(keys), _ptr(counts), n.value, C.byref(n))
+        if raw:
+            return rc
+        self._check(rc, "t1k_support_get")
+        return keys, counts
+
+    def support_stats(self):
+        """(keys emitted, folds, device ms of the folds) of the open table"""
+        k, f, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        self._check(lib().t1k_support_stats(self.h, C.byref(k), C.byref(f), C.byref(ms)), "t1k_support_stats")
+        return k.value, f.value, ms.value
+
+    def support_end(self, raw=False):
+        rc = lib().t1k_support_end(self.h)
+        if raw:
+            return rc
+        self._check(rc, "t1k_support_end")
+
+    def support(self, allele_off, site_allele, site_pos, aln, rec, book_ptr, book, text, ops, cuts=()):
+        """begin, add (the records split at the indices `cuts` into several calls), get, end: (keys, counts, kernels' ms, folds)"""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        rc_ = np.ascontiguousarray(rec, SUPPORT_REC_DTYPE)
+        bp = np.ascontiguousarray(book_ptr, np.uint64)
+        self.support_begin(allele_off, site_allele, site_pos)
+        try:
+            edges = [0] + [int(c) for c in cuts] + [len(a)]
+            ms = sum(self.support_add(a[lo:hi], rc_[lo:hi], bp[lo:hi + 1], book, text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
+            keys, counts = self.support_get()
+            return keys, counts, ms, self.support_stats()[1]
+        finally:
+            self.support_end()
 
     # read-backed phasing of site pairs (t1k_phase_begin / _add / _get / _stats / _end; DESIGN §11.5); raw=True returns the status code instead of raising
     def phase_begin(self, allele_off, site_allele, site_pos, raw=False):

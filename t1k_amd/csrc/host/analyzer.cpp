@@ -52,7 +52,10 @@ static const char *kPileupHeader = "#allele\tpos\texon_pos\tref\tA\tC\tG\tT\tN\t
 // the read text of the assigned fragments (once more for the read-ends with an overlap on the other strand) + 40 bytes per distinct
 // alignment + 4 bytes per assignment overlap.
 // --phase replays the same pieces through t1k_phase_add: its bookings are the assignments themselves, (record of mate 1,
-// record of mate 2 or none, uniq), 9 more bytes per assignment.  Either flag keeps the pieces; each keeps its own booking lists only.
+// record of mate 2 or none, uniq), 9 more bytes per assignment.
+// --siteSupport replays them through t1k_support_add: per distinct alignment its read-end's length, front clip and strand
+// (12 bytes), per assignment overlap its flags and its template's extent (12 bytes, plus the 8 bytes of a list pointer per alignment).
+// Any of the flags keeps the pieces; each keeps its own booking lists only.
 struct AnalyzerSitepile {
   struct Piece {
     std::vector<t1k_pileup_aln> recs;
@@ -61,9 +64,12 @@ struct AnalyzerSitepile {
     std::vector<uint32_t> book;
     std::vector<uint32_t> asgRec;    // --phase: two per assignment, 0xFFFFFFFF = no mate
     std::vector<uint8_t> asgUniq;
+    std::vector<t1k_support_rec> supRec;     // --siteSupport: one per record,
+    std::vector<uint64_t> supBookPtr;        // its bookings
+    std::vector<t1k_support_book> supBook;   // one per assignment overlap
     uint64_t ops0 = 0, ops1 = 0;   // the piece's edit strings: V.ops[ops0 .. ops1)
   };
-  bool barcodes = false, phase = false;    // --barcodePileup, --phase
+  bool barcodes = false, phase = false, support = false;    // --barcodePileup, --phase, --siteSupport
   const std::vector<int> *bcOf = nullptr;  // fragment -> barcode id (--barcodePileup)
   std::vector<Piece> pieces;
   // extra sites of --sites (allele, 0-based position), and the lines of the file that name an allele which is not selected
@@ -81,7 +87,8 @@ struct AnalyzerSam {
 };
 
 static const char *kPhaseHeader = "#allele\tpos1\tpos2\texon_pos1\texon_pos2\tref1\tref2\tvar1\tvar2\tobs1\tobs2\tcount\tcount_uniq\n";
-static const char *kBarcodePileupHeader = "#barcode\tallele\tpos\texon_pos\tref\tvar\tA\tC\tG\tT\tN\tdel\tins\tA_uniq\tC_uniq\tG_uniq\tT_uniq\tN_uniq\tdel_uniq\tins_uniq\n";
+static const char *kSupportHeader = "#allele\tpos\texon_pos\tref\tvar\tobs\tcount\tcount_uniq\tfwd\trev\tmate1\tmate2\tend_min\tend_med\tnear_end\ttemplates\n";
+static const char *kBarcodePileupHeader ="#barcode\tallele\tpos\texon_pos\tref\tvar\tA\tC\tG\tT\tN\tdel\tins\tA_uniq\tC_uniq\tG_uniq\tT_uniq\tN_uniq\tdel_uniq\tins_uniq\n";
 
 // every fragment's raw row (the reference's list order): cnt[f] entries at rows[rowAt[f]]
 static int analyzerRows(t1k_job *job, std::vector<uint32_t> &cnt, std::vector<uint64_t> &rowAt, std::vector<t1k_row_entry> &rows) {
@@ -489,9 +496,38 @@ static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerP
             fill.assign(pc.bookPtr.begin(), pc.bookPtr.end() - 1);
           }
           if (sp->phase) { pc.asgRec.reserve(2 * nAsg); pc.asgUniq.reserve(nAsg); }
+          std::vector<uint64_t> supFill;
+          if (sp->support) {
+            // per record what AnalyzerSam takes its clips and flag 0x10 from: the read-end's length, the bases in front of the window (in the
+            // strand-corrected read-end, which is what `pat` holds) and the strand
+            pc.supRec.resize(nJ);
+            pc.supBookPtr.assign(nJ + 1, 0);
+            for (size_t j = 0; j < nJ; ++j) {
+              const t1k_overlap &o = lists[listAt[jobs[j].end] + jobs[j].idx];
+              pc.supRec[j] = t1k_support_rec{ends[jobs[j].end].second, (uint32_t)o.read_start, o.strand == -1 ? 1u : 0u};
+              pc.supBookPtr[j + 1] = pc.supBookPtr[j] + recs[j].w_all;
+            }
+            pc.supBook.resize(pc.supBookPtr[nJ]);
+            supFill.assign(pc.supBookPtr.begin(), pc.supBookPtr.end() - 1);
+          }
           for (uint32_t f = f0; f < f1; ++f) {
             const uint32_t one = V.asgPtr[f + 1] - V.asgPtr[f] == 1 ? 1u : 0u;
             for (uint64_t q = V.asgPtr[f]; q < V.asgPtr[f + 1]; ++q) {
+              if (sp->support) {
+                // the template of the assignment: both mates' extent on the allele, and which way the fragment lies (file 1 on the reverse
+                // strand; with a file-2 read-end alone, that one on the forward strand)
+                const t1k_frag_assignment &a = V.asg[q];
+                const bool pairHere = a.has_mate_pair != 0, from2 = a.o1_from_r2 && !pairHere;
+                const uint32_t tStart = (uint32_t)(pairHere ? std::min(a.o1.seq_start, a.o2.seq_start) : a.o1.seq_start);
+                const uint32_t tEnd = (uint32_t)(pairHere ? std::max(a.o1.seq_end, a.o2.seq_end) : a.o1.seq_end);
+                const uint32_t orient = (from2 ? a.o1.strand == 1 : a.o1.strand == -1) ? 1u : 0u;
+                for (int m = 0; m < 2; ++m) {
+                  const int64_t j = jobOfAsg[m][q - q0];
+                  if (j < 0) continue;
+                  const uint32_t second = (m == 1 || from2) ? 1u : 0u;  // the read-end is read 2, as AnalyzerSam's `second`
+                  pc.supBook[supFill[j]++] = t1k_support_book{one | (second << 1) | (orient << 2), tStart, tEnd};
+                }
+              }
               if (sp->barcodes)
                 for (int m = 0; m < 2; ++m) {
                   const int64_t j = jobOfAsg[m][q - q0];
@@ -635,7 +671,7 @@ static bool analyzerReadSites(t1k_job *job, const std::string &path, AnalyzerSit
   return ok;
 }
 
-// the sites of --barcodePileup and --phase: the rows of _allele.vcf united with those of --sites, sorted and free of
+// the sites of --barcodePileup, --phase and --siteSupport: the rows of _allele.vcf united with those of --sites, sorted and free of
 // duplicates; per site the called bases in VCF order and the columns both files print for it
 struct AnalyzerSiteList {
   std::vector<std::pair<uint32_t, uint32_t>> sites;
@@ -828,6 +864,107 @@ static bool analyzerPhase(t1k_job *job, const std::string &prefix, const Analyze
     fprintf(stderr, "phase: %zu sites, %llu records, %llu bookings (%llu with two observed sites or more), %llu observations, %llu discordant, %llu keys emitted, %llu folds, %llu cells; "
                     "upload %.1f ms, kernels %.1f ms, fold %.1f ms, write %.1f ms\n", nSites, (unsigned long long)nRecs, (unsigned long long)nBook, (unsigned long long)nPaired,
             (unsigned long long)nObs, (unsigned long long)discordant, (unsigned long long)emitted, (unsigned long long)folds, (unsigned long long)cells,
+            std::max(0.0, (tw - t0) - msKernels - msFold), msKernels, msFold, nowMs() - tw);
+  return true;
+}
+
+// <prefix>_allele_support.tsv: the kept pieces through t1k_support_add at the sites; one line per (site, obs) with a booking,
+// in key order: the alleles of job->ref.al, then pos, then obs in state order.  The runs come back as two families: family A (below 2^57)
+// holds per (site, state, strand, mate, d, uniq) the bookings, family B per (site, state, orient, dStart, dEnd) one run per distinct
+// template; both ascend by (site, state), so one pass over each folds them into lines.  nearEnd: bookings with d < nearEnd count as near_end
+static bool analyzerSupport(t1k_job *job, const std::string &prefix, const AnalyzerVariants &V, const AnalyzerSitepile &sp, const AnalyzerSiteList &L, int nearEnd) {
+  const double t0 = nowMs();
+  const RefSet &R = job->ref;
+  const size_t A = R.seqs.size(), nSites = L.sites.size();
+  t1k_ctx *ctx = job->ctx;
+  auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
+  int rc;
+  double msKernels = 0, msFold = 0;
+  uint64_t nRecs = 0, nBook = 0, nRuns = 0, emitted = 0, folds = 0;
+  std::vector<uint64_t> keys;
+  std::vector<int32_t> counts;
+  if (nSites) {
+    if ((rc = t1k_support_begin(ctx, (uint32_t)A, L.refOff.data(), nSites, L.siteAllele.data(), L.sitePos.data())) != T1K_OK) return fail(rc);
+    for (const AnalyzerSitepile::Piece &pc : sp.pieces) {
+      double ms = 0;
+      if ((rc = t1k_support_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), pc.supRec.data(), pc.supBookPtr.data(), pc.supBook.data(), pc.pat.data(), pc.pat.size(),
+                                V.ops.data() + pc.ops0, pc.ops1 - pc.ops0, &ms)) != T1K_OK) {
+        fail(rc);
+        t1k_support_end(ctx);
+        return false;
+      }
+      msKernels += ms;
+      nRecs += pc.recs.size();
+      nBook += pc.supBook.size();
+    }
+    if ((rc = t1k_support_get(ctx, nullptr, nullptr, 0, &nRuns)) == T1K_OK && nRuns) {
+      keys.resize(nRuns); counts.resize(nRuns);
+      rc = t1k_support_get(ctx, keys.data(), counts.data(), nRuns, &nRuns);
+    }
+    if (rc == T1K_OK) rc = t1k_support_stats(ctx, &emitted, &folds, &msFold);
+    if (rc != T1K_OK) { fail(rc); t1k_support_end(ctx); return false; }
+    if ((rc = t1k_support_end(ctx)) != T1K_OK) return fail(rc);
+  }
+  const double tw = nowMs();
+  FILE *fp = fopen((prefix + "_allele_support.tsv").c_str(), "w");
+  if (!fp) { fprintf(stderr, "analyzer: cannot write %s_allele_support.tsv\n", prefix.c_str()); return false; }
+  fputs(kSupportHeader, fp);
+  static const char *kObs[7] = {"A", "C", "G", "T", "N", "-", "+"};
+  const uint64_t familyB = 1ull << 57;
+  const size_t nA = std::lower_bound(keys.begin(), keys.end(), familyB) - keys.begin();
+  std::string out;
+  char num[160];
+  uint64_t lines = 0;
+  size_t b = nA;
+  std::vector<int64_t> hist(512);
+  for (size_t i = 0; i < nA;) {
+    const uint64_t cell = keys[i] >> 12;  // site * 7 + state: its family-A runs are consecutive
+    int64_t all = 0, uniq = 0, strand[2] = {0, 0}, mate[2] = {0, 0};
+    std::fill(hist.begin(), hist.end(), 0);
+    for (; i < nA && (keys[i] >> 12) == cell; ++i) {
+      const int64_t c = counts[i];
+      all += c;                                               // a uniq booking counts in the plain counter as well
+      if ((keys[i] & 1) == 0) uniq += c;
+      strand[(keys[i] >> 11) & 1] += c;
+      mate[(keys[i] >> 10) & 1] += c;
+      hist[(keys[i] >> 1) & 511] += c;
+    }
+    int64_t templates = 0;                                    // its family-B runs: one per distinct template
+    for (; b < keys.size() && ((keys[b] ^ familyB) >> 25) < cell; ++b) {}
+    for (; b < keys.size() && ((keys[b] ^ familyB) >> 25) == cell; ++b) ++templates;
+    int endMin = -1, endMed = -1;
+    int64_t cum = 0, near = 0;
+    for (int d = 0; d < 512; ++d) {
+      if (!hist[d]) continue;
+      if (endMin < 0) endMin = d;
+      if (d < nearEnd) near += hist[d];
+      cum += hist[d];
+      if (endMed < 0 && 2 * cum >= all) endMed = d;           // the lower median: the first d whose cumulative count reaches ceil(all / 2)
+    }
+    const uint64_t site = cell / 7;
+    const uint32_t a = L.siteAllele[site], pos = L.sitePos[site];
+    ++lines;
+    out += R.al[a].name;
+    snprintf(num, sizeof num, "\t%u\t", pos + 1);
+    out += num;
+    out += L.exonPos[site] ? std::to_string(L.exonPos[site]) : std::string(".");
+    out += '\t';
+    out += R.seqs[a][pos];
+    out += '\t';
+    auto it = L.varOf.find(L.sites[site]);
+    out += it == L.varOf.end() ? std::string(".") : it->second;
+    out += '\t';
+    out += kObs[cell % 7];
+    snprintf(num, sizeof num, "\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%d\t%d\t%lld\t%lld\n", (long long)all, (long long)uniq, (long long)strand[0], (long long)strand[1], (long long)mate[0],
+             (long long)mate[1], endMin, endMed, (long long)near, (long long)templates);
+    out += num;
+    if (out.size() >= (1u << 20)) { fwrite(out.data(), 1, out.size(), fp); out.clear(); }
+  }
+  fwrite(out.data(), 1, out.size(), fp);
+  fclose(fp);
+  if (getenv("T1K_DEBUG_PHASES"))
+    fprintf(stderr, "site support: %zu sites, %llu records, %llu bookings, %llu keys emitted, %llu folds, %llu runs, %llu lines; upload %.1f ms, kernels %.1f ms, fold %.1f ms, write %.1f ms\n",
+            nSites, (unsigned long long)nRecs, (unsigned long long)nBook, (unsigned long long)emitted, (unsigned long long)folds, (unsigned long long)nRuns, (unsigned long long)lines,
             std::max(0.0, (tw - t0) - msKernels - msFold), msKernels, msFold, nowMs() - tw);
   return true;
 }
@@ -1109,7 +1246,10 @@ static const char *kAnalyzerUsage =
     "\t\tshow both, by what they show there (A C G T N or - for a deletion): read-backed phasing of the variants\n"
     "\t--sam: also write prefix_aligned.sam, the alignments the variant pass holds as SAM records on the selected alleles (CIGAR, NM, MD, NH, HI), one line per\n"
     "\t\taligned read-end of every assignment of every assigned fragment (no counterpart in the reference)\n"
-    "\t--sites FILE: more sites for --barcodePileup and --phase, one per line as allele_name<TAB>pos (1-based, the pos column of prefix_allele_pileup.tsv); '#' lines,\n"
+    "\t--siteSupport: also write prefix_allele_support.tsv, for the positions of prefix_allele.vcf and of --sites one line per observed base, deletion (-) or\n"
+    "\t\tinserted base (+): the bookings of --pileup there by strand, by mate, by distance from the read-end's nearer end, and the distinct templates behind them\n"
+    "\t--supportEnd INT: bookings fewer than INT bases from an end of their read-end count in the near_end column of --siteSupport, 0 .. 511 (default: 10)\n"
+    "\t--sites FILE: more sites for --barcodePileup and --phase, and for --siteSupport, one per line as allele_name<TAB>pos (1-based, the pos column of prefix_allele_pileup.tsv); '#' lines,\n"
     "\t\tblank lines and alleles that are not selected are skipped\n"
     "\t--relaxIntronAlign: allow one more mismatch in intronic alignment\n"
     "\t--alleleDigitUnits INT, --alleleDelimiter CHR: as in genotyper\n"
@@ -1122,16 +1262,18 @@ int t1k_analyzer_main(int argc, char **argv) {
                                      {"alleleDelimiter", required_argument, 0, 10006}, {"varMaxGroup", required_argument, 0, 10007}, {"device", required_argument, 0, 10010},
                                      {"barcodeEM", no_argument, 0, 10011}, {"barcodeEMPrior", required_argument, 0, 10012}, {"umi", required_argument, 0, 10013},
                                      {"umiMismatch", required_argument, 0, 10014}, {"pileup", no_argument, 0, 10015}, {"barcodePileup", no_argument, 0, 10016},
-                                     {"sites", required_argument, 0, 10017}, {"phase", no_argument, 0, 10018}, {"sam", no_argument, 0, 10019}, {0, 0, 0, 0}};
+                                     {"sites", required_argument, 0, 10017}, {"phase", no_argument, 0, 10018}, {"sam", no_argument, 0, 10019},
+                                     {"siteSupport", no_argument, 0, 10020}, {"supportEnd", required_argument, 0, 10021}, {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
   std::string refFile, alleleFile, prefix = "t1k", barcode;
   std::vector<const char *> f1, f2, single;
   int varMaxGroup = 8;  // Analyzer.cpp:251
-  bool barcodeEM = false, pileup = false, barcodePileup = false, phase = false, samOut = false;
+  bool barcodeEM = false, pileup = false, barcodePileup = false, phase = false, samOut = false, siteSupport = false;
   double emPrior = 0;
-  const char *emPriorText = nullptr, *umiMismatchText = nullptr;
+  const char *emPriorText = nullptr, *umiMismatchText = nullptr, *supportEndText = nullptr;
+  int supportEnd = 10;
   std::string umiPath, sitesPath;
   int umiMismatch = 1;
   optind = 1;
@@ -1162,6 +1304,8 @@ int t1k_analyzer_main(int argc, char **argv) {
       case 10017: sitesPath = optarg; break;
       case 10018: phase = true; break;
       case 10019: samOut = true; break;
+      case 10020: siteSupport = true; break;
+      case 10021: supportEndText = optarg; break;
       default: fprintf(stderr, "%s", kAnalyzerUsage); return EXIT_FAILURE;
     }
   }
@@ -1177,7 +1321,13 @@ int t1k_analyzer_main(int argc, char **argv) {
   }
   if (!umiPath.empty() && barcode.empty()) { fprintf(stderr, "--umi needs --barcode.\n"); return EXIT_FAILURE; }
   if (barcodePileup && barcode.empty()) { fprintf(stderr, "--barcodePileup needs --barcode.\n"); return EXIT_FAILURE; }
-  if (!sitesPath.empty() && !barcodePileup && !phase) { fprintf(stderr, "--sites has no meaning without --barcodePileup or --phase: ignored.\n"); sitesPath.clear(); }
+  if (!sitesPath.empty() && !barcodePileup && !phase && !siteSupport) { fprintf(stderr, "--sites has no meaning without --barcodePileup, --phase or --siteSupport: ignored.\n"); sitesPath.clear(); }
+  if (supportEndText) {
+    char *end = nullptr;
+    const long v = strtol(supportEndText, &end, 10);
+    if (end == supportEndText || *end || !isdigit((unsigned char)supportEndText[0]) || v < 0 || v > 511) { fprintf(stderr, "--supportEnd needs an integer from 0 to 511.\n"); return EXIT_FAILURE; }
+    supportEnd = (int)v;
+  }
   if (umiMismatchText) {
     if (strcmp(umiMismatchText, "0") && strcmp(umiMismatchText, "1")) { fprintf(stderr, "--umiMismatch needs 0 or 1.\n"); return EXIT_FAILURE; }
     umiMismatch = atoi(umiMismatchText);
@@ -1236,6 +1386,12 @@ int t1k_analyzer_main(int argc, char **argv) {
       fputs(kPhaseHeader, fs);
       fclose(fs);
     }
+    if (siteSupport) {
+      FILE *fs = fopen((prefix + "_allele_support.tsv").c_str(), "w");
+      if (!fs) { fprintf(stderr, "analyzer: cannot write %s_allele_support.tsv\n", prefix.c_str()); return EXIT_FAILURE; }
+      fputs(kSupportHeader, fs);
+      fclose(fs);
+    }
     if (samOut) {
       AnalyzerSam sam;
       if (!analyzerSamOpen(nullptr, prefix, sam) || !analyzerSamClose(sam)) return EXIT_FAILURE;
@@ -1251,8 +1407,8 @@ int t1k_analyzer_main(int argc, char **argv) {
     return EXIT_FAILURE;
   }
   job->analyzer = true;
-  std::unique_ptr<AnalyzerSitepile> sp(barcodePileup || phase ? new AnalyzerSitepile : nullptr);
-  if (sp) { sp->barcodes = barcodePileup; sp->phase = phase; }
+  std::unique_ptr<AnalyzerSitepile> sp(barcodePileup || phase || siteSupport ? new AnalyzerSitepile : nullptr);
+  if (sp) { sp->barcodes = barcodePileup; sp->phase = phase; sp->support = siteSupport; }
   if (sp && !sitesPath.empty() && !analyzerReadSites(job, sitesPath, *sp)) { t1k_job_destroy(job); return EXIT_FAILURE; }
   const bool paired = !f2.empty();
   const std::vector<const char *> &first = !f1.empty() ? f1 : single;
@@ -1295,7 +1451,7 @@ int t1k_analyzer_main(int argc, char **argv) {
     logLine("Finish allele quantification in %d EM iterations.", V.emIterations);
   } else if (pileup || sam || (sp && !sp->fileSites.empty())) {
     // no variant is called, but the pileup is of the alignments of steps (1) - (3): they run, VariantCaller does not (V.vc stays empty: the
-    // VCF is the empty file and the per-barcode table counts the raw lists).  --barcodePileup and --phase without sites of their own have nothing to book.
+    // VCF is the empty file and the per-barcode table counts the raw lists).  --barcodePileup, --phase and --siteSupport without sites of their own have nothing to book.
     rc = analyzerAlignAssignments(job, V, pile.get(), sp.get(), sam.get());
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
   } else if (barcodeEM && emPrior > 0) {
@@ -1326,6 +1482,7 @@ int t1k_analyzer_main(int argc, char **argv) {
     const AnalyzerSiteList siteList(job, V, *sp);
     if (barcodePileup && !analyzerSitepile(job, prefix, V, *sp, siteList, names)) { t1k_job_destroy(job); return EXIT_FAILURE; }
     if (phase && !analyzerPhase(job, prefix, V, *sp, siteList)) { t1k_job_destroy(job); return EXIT_FAILURE; }
+    if (siteSupport && !analyzerSupport(job, prefix, V, *sp, siteList, supportEnd)) { t1k_job_destroy(job); return EXIT_FAILURE; }
     sp.reset();
   }
   if (in.hasBarcode) {

@@ -1017,6 +1017,12 @@ struct t1k_ctx {
   T1kDevBuf bSpIn;
   bool spOpen = false;
   uint64_t spBarcodes = 0;
+  // strand / mate / end-distance / template support at sites (t1k_support.hip), open from t1k_support_begin to _end: its sites, its one
+  // table of both key families and the staging block of one _add call
+  T1kSiteMap supMap;
+  T1kCountTable supTab;
+  T1kDevBuf bSupIn;
+  bool supOpen = false;
   // read-backed phasing of site pairs (t1k_phase.hip), open from t1k_phase_begin to _end: its sites, its table of (site pair, state pair,
   // uniq) cells, the staging block of one _add call, that call's observation words and merge arena, and what _stats reports
   T1kSiteMap phMap;

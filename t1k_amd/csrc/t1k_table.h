@@ -1,4 +1,4 @@
-// t1k_amd/csrc/t1k_table.h -- internal: the two pieces the sparse analyzer stages share (t1k_sitepile.hip; t1k_phase.hip, §11.5);
+// t1k_amd/csrc/t1k_table.h -- internal: the two pieces the sparse analyzer stages share (t1k_sitepile.hip; t1k_phase.hip, §11.5; t1k_support.hip, §11.7);
 // the types live in t1k_dev.h (the context holds them), the host side in t1k_table.hip.
 // T1kSiteMap: a set of (allele, position) sites as a bitmap over the allele-offset space (bit alleleOff[a] + p) and a rank directory (sites
 // in front of each 64-bit word): a lane maps its allele position to a site index with one bit test and one population count.

@@ -1,5 +1,5 @@
 // t1k_amd/csrc/t1k_table.hip -- the host side of t1k_table.h: the site map's builder and the sparse count table's reserve / fold / read,
-// shared by t1k_sitepile.hip and t1k_phase.hip.
+// shared by t1k_sitepile.hip, t1k_support.hip and t1k_phase.hip.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>

@@ -1,4 +1,4 @@
-// t1k_amd/csrc/t1k_walk.h -- internal: what k_pileup (t1k_pileup.hip), k_sitepile (t1k_sitepile.hip), k_phase_obs (t1k_phase.hip) and k_cigar_size /
+// t1k_amd/csrc/t1k_walk.h -- internal: what k_pileup (t1k_pileup.hip), k_sitepile (t1k_sitepile.hip), k_support (t1k_support.hip), k_phase_obs (t1k_phase.hip) and k_cigar_size /
 // k_cigar_emit (t1k_cigar.hip) share, on both sides of the launch.
 // Device: the record header of a wave (pileupLoadRec), the edit-string walk of one alignment by one wave64 (pileupWalk) and the verdict on
 // where it ended (pileupWalkVerdict).  64 edit columns per step.  A lane's allele coordinate is seq_start + the non-insert ops before it, its
@@ -14,7 +14,7 @@
 #include "t1k_launch.h"
 
 enum { PILEUP_PLANES = 14, PILEUP_N = 4, PILEUP_DEL = 5, PILEUP_INS = 6, PILEUP_UNIQ = 7 };
-enum { PILEUP_BAD_OP = 1, PILEUP_BAD_ALLELE_WALK = 2, PILEUP_BAD_TEXT_WALK = 4 };
+enum { PILEUP_BAD_OP = 1, PILEUP_BAD_ALLELE_WALK = 2, PILEUP_BAD_TEXT_WALK = 4, PILEUP_BAD_READ_WINDOW = 8 };  // (the last: k_support's own check)
 
 __device__ __forceinline__ uint32_t pileupUniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ unsigned long long pileupUniform64(unsigned long long v) {
@@ -138,5 +138,5 @@ static inline int pileupStage(t1k_ctx *ctx, T1kDevBuf &buf, uint64_t opsBytes, E
 // the message of a batch whose check walk came back with `flag` set; verb: what did not happen ("nothing booked")
 static inline std::string pileupRefusal(const char *who, const char *verb, uint32_t flag) {
   return std::string(who) + ": " + verb + ":" + ((flag & PILEUP_BAD_OP) ? " an op outside 0 .. 3;" : "") + ((flag & PILEUP_BAD_ALLELE_WALK) ? " a walk leaves its allele;" : "") +
-         ((flag & PILEUP_BAD_TEXT_WALK) ? " a walk leaves `text`;" : "");
+         ((flag & PILEUP_BAD_TEXT_WALK) ? " a walk leaves `text`;" : "") + ((flag & PILEUP_BAD_READ_WINDOW) ? " a read window leaves its read;" : "");
 }
