@@ -522,6 +522,35 @@ typedef struct {
   double ms_load, ms_device, ms_coalesce, ms_write;
 } t1k_stats;
 int t1k_stats_get(t1k_ctx *ctx, t1k_stats *out);
+
+/* ---- route report: which kernel chained each group (diagnostics and tests) -----------------------------------------
+ * Off by default, and then t1k_assign_range issues exactly the launches and copies it issues without it.  t1k_route_report_enable(ctx, 1)
+ * clears the report and starts it; (ctx, 0) stops it and drops what it held.  While it is on, every range that t1k_assign_range
+ * finishes adds its totals and one record per multi-diagonal group; a range that ran again after a capacity error counts once, from the
+ * pass that was kept.  The records cost one copy of the general list, the big list and the listed group records per range.
+ * totals: arena totals of the kept passes (work-list lengths, not kernel launches) and T1K_STAT_FAST; eq / band / wide are the
+ * alignment queues of t1k_assign_range's own full alignments (0 with deferred coverage and no relax_intron_align).
+ * t1k_route_report_get: *nRecs = the records held; with recs given (cap >= *nRecs) they are copied out, in the order of the ranges. */
+enum { T1K_ROUTE_GENERAL_LANE = 0,    /* k_chain_general: n <= 32, or simple and n <= 96 */
+       T1K_ROUTE_WAVE_SMALL = 1,      /* k_chain_wave, first launch: n <= 512 */
+       T1K_ROUTE_WAVE_LARGE = 2,      /* k_chain_wave, second launch: n <= 4096 */
+       T1K_ROUTE_BIG_BY_SIZE = 3,     /* k_chain_big, more than 4096 hits (n is not kept by the kernels: 0xFFFFFFFF) */
+       T1K_ROUTE_BIG_BY_SCRATCH = 4,  /* k_chain_big after the lane / wavefront met a gap beyond the register band */
+       T1K_ROUTE_KINDS = 5 };
+typedef struct {
+  uint64_t ranges, ranges_nw5, ranges_nw10, ranges_xlong;  /* kept passes, by the instantiation of the chain kernels (xlong: also counted under its NW) */
+  uint64_t groups, fast, slow, jobs, retry, finish, general, wave, genjobs, big, eq, band, wide, extjobs, extretry;
+} t1k_route_totals;
+typedef struct {
+  uint32_t read_end, allele, n;   /* read-end index in the uploaded set; hits of the group (record word 4) */
+  uint8_t strand;                 /* 0: the read-end as given, 1: its reverse complement */
+  uint8_t near_done, simple;      /* k_near_hits wrote the hit list; ... and marked it a two-diagonal chain */
+  uint8_t route;                  /* T1K_ROUTE_* */
+  uint8_t nw, xlong, reserved[2]; /* 5 / 10; 1: the range held read-ends beyond 320 bases (k_near_hits did not run) */
+} t1k_route_rec;
+int t1k_route_report_enable(t1k_ctx *ctx, int on);
+int t1k_route_report_get(t1k_ctx *ctx, t1k_route_totals *totals /* may be NULL */, t1k_route_rec *recs /* may be NULL */, uint64_t cap, uint64_t *nRecs);
+
 /* wall time (ms) the context has spent allocating device memory and the bytes it asked for (diagnostics) */
 double t1k_alloc_ms(t1k_ctx *ctx, uint64_t *bytes);
 /* the device blocks the context holds right now, in bytes; print != 0: one line on stderr naming every block of 64 MB and more (diagnostics, T1K_DEBUG_MEM) */

@@ -76,6 +76,13 @@ SUPPORT_BOOK_DTYPE = np.dtype([("flags", "<u4"), ("t_start", "<u4"), ("t_end", "
 SUPPORT_STATES = ("A", "C", "G", "T", "N", "-", "+")
 SUPPORT_FAMILY_B = 1 << 57
 assert SUPPORT_REC_DTYPE.itemsize == 12 and SUPPORT_BOOK_DTYPE.itemsize == 12
+# t1k_route_totals / t1k_route_rec / T1K_ROUTE_* (route report)
+ROUTE_TOTALS = ("ranges", "ranges_nw5", "ranges_nw10", "ranges_xlong", "groups", "fast", "slow", "jobs", "retry", "finish", "general", "wave", "genjobs", "big",
+                "eq", "band", "wide", "extjobs", "extretry")
+ROUTE_REC_DTYPE = np.dtype([("read_end", "<u4"), ("allele", "<u4"), ("n", "<u4"), ("strand", "u1"), ("near_done", "u1"), ("simple", "u1"), ("route", "u1"),
+                            ("nw", "u1"), ("xlong", "u1"), ("reserved", "u1", (2,))])
+ROUTE_NAMES = ("general_lane", "wave_small", "wave_large", "big_by_size", "big_by_scratch")
+assert ROUTE_REC_DTYPE.itemsize == 20
 CIGAR_FILL = 0xAB  # what Context.cigar_batch fills its output arrays with before the call
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_void_p)
@@ -144,6 +151,8 @@ def lib():
     L.t1k_extract_batch.argtypes = [vp, C.c_uint32, vp, vp]
     L.t1k_extractor_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_stats_get.argtypes = [vp, C.POINTER(Stats)]
+    L.t1k_route_report_enable.argtypes = [vp, C.c_int]
+    L.t1k_route_report_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
     L.t1k_genotyper_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_job_params_default.argtypes = [C.POINTER(JobParams)]
     L.t1k_job_create.argtypes = [C.POINTER(JobParams), C.c_char_p, C.POINTER(vp)]
@@ -390,6 +399,19 @@ class Context:
         s = Stats()
         lib().t1k_stats_get(self.h, C.byref(s))
         return s.as_dict()
+
+    def route_report_enable(self, on=True):
+        """starts (and clears) or stops the route report (t1k_route_report_enable)"""
+        self._check(lib().t1k_route_report_enable(self.h, 1 if on else 0), "t1k_route_report_enable")
+
+    def route_report(self):
+        """(totals dict, records as ROUTE_REC_DTYPE) of the ranges finished since route_report_enable(); ROUTE_NAMES[rec["route"]] names the kernel"""
+        n = C.c_uint64()
+        self._check(lib().t1k_route_report_get(self.h, None, None, 0, C.byref(n)), "t1k_route_report_get")
+        tot = np.zeros(len(ROUTE_TOTALS), np.uint64)
+        recs = np.zeros(n.value, ROUTE_REC_DTYPE)
+        self._check(lib().t1k_route_report_get(self.h, _ptr(tot), _ptr(recs), n.value, C.byref(n)), "t1k_route_report_get")
+        return dict(zip(ROUTE_TOTALS, (int(x) for x in tot))), recs
 
     def align_batch(self, texts, pats, want_ops=True):
         n = len(texts)

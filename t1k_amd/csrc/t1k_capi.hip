@@ -821,6 +821,27 @@ int t1k_assign_batch(t1k_ctx *ctx) {
 
 static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count);
 
+// Route report: the range ended well, so its last pass is the one that counts.  The counter block is cleared once per pass and fetched
+// last at the range's end, so the cursors of every work list the pass filled are in the host's copy of it (no overflow: a cursor is
+// the list's length).
+static void routeCommit(t1k_ctx *ctx) {
+  auto &rr = ctx->route;
+  if (ctx->hRaw.size() < T1K_COUNTER_WORDS) return;
+  auto total = [&](int arena) {
+    uint64_t t = 0;
+    for (int s = 0; s < T1K_NSTRIPE; ++s) t += ctx->hRaw[T1K_ARENA_BASE + ((size_t)arena * T1K_NSTRIPE + s) * T1K_STRIPE_WORDS];
+    return t;
+  };
+  t1k_route_totals &k = rr.kept;
+  ++k.ranges; ++(rr.passLong ? k.ranges_nw10 : k.ranges_nw5); k.ranges_xlong += rr.passXlong ? 1 : 0;
+  k.groups += total(T1K_AR_GROUPS); k.slow += total(T1K_AR_SLOW); k.jobs += total(T1K_AR_JOBS); k.retry += total(T1K_AR_RETRY); k.finish += total(T1K_AR_FINISH);
+  k.general += total(T1K_AR_GENERAL); k.wave += total(T1K_AR_WAVE); k.genjobs += total(T1K_AR_GENJOBS); k.big += total(T1K_AR_BIG);
+  k.eq += total(T1K_AR_EQ); k.band += total(T1K_AR_BAND); k.wide += total(T1K_AR_WIDE); k.extjobs += total(T1K_AR_EXTJOBS); k.extretry += total(T1K_AR_EXTRETRY);
+  for (int s = 0; s < T1K_STAT_STRIPES; ++s) k.fast += ctx->hRaw[64 + s * 8 + T1K_STAT_FAST];
+  rr.keptRecs.insert(rr.keptRecs.end(), rr.passRecs.begin(), rr.passRecs.end());
+  rr.passRecs.clear();
+}
+
 // Working capacities.  t1k_params holds the LIMITS of the batch arenas; what is allocated follows the demand: the first range
 // starts from a floor per read-end, an overflow (always detected before anything of the range is committed) raises the working
 // capacity to the demand the device counted and the range runs again.  Fresh VRAM costs about 35 ms per GB on this platform
@@ -855,6 +876,7 @@ int t1k_assign_range(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   for (int attempt = 0;; ++attempt) {
     ctx->lastCapFlags = 0; ctx->needGroup = ctx->needCand = ctx->needOvl = ctx->needList = ctx->needRare = ctx->needJob = ctx->needGenJob = ctx->needGenHit = 0;
     const int rc = assignOnce(ctx, first, count);
+    if (ctx->route.on && rc == T1K_OK && count) routeCommit(ctx);  // (opt-in: the pass that was kept, once)
     if (rc != T1K_ERR_CAPACITY || attempt >= 10) return rc;
     bool grew = false;
     auto grow = [&](uint64_t &w, uint64_t need, int64_t limit) {  // to the demand the device counted, with a quarter to spare
@@ -1181,6 +1203,26 @@ double t1k_alloc_ms(t1k_ctx *ctx, uint64_t *bytes) {  // time this context has s
 int t1k_stats_get(t1k_ctx *ctx, t1k_stats *out) {
   if (!ctx || !out) return T1K_ERR_ARG;
   *out = ctx->stats;
+  return T1K_OK;
+}
+
+int t1k_route_report_enable(t1k_ctx *ctx, int on) {
+  if (!ctx) return T1K_ERR_ARG;
+  ctx->route.on = on != 0;
+  ctx->route.kept = t1k_route_totals{};
+  ctx->route.keptRecs.clear(); ctx->route.passRecs.clear();
+  return T1K_OK;
+}
+
+int t1k_route_report_get(t1k_ctx *ctx, t1k_route_totals *totals, t1k_route_rec *recs, uint64_t cap, uint64_t *nRecs) {
+  if (!ctx || !nRecs) return T1K_ERR_ARG;
+  if (!ctx->route.on) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_route_report_get: the route report is off (t1k_route_report_enable)");
+  *nRecs = ctx->route.keptRecs.size();
+  if (totals) *totals = ctx->route.kept;
+  if (recs) {
+    if (cap < *nRecs) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_route_report_get: room for " + std::to_string(cap) + " records, " + std::to_string(*nRecs) + " held");
+    if (*nRecs) memcpy(recs, ctx->route.keptRecs.data(), *nRecs * sizeof(t1k_route_rec));
+  }
   return T1K_OK;
 }
 

@@ -1479,6 +1479,58 @@ uint64_t t1k_arena_estimate(const t1k_ctx *ctx, int arena, uint64_t cap, uint32_
 void t1k_arena_estimate_set(t1k_ctx *ctx, int arena, uint64_t total, uint32_t nRe) { ctx->estTotal[arena] = (total << 16) / std::max(1u, nRe) + 1; }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Route report (t1k_route_report_enable): one record per multi-diagonal group of the pass that has just ended, classified from the words the
+// kernels left in its record -- word 4 = hits (0xFFFFFFFF: k_gather_general handed the group to k_chain_big by size), word 5 ==
+// REC_NEAR_DONE and word 6 == 1 (k_near_hits; in an xlong range it did not run and the words still hold mask bits) -- and from the
+// big list (a group on it that has a hit count came from a lane or a wavefront that met a gap beyond the register band).  Host only: it
+// reads what is there after the range's counter fetch (the stream is idle), before the records' memory is used again.
+// ------------------------------------------------------------------------------------------------------------------
+static int routeCollect(t1k_ctx *ctx, const ChainArgs &a, bool longReads, bool xlong, uint64_t nGen, uint64_t nBig) {
+  auto &rr = ctx->route;
+  rr.passRecs.clear();
+  rr.passLong = longReads; rr.passXlong = xlong;
+  if (!nGen) return 0;
+  std::vector<uint32_t> gen(nGen), big(nBig);
+  T1K_HIP(ctx, hipMemcpy(gen.data(), a.generalList, nGen * 4, hipMemcpyDeviceToHost));
+  if (nBig) T1K_HIP(ctx, hipMemcpy(big.data(), a.bigList, nBig * 4, hipMemcpyDeviceToHost));
+  std::sort(big.begin(), big.end());
+  // the listed records: the group arena is dense inside each stripe, so the sorted ids fall into a few runs; each run is one copy
+  std::vector<uint32_t> ids(gen);
+  std::sort(ids.begin(), ids.end());
+  if (ids.back() >= a.groupCap) return t1k_fail(ctx, T1K_ERR_INTERNAL, "route report: a listed group lies outside the group arena");
+  const uint32_t stride = a.recStride;
+  std::vector<uint32_t> words((size_t)nGen * 8);  // words 0 .. 7 of each listed record, in the order of `ids`
+  std::vector<uint32_t> buf;
+  for (size_t s = 0; s < ids.size();) {
+    size_t e = s + 1;
+    while (e < ids.size() && ids[e] - ids[e - 1] <= 4096u && (uint64_t)(ids[e] - ids[s] + 1) * stride <= (64u << 20)) ++e;
+    const uint64_t span = (uint64_t)(ids[e - 1] - ids[s] + 1) * stride;
+    buf.resize(span);
+    T1K_HIP(ctx, hipMemcpy(buf.data(), a.recs + (uint64_t)ids[s] * stride, span * 4, hipMemcpyDeviceToHost));
+    for (size_t i = s; i < e; ++i) std::copy_n(&buf[(uint64_t)(ids[i] - ids[s]) * stride], 8, &words[i * 8]);
+    s = e;
+  }
+  const uint64_t first = (uint64_t)(a.reads.len - ctx->reads.len);  // the range's first read-end in the uploaded set
+  rr.passRecs.reserve(nGen);
+  for (uint64_t q = 0; q < nGen; ++q) {
+    const size_t at = std::lower_bound(ids.begin(), ids.end(), gen[q]) - ids.begin();
+    const uint32_t *r = &words[at * 8];
+    t1k_route_rec o{};
+    o.read_end = (uint32_t)(first + (r[0] & 0x7FFFFFFFu)); o.allele = r[1]; o.n = r[4];
+    o.strand = (r[0] >> 31) ? 0 : 1;
+    o.near_done = !xlong && r[5] == REC_NEAR_DONE;
+    o.simple = o.near_done && r[6] == 1u;
+    o.nw = longReads ? 10 : 5; o.xlong = xlong ? 1 : 0;
+    if (r[4] == 0xFFFFFFFFu) o.route = T1K_ROUTE_BIG_BY_SIZE;
+    else if (std::binary_search(big.begin(), big.end(), gen[q])) o.route = T1K_ROUTE_BIG_BY_SCRATCH;
+    else if (o.n <= GENERAL_SMALL || (o.simple && o.n <= 3 * GENERAL_SMALL)) o.route = T1K_ROUTE_GENERAL_LANE;
+    else o.route = o.n <= 512u ? T1K_ROUTE_WAVE_SMALL : T1K_ROUTE_WAVE_LARGE;
+    rr.passRecs.push_back(o);
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The chain of one range as ONE submission (round 5).  Rounds 1-4 fetched the counter block six times per range -- after seeding, after
 // the closed-form pass, after the gap walk, twice inside the multi-diagonal path, at the end -- because every consumer's grid and item
 // count were launch arguments.  Here every consumer reads its item count on the device (the total word k_arena_compact leaves where it
@@ -1572,6 +1624,11 @@ int t1k_run_chain(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBlocks, bo
     const int ar[] = {T1K_AR_GROUPS, T1K_AR_SLOW, T1K_AR_JOBS, T1K_AR_RETRY, T1K_AR_GENERAL, T1K_AR_WAVE, T1K_AR_GENJOBS, T1K_AR_BIG};
     for (int i = 0; i < 8; ++i) t1k_arena_estimate_set(ctx, ar[i], cs[i]->total, nRe);
     ctx->estValid = true;
+  }
+  if (ctx->route.on) {  // (opt-in: nothing above depends on it)
+    ctx->route.passRecs.clear();
+    if (!hc[2])
+      if (const int rc = routeCollect(ctx, a, longReads, xlong, gen.total, big.total)) return rc;
   }
   return 0;
 }

@@ -993,6 +993,8 @@ struct t1k_ctx {
   uint64_t lastSlowGroups = 0;             // groups the last range left to the gap walk (T1K_DEBUG_PHASES)
   uint64_t estTotal[T1K_NARENA] = {};      // entries per arena the last range of this context ended with, per read-end x 2^16: the next range's launch grids (t1k_run_chain)
   bool estValid = false;
+  // route report (t1k_route_report_enable): `pass` is what the running pass of a range has collected, moved to `kept` when the range ends well
+  struct { bool on = false; t1k_route_totals kept{}; std::vector<t1k_route_rec> keptRecs, passRecs; bool passLong = false, passXlong = false; } route;
   uint64_t pairEpoch = 0;      // epochs handed out to k_pair's allele tables since they were last cleared
   uint64_t pairBigCap = 0;     // entries of k_pair's big arena (scratch of the fragments whose lists exceed a workgroup's own)
   unsigned long long *countersPinned = nullptr;  // page-locked landing buffer of t1k_fetch_counters
