@@ -5,8 +5,10 @@
 //   (seeding / hit grouping / chaining / strand vote: t1k_chain.hip)
 //   k_extend       one lane per candidate: similarity / low-complexity filter (1838-1845, 458-485, 1894-1908),
 //                  separator tests (2163-2169), ExtendOverlap (1994-2100)
+//   k_select_classes  the read-ends of the range by candidate count: one list per size class, each the hand-out of one k_select launch
 //   k_select       one workgroup per read-end: sort by _overlap::operator< (103-127), the onlyConsiderClip latch
-//                  (2156-2186) evaluated in parallel, near-best flags (2192-2200)
+//                  (2156-2186) evaluated in parallel, near-best flags (2192-2200); lists that can be cut decide the latch rule on
+//                  the unsorted list (t1k_select_rule.h) and are sorted once
 //   k_fullalign    one lane per kept overlap: near-best full alignment -> relaxedMatchCnt + base coverage as a
 //                  difference array (2188-2285); alignments that need a real DP traceback go to a queue (k_fullalign_slow)
 //   k_truncate     >1000 overlaps: re-sort and cut at similarity < best - 0.1 (2290-2298)
@@ -15,6 +17,7 @@
 #include "t1k_dev.h"
 #include "t1k_launch.h"
 #include "t1k_memo.h"
+#include "t1k_select_rule.h"
 
 #define WG 256
 #define GA_BIG_MAX 2048
@@ -348,7 +351,6 @@ __device__ inline void ldsCountingPass(uint64_t *key, uint32_t n, uint16_t *cnt,
   const uint32_t seg = (((n + NW - 1) / NW) + 63u) & ~63u;  // entries of one wavefront's piece (<= 512)
   uint64_t kk[ROUNDS];
   uint32_t at[ROUNDS];  // digit << 16 | position inside the piece's run of that digit (0xFFFFFFFF: no entry)
-  const uint64_t ltMask = lane ? (~0ull >> (64 - lane)) : 0ull;
 #pragma unroll
   for (int q = 0; q < ROUNDS; ++q) {
     kk[q] = 0; at[q] = 0xFFFFFFFFu;
@@ -372,7 +374,7 @@ __device__ inline void ldsCountingPass(uint64_t *key, uint32_t n, uint16_t *cnt,
         *c = (uint16_t)(base + (uint32_t)__popcll(m));
       }
       base = (uint32_t)__shfl((int)base, leader, 64);
-      if (valid) at[q] = (r << 16) | (base + (uint32_t)__popcll(m & ltMask));
+      if (valid) at[q] = (r << 16) | (base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)));  // (the lanes of m below this one)
       __builtin_amdgcn_wave_barrier();
     }
   }
@@ -425,9 +427,6 @@ __device__ __forceinline__ bool packSortKey(const KeyW &W, int m, int d, int rsp
 // k_select's entry: [emit mark : 1 | MMAX - seed matchCnt : MB | span sum : DB | RMAX - read span : RB | allele : aBits | index : iBits |
 // flags : 3] (fast windows: 10 / 10 / 9); the flags (separator in the seed, extension passed, "needs clipping and similarity >= 0.95")
 // are all the later phases need to know about a candidate, so they never go back to HBM for it.  The index is unique, so the flags never order.
-#define SEL_F_SEPSEED 1u
-#define SEL_F_EXTOK 2u
-#define SEL_F_KEEPCLIP 4u
 __device__ __forceinline__ bool packSelectKey(const KeyW &W, int m, int d, int rspan, uint32_t allele, uint32_t index, uint32_t flags, int aBits, int iBits, uint64_t *out) {
   const int MMAX = (1 << W.MB) - 1, DMAX = (1 << W.DB) - 1, RMAX = (1 << W.RB) - 1;
   if (m < 0 || m > MMAX || d < 0 || d > DMAX || rspan < 0 || rspan > RMAX || 1 + W.MB + W.DB + W.RB + 3 + aBits + iBits > 64) return false;
@@ -457,17 +456,90 @@ __device__ inline bool candBeforeFull(const T1kCand &a, const T1kCand &b) {
 #define T1K_SELECT_SMALL_WAVES 7
 #endif
 // PK, the packed form (no --relaxIntronAlign, coverage deferred: nothing reads the records between the selection and the cut): the lists
-// are finished here.  A list of more than 1000 emitted overlaps is put into _overlap::operator< order on the extended records and cut
-// (SeqSet.hpp:2290-2298) before anything is written, and the kept records go to the store in their 16-byte form, once.
-template <int SELECT_LDS_CAP, int NT, bool XL, bool PK>
+// are finished here.  A list of more than SELECT_CUT_LEN emitted overlaps is put into _overlap::operator< order on the extended records and
+// cut (SeqSet.hpp:2290-2298) before anything is written, and the kept records go to the store in their 16-byte form, once.
+// CUT: the instantiation holds the cut's code.  A list of at most SELECT_CUT_LEN candidates cannot have more emitted, so the launch that
+// takes those lists is compiled without it (PK && !CUT) and its register allocation is the unpacked form's.
+#define SELECT_CUT_LEN 1000
+// Size classes of the read-ends of a range, by candidate count: 1 .. SELECT_CUT_LEN, .. SELECT_SMALL, beyond.  k_select_classes writes one
+// dense, ascending list of read-ends per class (classList[c * nReadEnds ..], its length in counters[T1K_CTR_SELECT_LEN + c]) and publishes
+// the empty lists of the read-ends without candidates; every selection launch is handed the read-ends of its own class and sees no other.
+#define SELECT_NCLASS 3
+__device__ __forceinline__ int selectClassOf(uint32_t candCount) {
+  return candCount == 0 ? -1 : candCount <= SELECT_CUT_LEN ? 0 : candCount <= SELECT_SMALL ? 1 : 2;
+}
+// One workgroup: every wavefront takes a contiguous piece of the range, counts its classes (ballots), and after one prefix over the
+// wavefronts' counts writes its read-ends behind those of the wavefronts before it -- ascending inside a class, so that neighbouring
+// read-ends' records are in flight together in the selection as they were when every launch walked the whole range.
+__global__ __launch_bounds__(1024) void k_select_classes(SelectArgs P, int packed) {
+  constexpr int NW = 1024 / 64;
+  __shared__ uint32_t sWave[SELECT_NCLASS][NW];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint32_t n = P.reads.nReadEnds;
+  const uint32_t seg = (((n + NW - 1) / NW) + 63u) & ~63u;
+  const uint32_t lo = min((uint32_t)w * seg, n), hi = min(lo + seg, n);
+  const uint64_t ltMask = lane ? (~0ull >> (64 - lane)) : 0ull;
+  uint32_t cnt[SELECT_NCLASS] = {0, 0, 0};
+  for (uint32_t i0 = lo; i0 < hi; i0 += 64) {
+    const uint32_t i = i0 + (uint32_t)lane;
+    const uint32_t c = i < hi ? P.candCount[i] : 0u;
+    const int cls = selectClassOf(c);
+    if (i < hi && c == 0) {  // no candidate: the empty list is published here (a skipped entry comes from an earlier window: t1k_xwin_resolve)
+      P.ovlStart[i] = 0; P.ovlCount[i] = 0;
+      if (packed && !(P.reads.skip && P.reads.skip[i])) { P.listPtr[i] = (unsigned long long)P.store; P.listCount[i] = 0; }
+    }
+#pragma unroll
+    for (int k = 0; k < SELECT_NCLASS; ++k) cnt[k] += (uint32_t)__popcll(__ballot(cls == k));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < SELECT_NCLASS; ++k) sWave[k][w] = cnt[k];
+  }
+  __syncthreads();
+  uint32_t at[SELECT_NCLASS], listed = 0;
+#pragma unroll
+  for (int k = 0; k < SELECT_NCLASS; ++k) {
+    uint32_t base = 0, tot = 0;
+    for (int q = 0; q < NW; ++q) { const uint32_t s = sWave[k][q]; if (q < w) base += s; tot += s; }
+    at[k] = base; listed += tot;
+    if (tid == 0) P.counters[T1K_CTR_SELECT_LEN + k] = tot;
+  }
+#ifdef T1K_SELECT_ROUTES
+  if (tid == 0) P.counters[40] = n - listed;  // route 0: read-ends without a candidate
+#else
+  (void)listed;
+#endif
+  for (uint32_t i0 = lo; i0 < hi; i0 += 64) {
+    const uint32_t i = i0 + (uint32_t)lane;
+    const int cls = i < hi ? selectClassOf(P.candCount[i]) : -1;
+#pragma unroll
+    for (int k = 0; k < SELECT_NCLASS; ++k) {
+      const uint64_t bal = __ballot(cls == k);
+      if (cls == k) P.classList[(size_t)k * n + at[k] + (uint32_t)__popcll(bal & ltMask)] = i;
+      at[k] += (uint32_t)__popcll(bal);
+    }
+  }
+}
+
+// -DT1K_SELECT_ROUTES: read-ends and candidates per route of the selection (no candidate; 1 .. SELECT_CUT_LEN; .. SELECT_SMALL not cut / cut;
+// beyond not cut / cut), counted in counters[40 .. 52) and summed per process (a measurement build: thread 0 pays two atomics per read-end)
+#ifdef T1K_SELECT_ROUTES
+#define T1K_SELECT_ROUTE_COUNT() do { if (tid == 0) { const int r_ = n <= SELECT_CUT_LEN ? 1 : (n <= SELECT_SMALL ? 2 : 4) + (cutList ? 1 : 0); \
+  atomicAdd(&P.counters[40 + 2 * r_], 1ull); atomicAdd(&P.counters[41 + 2 * r_], (unsigned long long)n); } } while (0)
+#else
+#define T1K_SELECT_ROUTE_COUNT() do { } while (0)
+#endif
+
+template <int SELECT_LDS_CAP, int NT, bool XL, bool PK, bool CUT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_CAP == SELECT_SMALL ? T1K_SELECT_SMALL_WAVES : 8))) void k_select(SelectArgs P) {
+  static_assert(PK || !CUT, "only the packed form cuts");
   extern __shared__ uint64_t dynLds[];
   uint64_t *sKey = dynLds;
   __shared__ uint32_t warpSums[NT / 64];
   __shared__ int sLatch, sGood, sBest, sTie;
   __shared__ uint32_t sBase;
   __shared__ CsTables sCs;
-  __shared__ uint16_t sCnt[256 * (NT / 64)];
+  __shared__ __attribute__((aligned(8))) uint16_t sCnt[256 * (NT / 64)];  // (the cut's emit words live here too)
   const int tid = threadIdx.x;
   unsigned int nbTotal = 0;
   unsigned long long emitTotal = 0;  // (thread 0, PK) emitted overlaps before the cut: counters[1] counts the kept ones
@@ -476,43 +548,47 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
     P.ovlStart[re] = start; P.ovlCount[re] = count;
     if (PK && !(P.reads.skip && P.reads.skip[re])) { P.listPtr[re] = (unsigned long long)(P.store + start); P.listCount[re] = count; }  // (a skipped entry comes from an earlier window: t1k_xwin_resolve)
   };
+  // the empty list of an error path.  Its pointer is the store's base, the same for every read-end: as a constant it was copied to a
+  // register pair per lane in front of the read-end loop and spilled there (8 of the packed form's bytes of scratch); behind the empty
+  // statement it is formed where it is stored
+  auto publishEmpty = [&](uint32_t re) {
+    P.ovlStart[re] = 0; P.ovlCount[re] = 0;
+    if (PK && !(P.reads.skip && P.reads.skip[re])) {
+      unsigned long long base = (unsigned long long)P.store;
+      asm volatile("" : "+s"(base));
+      P.listPtr[re] = base; P.listCount[re] = 0;
+    }
+  };
   // read-ends are handed out one at a time (a device counter per launch): their cost is uneven, and a workgroup of this shape that waits
   // for a free CU would otherwise hold up its whole fixed share of them.  (Alone the kernels are 20 - 35 % faster for it; under three
   // pipelines the step is not: what one kernel gives back the others take.  64 at a time with the counts pre-read was slower.)
+  // What is handed out are positions in the launch's own class list (k_select_classes), whose length the device reads.
   __shared__ uint32_t sNextRe;
   uint32_t hoNext = 0, hoLeft = 0;  // thread 0: what it holds from its last hand-out
+  const uint32_t nMine = (uint32_t)P.counters[P.lenWord];
   for (;;) {
     __syncthreads();
     if (tid == 0) {  // (T1K_RE_HANDOUT read-ends per atomic on the hand-out word: round 6)
-      constexpr uint32_t HO = SELECT_LDS_CAP == SELECT_SMALL ? T1K_SELECT_SMALL_HANDOUT : T1K_SELECT_LARGE_HANDOUT;
-      if (hoLeft == 0) { hoNext = (uint32_t)atomicAdd(&P.counters[SELECT_LDS_CAP == SELECT_SMALL ? 28 : 29], (unsigned long long)HO); hoLeft = HO; }
+      constexpr uint32_t HO = SELECT_LDS_CAP == SELECT_SMALL ? (CUT ? T1K_SELECT_MID_HANDOUT : T1K_SELECT_SMALL_HANDOUT) : T1K_SELECT_LARGE_HANDOUT;
+      if (hoLeft == 0) { hoNext = (uint32_t)atomicAdd(&P.counters[P.hoWord], (unsigned long long)HO); hoLeft = HO; }
       sNextRe = hoNext++; --hoLeft;
     }
     __syncthreads();
-    const uint32_t re = sNextRe;
-    if (re >= P.reads.nReadEnds) break;
+    if (sNextRe >= nMine) break;
+    const uint32_t re = P.classList[sNextRe];
     const uint32_t n = P.candCount[re], c0 = P.candStart[re];
-    if (n == 0) {
-      if (tid == 0 && SELECT_LDS_CAP == SELECT_SMALL) publish(re, 0, 0);
-      continue;
-    }
     // every candidate of the list is sorted (the ones that failed the similarity filter were left out by k_collect; until round 4 this
     // kernel -- both instantiations -- swept the extension records once just to count survivors that all survive, each thread over its own
     // contiguous piece).  Candidate i goes to position i: the list keeps the order in which k_collect wrote it (allele order), which the
     // counting sort below relies on, and neighbouring lanes read neighbouring records
-    if ((n > SELECT_SMALL) != (SELECT_LDS_CAP == SELECT_LARGE)) continue;  // the other instantiation's read-end
     const uint32_t live = n;
-    if (live == 0) {
-      if (tid == 0) publish(re, 0, 0);
-      continue;
-    }
     uint32_t np2 = 8;
     while (np2 < live) np2 <<= 1;
     uint64_t *key;
     if (np2 <= SELECT_LDS_CAP) key = sKey;
-    else if (np2 <= P.sortCap) key = P.sortScratch + (uint64_t)blockIdx.x * P.sortCap * 6;
+    else if (SELECT_LDS_CAP == SELECT_LARGE && np2 <= P.sortCap && np2 <= (1u << 15)) key = P.sortScratch + (uint64_t)blockIdx.x * P.sortCap * 6;
     else {
-      if (tid == 0) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); publish(re, 0, 0); }
+      if (tid == 0) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); publishEmpty(re); }
       continue;
     }
     // key: matchCnt desc, similarity desc (== readSpan+seqSpan asc at equal matchCnt), readSpan desc, allele asc; payload: candidate
@@ -540,72 +616,138 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
       key[slot] = kk;
     }
     __syncthreads();
-    // the list is in allele order: one stable pass by the (seed matchCnt, span sum, read span) class orders it; the bitonic network
-    // on the whole key takes the lists with more than 256 classes and the ones that live in HBM scratch
-    if (key != sKey || !ldsClassRanks<NT>(key, live, P.alleleBits + iBits + 3, sCs)) bitonicSort(key, np2);
-    else ldsCountingPass<NT>(key, live, sCnt, warpSums, [&](uint64_t kk) { return csRankOf(sCs, (uint32_t)(kk >> (P.alleleBits + iBits + 3))); });
-    // resolve ties of the packed key with the remaining comparator fields (same allele, same spans)
-    const uint32_t nAll = n;
-    (void)nAll;
-    // equal packed keys (same allele, same spans and match count; rare) are ordered by the remaining comparator fields
-    if (tid == 0) { sTie = 0; sLatch = 0x7FFFFFFF; sGood = -1; sBest = -1; }
-    __syncthreads();
-    for (uint32_t i = 1 + tid; i < live; i += NT)
-      if ((key[i] >> (iBits + 3)) == (key[i - 1] >> (iBits + 3))) sTie = 1;
-    __syncthreads();
-    if (sTie && tid == 0) {
-      for (uint32_t i = 1; i < live; ++i) {
-        if ((key[i] >> (iBits + 3)) != (key[i - 1] >> (iBits + 3))) continue;
-        uint32_t j = i;
-        while (j > 0 && (key[j - 1] >> (iBits + 3)) == (key[j] >> (iBits + 3)) && candBeforeFull(P.cand[c0 + idxOf(key[j])], P.cand[c0 + idxOf(key[j - 1])])) {
-          uint64_t t = key[j]; key[j] = key[j - 1]; key[j - 1] = t;
-          --j;
+    // The selection's order.  The list is in allele order: one stable pass by the (seed matchCnt, span sum, read span) class orders it; the
+    // bitonic network on the whole key takes the lists with more than 256 classes and the ones that live in HBM scratch.  Equal packed keys
+    // above the candidate number (same allele, same spans and match count; rare) are then ordered by the remaining comparator fields.
+    // (`first`: the emit decision follows and reads the order, its words are set up along with the tie flag)
+    auto orderBySelect = [&](bool first) {
+      if (key != sKey || !ldsClassRanks<NT>(key, live, P.alleleBits + iBits + 3, sCs)) bitonicSort(key, np2);
+      else ldsCountingPass<NT>(key, live, sCnt, warpSums, [&](uint64_t kk) { return csRankOf(sCs, (uint32_t)(kk >> (P.alleleBits + iBits + 3))); });
+      if (tid == 0) { sTie = 0; if (first) { sLatch = 0x7FFFFFFF; sGood = -1; sBest = -1; } }
+      __syncthreads();
+      for (uint32_t i = 1 + tid; i < live; i += NT)
+        if ((key[i] >> (iBits + 3)) == (key[i - 1] >> (iBits + 3))) sTie = 1;
+      __syncthreads();
+      if (sTie && tid == 0) {
+        for (uint32_t i = 1; i < live; ++i) {
+          if ((key[i] >> (iBits + 3)) != (key[i - 1] >> (iBits + 3))) continue;
+          uint32_t j = i;
+          while (j > 0 && (key[j - 1] >> (iBits + 3)) == (key[j] >> (iBits + 3)) && candBeforeFull(P.cand[c0 + idxOf(key[j])], P.cand[c0 + idxOf(key[j - 1])])) {
+            uint64_t t = key[j]; key[j] = key[j - 1]; key[j - 1] = t;
+            --j;
+          }
         }
       }
-    }
-    __syncthreads();
-    // latch position: first tried candidate whose extension fails (all candidates before the latch are tried)
-    int myLatch = 0x7FFFFFFF;
-    for (uint32_t i = tid; i < live; i += NT) {
-      const uint32_t fl = (uint32_t)key[i] & 7u;
-      if (fl & SEL_F_SEPSEED) continue;
-      if (!(fl & SEL_F_EXTOK)) { if ((int)i < myLatch) myLatch = (int)i; }
-    }
-    atomicMin(&sLatch, myLatch);
-    __syncthreads();
-    const int latch = sLatch;
-    // goodMatchCnt = seed matchCnt of the first emitted candidate before the latch (the list is sorted by it)
-    int myGood = 0x7FFFFFFF;
-    for (uint32_t i = tid; i < live && (int)i < latch; i += NT) {
-      const uint32_t fl = (uint32_t)key[i] & 7u;
-      if ((fl & SEL_F_SEPSEED) || !(fl & SEL_F_EXTOK)) continue;
-      if ((int)i < myGood) myGood = (int)i;
-    }
-    __shared__ int sFirst;
-    if (tid == 0) sFirst = 0x7FFFFFFF;
-    __syncthreads();
-    atomicMin(&sFirst, myGood);
-    __syncthreads();
-    if (tid == 0) sGood = sFirst == 0x7FFFFFFF ? -1 : seedOf(key[sFirst]);
-    __syncthreads();
-    const int good = sGood;
-    // emit flags + best extended matchCnt
+      __syncthreads();
+    };
+    // emit marks + best extended matchCnt
     uint32_t written = 0;
     unsigned int nbLocal = 0;
     int myBest = -1;
-    // first pass: count and best
     uint32_t mine = 0;
-    for (uint32_t i = tid; i < live; i += NT) {
-      const uint64_t kk = key[i];
-      const uint32_t fl = (uint32_t)kk & 7u;
-      bool emit = false;
-      if (!(fl & SEL_F_SEPSEED)) {
-        bool tried = true;
-        if ((int)i > latch && seedOf(kk) < good && !(fl & SEL_F_KEEPCLIP)) tried = false;  // SeqSet.hpp:2170-2172
-        emit = tried && (fl & SEL_F_EXTOK);
-        if (emit) { const int xm = (int)P.ext[c0 + idxOf(kk)].matchCnt; if (xm > myBest) myBest = xm; }
+    auto marked = [&](uint64_t kk) { return CUT ? ((uint32_t)kk & SEL_M_EMIT) != 0 : (kk >> 63) != 0; };
+    if constexpr (!CUT) {
+      orderBySelect(true);
+      // latch position: first tried candidate whose extension fails (all candidates before the latch are tried)
+      int myLatch = 0x7FFFFFFF;
+      for (uint32_t i = tid; i < live; i += NT) {
+        const uint32_t fl = (uint32_t)key[i] & 7u;
+        if (fl & SEL_F_SEPSEED) continue;
+        if (!(fl & SEL_F_EXTOK)) { if ((int)i < myLatch) myLatch = (int)i; }
       }
-      if (emit) { ++mine; key[i] = kk | (1ull << 63); }
+      atomicMin(&sLatch, myLatch);
+      __syncthreads();
+      const int latch = sLatch;
+      // goodMatchCnt = seed matchCnt of the first emitted candidate before the latch (the list is sorted by it)
+      int myGood = 0x7FFFFFFF;
+      for (uint32_t i = tid; i < live && (int)i < latch; i += NT) {
+        const uint32_t fl = (uint32_t)key[i] & 7u;
+        if ((fl & SEL_F_SEPSEED) || !(fl & SEL_F_EXTOK)) continue;
+        if ((int)i < myGood) myGood = (int)i;
+      }
+      __shared__ int sFirst;
+      if (tid == 0) sFirst = 0x7FFFFFFF;
+      __syncthreads();
+      atomicMin(&sFirst, myGood);
+      __syncthreads();
+      if (tid == 0) sGood = sFirst == 0x7FFFFFFF ? -1 : seedOf(key[sFirst]);
+      __syncthreads();
+      const int good = sGood;
+      // first pass: count and best
+      for (uint32_t i = tid; i < live; i += NT) {
+        const uint64_t kk = key[i];
+        const uint32_t fl = (uint32_t)kk & 7u;
+        bool emit = false;
+        if (!(fl & SEL_F_SEPSEED)) {
+          bool tried = true;
+          if ((int)i > latch && seedOf(kk) < good && !(fl & SEL_F_KEEPCLIP)) tried = false;  // SeqSet.hpp:2170-2172
+          emit = tried && (fl & SEL_F_EXTOK);
+          if (emit) { const int xm = (int)P.ext[c0 + idxOf(kk)].matchCnt; if (xm > myBest) myBest = xm; }
+        }
+        if (emit) { ++mine; key[i] = kk | (1ull << 63); }
+      }
+    } else {
+      // Lists of more than SELECT_CUT_LEN candidates: nearly all of them are cut, and the cut builds its own keys in candidate order and
+      // sorts those -- the selection's order would be thrown away.  What is emitted follows from two order statistics of the list as it
+      // lies (t1k_select_rule.h): the latch L, a 64-bit min-reduction over the keys above the flags, and `good`, a max-reduction.
+      __shared__ unsigned long long sLKey, sTieHi, sTieLo;
+      if (tid == 0) { sLKey = ~0ull; sTieHi = ~0ull; sTieLo = ~0ull; sTie = 0; sGood = -1; sBest = -1; }
+      __syncthreads();
+      {
+        uint64_t myL = ~0ull;
+        for (uint32_t i = tid; i < live; i += NT) {
+          const uint64_t kk = key[i];
+          if (selLatchCand((uint32_t)kk & 7u) && (kk >> 3) < myL) myL = kk >> 3;
+        }
+        if (myL != ~0ull) atomicMin(&sLKey, (unsigned long long)myL);
+      }
+      __syncthreads();
+      const bool hasL = sLKey != ~0ull;
+      const uint64_t caL = sLKey >> iBits;  // L's class and allele
+      uint32_t idxL = (uint32_t)(sLKey & iMask);
+      auto tieOf = [&](uint32_t i) { const T1kCand c = P.cand[c0 + i]; return selTieOf(c.readSE, c.seqStart, c.seqEnd, i); };
+      if (hasL) {
+        // another latch candidate on L's allele in L's class (rare): L is the first of them by the seed coordinates, then the candidate
+        // number -- two exact min-reductions over the two words of SelTie
+        for (uint32_t i = tid; i < live; i += NT) {
+          const uint64_t kk = key[i];
+          if (selLatchCand((uint32_t)kk & 7u) && (kk >> (iBits + 3)) == caL && idxOf(kk) != idxL) sTie = 1;
+        }
+        __syncthreads();
+        if (sTie) {
+          for (uint32_t i = tid; i < live; i += NT) {
+            const uint64_t kk = key[i];
+            if (selLatchCand((uint32_t)kk & 7u) && (kk >> (iBits + 3)) == caL) atomicMin(&sTieHi, (unsigned long long)tieOf(i).hi);
+          }
+          __syncthreads();
+          for (uint32_t i = tid; i < live; i += NT) {
+            const uint64_t kk = key[i];
+            if (selLatchCand((uint32_t)kk & 7u) && (kk >> (iBits + 3)) == caL) { const SelTie t = tieOf(i); if (t.hi == sTieHi) atomicMin(&sTieLo, (unsigned long long)t.lo); }
+          }
+          __syncthreads();
+          idxL = (uint32_t)(sTieLo & 0xFFFFFFFFull);
+        }
+      }
+      SelTie tieL{0, 0};
+      if (hasL) tieL = tieOf(idxL);
+      // the flags become the marks (can be emitted, behind L, KEEPCLIP); good = the largest seed match count of what can be emitted before L
+      int myGood = -1;
+      for (uint32_t i = tid; i < live; i += NT) {
+        const uint64_t kk = key[i];
+        const bool before = hasL ? selBeforeLatch(kk >> (iBits + 3), caL, tieL, [&]() { return tieOf(i); }) : true;
+        const uint32_t mk = selMarks((uint32_t)kk & 7u, hasL, before);
+        key[i] = (kk & ~7ull) | mk;
+        if (selCountsForGood(mk) && seedOf(kk) > myGood) myGood = seedOf(kk);
+      }
+      if (myGood >= 0) atomicMax(&sGood, myGood);
+      __syncthreads();
+      const int good = sGood;
+      for (uint32_t i = tid; i < live; i += NT) {
+        const uint64_t kk = key[i];
+        const bool emit = selEmit((uint32_t)kk & 7u, seedOf(kk), good);
+        if (emit) { ++mine; const int xm = (int)P.ext[c0 + i].matchCnt; if (xm > myBest) myBest = xm; }
+        key[i] = (kk & ~7ull) | (emit ? SEL_M_EMIT : 0u);
+      }
     }
     atomicMax(&sBest, myBest);
     uint32_t tot;
@@ -630,37 +772,43 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
       P.store[at] = p;
     };
     uint32_t keep = tot;  // records of the list that are written
-    const bool cutList = PK && tot > 1000;
+    const bool cutList = CUT && tot > SELECT_CUT_LEN;
+    T1K_SELECT_ROUTE_COUNT();
+    if (CUT && !cutList) orderBySelect(false);  // the list is written in the selection's order
     if (cutList) {
       // More than 1000 emitted: order them by (extended match count desc, span sum incl. clips asc, read span desc, allele asc) and cut at
-      // the first one whose similarity lies more than 0.1 below the first one's.  The select keys are dead: the emit marks go into a bitmap
-      // by candidate index (in sCnt, which the counting pass takes over afterwards), and the new keys are built in candidate order -- the
-      // allele order k_collect left -- so that one stable class pass orders them, and compacted into the key array.
+      // the first one whose similarity lies more than 0.1 below the first one's.  The select keys are dead and still lie in candidate order:
+      // their emit marks become a bitmap (ballots; in sCnt, which the counting pass takes over afterwards), one prefix over its words gives
+      // every emitted candidate its place, and the new keys are written there -- in candidate order, the allele order k_collect left, so
+      // that one stable class pass orders them.
       __syncthreads();  // (sBest is complete)
       const int bestMatch = sBest;
-      uint32_t *emitBits = (uint32_t *)sCnt;  // n <= sortCap = 2^15 candidates: 4 KB of the 1024-thread shape's 8, 256 bytes of the 256-thread shape's 2 KB
-      for (uint32_t q = tid; q < (n + 31) / 32; q += NT) emitBits[q] = 0;
+      // n <= 2^15 candidates: 512 words of marks and their prefix, 6 KB of the 1024-thread shape's 8; 32 words, 384 bytes of the 256-thread shape's 2 KB
+      const uint32_t nWords = (n + 63) / 64;
+      uint64_t *emitBits = (uint64_t *)sCnt;
+      uint32_t *wordBase = (uint32_t *)(emitBits + nWords);
+      for (uint32_t i0 = 0; i0 < n; i0 += NT) {  // (a wavefront's 64 candidates are one word)
+        const uint32_t i = i0 + tid;
+        const uint64_t bal = __ballot(i < n && marked(key[i]));
+        if ((tid & 63) == 0 && i < n) emitBits[i >> 6] = bal;
+      }
       __syncthreads();
-      for (uint32_t i = tid; i < live; i += NT)
-        if (key[i] >> 63) { const uint32_t ix = idxOf(key[i]); atomicOr(&emitBits[ix >> 5], 1u << (ix & 31)); }
+      {
+        uint32_t t2;  // nWords <= NT: one prefix over the words
+        const uint32_t ex = t1k_block_scan_exclusive_n<NT / 64>((uint32_t)tid < nWords ? (uint32_t)__popcll(emitBits[tid]) : 0u, warpSums, &t2);
+        if ((uint32_t)tid < nWords) wordBase[tid] = ex;
+      }
       __syncthreads();
       const KeyW TW = truncWidths<XL>((int)P.reads.len[re]);
-      uint32_t done = 0;
-      for (uint32_t i0 = 0; i0 < n; i0 += NT) {
-        const uint32_t i = i0 + tid;
-        const bool flag = i < n && ((emitBits[i >> 5] >> (i & 31)) & 1u);
-        uint64_t kk = 0;
-        if (flag) {
-          const T1kExt x = P.ext[c0 + i];
-          const int rspan = x.readEnd - x.readStart;
-          const int d = rspan + 1 + x.seqEnd - x.seqStart + 1 + 2 * x.leftClip + 2 * x.rightClip;  // similarity desc == d asc at equal matchCnt
-          if (!packSortKey(TW, (int)x.matchCnt, d, rspan, P.cand[c0 + i].allele & 0x7FFFFFFFu, i, P.alleleBits, iBits, &kk)) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); kk = i; }
-          if ((int)x.matchCnt >= bestMatch - 10) ++nbLocal;  // (the near-best statistic counts the emitted overlaps, before the cut)
-        }
-        uint32_t t2;
-        const uint32_t off = t1k_block_scan_exclusive_n<NT / 64>(flag ? 1u : 0u, warpSums, &t2);
-        if (flag) key[done + off] = kk;
-        done += t2;
+      for (uint32_t i = tid; i < n; i += NT) {
+        if (!((emitBits[i >> 6] >> (i & 63)) & 1ull)) continue;
+        const T1kExt x = P.ext[c0 + i];
+        const int rspan = x.readEnd - x.readStart;
+        const int d = rspan + 1 + x.seqEnd - x.seqStart + 1 + 2 * x.leftClip + 2 * x.rightClip;  // similarity desc == d asc at equal matchCnt
+        uint64_t kk;
+        if (!packSortKey(TW, (int)x.matchCnt, d, rspan, P.cand[c0 + i].allele & 0x7FFFFFFFu, i, P.alleleBits, iBits, &kk)) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); kk = i; }
+        if ((int)x.matchCnt >= bestMatch - 10) ++nbLocal;  // (the near-best statistic counts the emitted overlaps, before the cut)
+        key[selBitPos(emitBits, wordBase, i)] = kk;
       }
       uint32_t np2t = 8;
       while (np2t < tot) np2t <<= 1;
@@ -721,7 +869,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
     if (tid == 0) {
       unsigned long long b = atomicAdd(&P.counters[1], (unsigned long long)keep);
       emitTotal += tot;
-      if (b + keep > P.ovlCap) { atomicOr(&P.counters[2], (unsigned long long)ERR_OVLCAP); sBase = 0xFFFFFFFFu; publish(re, 0, 0); }
+      if (b + keep > P.ovlCap) { atomicOr(&P.counters[2], (unsigned long long)ERR_OVLCAP); sBase = 0xFFFFFFFFu; publishEmpty(re); }
       else { sBase = (uint32_t)b; publish(re, (uint32_t)b, keep); }
     }
     __syncthreads();
@@ -732,7 +880,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
       } else {
         for (uint32_t i0 = 0; i0 < live; i0 += NT) {
           uint32_t i = i0 + tid;
-          uint32_t flag = (i < live && (key[i] >> 63)) ? 1u : 0u;
+          uint32_t flag = (i < live && marked(key[i])) ? 1u : 0u;
           uint32_t t2;
           uint32_t off = t1k_block_scan_exclusive_n<NT / 64>(flag, warpSums, &t2);
           if (flag) {
@@ -1286,9 +1434,13 @@ void t1k_launch_extend_retry_dev(t1k_ctx *ctx, const ExtendArgs &a, const uint32
 }
 template <bool XL, bool PK>
 static void launchSelect(t1k_ctx *ctx, const SelectArgs &a, int nWg) {
-  hipFuncSetAttribute((const void *)k_select<SELECT_LARGE, 1024, XL, PK>, hipFuncAttributeMaxDynamicSharedMemorySize, SELECT_LARGE * 8);
-  hipLaunchKernelGGL((k_select<SELECT_SMALL, 256, XL, PK>), dim3(nWg), dim3(256), SELECT_SMALL * 8, ctx->stream, a);
-  hipLaunchKernelGGL((k_select<SELECT_LARGE, 1024, XL, PK>), dim3(std::min(nWg, 512)), dim3(1024), SELECT_LARGE * 8, ctx->stream, a);
+  hipLaunchKernelGGL(k_select_classes, dim3(1), dim3(1024), 0, ctx->stream, a, PK ? 1 : 0);
+  // one launch per size class, each over its own list (the grids as before the lists: the class sizes stay on the device)
+  auto of = [&](int c) { SelectArgs s = a; s.classList = a.classList + (size_t)c * a.reads.nReadEnds; s.lenWord = T1K_CTR_SELECT_LEN + c; s.hoWord = T1K_CTR_SELECT_HANDOUT + c; return s; };
+  hipFuncSetAttribute((const void *)k_select<SELECT_LARGE, 1024, XL, PK, PK>, hipFuncAttributeMaxDynamicSharedMemorySize, SELECT_LARGE * 8);
+  hipLaunchKernelGGL((k_select<SELECT_SMALL, 256, XL, PK, false>), dim3(nWg), dim3(256), SELECT_SMALL * 8, ctx->stream, of(0));
+  hipLaunchKernelGGL((k_select<SELECT_SMALL, 256, XL, PK, PK>), dim3(std::min(nWg, 512)), dim3(256), SELECT_SMALL * 8, ctx->stream, of(1));
+  hipLaunchKernelGGL((k_select<SELECT_LARGE, 1024, XL, PK, PK>), dim3(std::min(nWg, 512)), dim3(1024), SELECT_LARGE * 8, ctx->stream, of(2));
 }
 void t1k_launch_select(t1k_ctx *ctx, const SelectArgs &a, int nWg, bool packed) {
   // xl: a window with reads beyond T1K_MAX_READ_LEN (wider key fields); packed: the lists are cut and stored in the 16-byte form here

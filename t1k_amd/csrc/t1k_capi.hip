@@ -311,7 +311,7 @@ void t1k_ctx_destroy(t1k_ctx *ctx) {
   for (auto &b : ctx->refBufs) freeBuf(b);
   T1kDevBuf *all[] = {&ctx->bReadAscii, &ctx->bReadOffs, &ctx->bReadBases, &ctx->bReadN, &ctx->bReadLen, &ctx->bReadWeight, &ctx->bWgHits, &ctx->bWgGroups,
                       &ctx->bWgStage, &ctx->bWgBig, &ctx->bWgCache, &ctx->bLists, &ctx->bCand, &ctx->bExt, &ctx->bCandStart, &ctx->bCandCount, &ctx->bListPtr, &ctx->bListCount,
-                      &ctx->bOvlWork, &ctx->bOvlUpload, &ctx->bDedupScratch, &ctx->bDedupBases, &ctx->bDedupN, &ctx->bDedupLen, &ctx->bDedupWeight, &ctx->bOvlStart, &ctx->bOvlCount, &ctx->bCounters, &ctx->bSlowQueue, &ctx->bSlowScratch, &ctx->bSortScratch, &ctx->bEqTrace, &ctx->bSortTmp, &ctx->bJobSort, &ctx->bEnd1, &ctx->bEnd2,
+                      &ctx->bOvlWork, &ctx->bOvlUpload, &ctx->bDedupScratch, &ctx->bDedupBases, &ctx->bDedupN, &ctx->bDedupLen, &ctx->bDedupWeight, &ctx->bOvlStart, &ctx->bOvlCount, &ctx->bCounters, &ctx->bSlowQueue, &ctx->bSlowScratch, &ctx->bSortScratch, &ctx->bSelClass, &ctx->bEqTrace, &ctx->bSortTmp, &ctx->bJobSort, &ctx->bEnd1, &ctx->bEnd2,
                       &ctx->bHasN, &ctx->bRows, &ctx->bRowStart, &ctx->bRowCount, &ctx->bFragAssigned, &ctx->bPairScratch, &ctx->bPairOverflow, &ctx->bPairBig, &ctx->bExtractHuge, &ctx->bEmRowPtr, &ctx->bEmEc,
                       &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bExtract, &ctx->bPileup, &ctx->bPileupIn, &ctx->spMap.buf, &ctx->spTab.keys, &ctx->spTab.vals, &ctx->spTab.work, &ctx->bSpIn,
                       &ctx->phMap.buf, &ctx->phTab.keys, &ctx->phTab.vals, &ctx->phTab.work, &ctx->bPhIn, &ctx->bPhObs, &ctx->bPhArena,
@@ -334,7 +334,7 @@ uint64_t t1k_ctx_mem_report(t1k_ctx *ctx, const char *tag, int print) {
 #define B(x) {#x, &ctx->x}
   const struct { const char *name; T1kDevBuf *b; } all[] = {B(bReadAscii), B(bReadOffs), B(bReadBases), B(bReadN), B(bReadLen), B(bReadWeight), B(bWgHits), B(bWgGroups),
     B(bWgStage), B(bWgBig), B(bWgCache), B(bLists), B(bCand), B(bExt), B(bCandStart), B(bCandCount), B(bListPtr), B(bListCount), B(bOvlWork), B(bOvlUpload), B(bDedupScratch), B(bDedupBases), B(bDedupN),
-    B(bDedupLen), B(bDedupWeight), B(bOvlStart), B(bOvlCount), B(bCounters), B(bSlowQueue), B(bSlowScratch), B(bSortScratch), B(bEqTrace), B(bSortTmp), B(bJobSort), B(bEnd1),
+    B(bDedupLen), B(bDedupWeight), B(bOvlStart), B(bOvlCount), B(bCounters), B(bSlowQueue), B(bSlowScratch), B(bSortScratch), B(bSelClass), B(bEqTrace), B(bSortTmp), B(bJobSort), B(bEnd1),
     B(bEnd2), B(bHasN), B(bRows), B(bRowStart), B(bRowCount), B(bFragAssigned), B(bPairScratch), B(bPairOverflow), B(bPairBig), B(bExtractHuge), B(bEmRowPtr), B(bEmEc), B(bEmCount),
     B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract), B(bPileup), B(bPileupIn), B(bSpIn), B(bPhIn), B(bPhObs), B(bPhArena), B(bSupIn),
     {"bSupSites", &ctx->supMap.buf}, {"bSupKeys", &ctx->supTab.keys}, {"bSupVals", &ctx->supTab.vals}, {"bSupWork", &ctx->supTab.work},
@@ -992,6 +992,7 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   if ((rc = t1k_ensure(ctx, ctx->bOvlStart, (size_t)(n + 1) * 4))) return rc;
   if ((rc = t1k_ensure(ctx, ctx->bOvlCount, (size_t)(n + 1) * 4))) return rc;
   if ((rc = t1k_ensure(ctx, ctx->bSortScratch, (size_t)std::min(nWg, 512) * sortCap * 48))) return rc;  // only the kernels launched with <= 512 workgroups use it
+  if ((rc = t1k_ensure(ctx, ctx->bSelClass, (size_t)(n + 1) * 3 * 4))) return rc;  // the selection's three size-class lists (k_select_classes)
   T1K_HIP(ctx, hipMemsetAsync(ctx->bCounters.p, 0, (size_t)T1K_COUNTER_WORDS * 8, ctx->stream));
   T1K_HIP(ctx, hipMemsetAsync(ctx->bOvlCount.p, 0, (size_t)n * 4 + 4, ctx->stream));
   T1K_HIP(ctx, hipMemsetAsync(ctx->bCandCount.p, 0, (size_t)n * 4 + 4, ctx->stream));
@@ -1059,6 +1060,7 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   s.alleleBits = 1; s.relax = relaxFlag; s.xl = ctx->batchMaxLen > T1K_MAX_READ_LEN ? 1 : 0;
   while ((1u << s.alleleBits) < ctx->ref.nAlleles) ++s.alleleBits;
   s.store = ctx->storeBase; s.listPtr = rd.listPtr + first; s.listCount = rd.listCount + first;
+  s.classList = (uint32_t *)ctx->bSelClass.p;
   t1k_launch_select(ctx, s, nWg, packedSelect);
   T1K_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
   if (packedSelect) {
@@ -1072,6 +1074,17 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
     ctx->nOvl = hc[1];  // the records kept: the store advances by them
     ctx->storeUsed[ctx->storeSlot] += ctx->nOvl;
     if (getenv("T1K_DEBUG_PHASES")) fprintf(stderr, "[t1k] packed selection: cand %llu emitted %llu kept %llu\n", hc[0], hc[21], hc[1]);
+#ifdef T1K_SELECT_ROUTES
+    {
+      static unsigned long long sum[12];
+      static const int once = atexit([] {
+        static const char *name[6] = {"no candidate", "1 .. 1000", "1001 .. 2048, not cut", "1001 .. 2048, cut", "beyond 2048, not cut", "beyond 2048, cut"};
+        for (int r = 0; r < 6; ++r) fprintf(stderr, "[t1k] select routes: %-22s %12llu read-ends %14llu candidates\n", name[r], sum[2 * r], sum[2 * r + 1]);
+      });
+      (void)once;
+      for (int r = 0; r < 12; ++r) __atomic_fetch_add(&sum[r], hc[40 + r], __ATOMIC_RELAXED);
+    }
+#endif
     return finishRangeStats(ctx, n, hc, hc[21], t0);
   }
   if ((rc = fetchCounters(ctx, hc))) return rc;

@@ -804,6 +804,15 @@ enum { T1K_STAT_DP = 0, T1K_STAT_FAST = 1, T1K_STAT_GENERAL = 2, T1K_STAT_EXTEND
 #ifndef T1K_SELECT_LARGE_HANDOUT
 #define T1K_SELECT_LARGE_HANDOUT 1
 #endif
+// (the selection's launches take positions of their own size class's list, k_select_classes: none of them skips a read-end any more.  The 256-thread
+// shape's launch over the lists of 1001 .. 2048 candidates takes them one at a time like the 1024-thread shape: every one of them is a long list)
+#ifndef T1K_SELECT_MID_HANDOUT
+#define T1K_SELECT_MID_HANDOUT 1
+#endif
+// control counters of the selection: hand-out word and list length per size class (words 28 / 29 were the hand-out words of the two launches that
+// walked the whole range)
+#define T1K_CTR_SELECT_HANDOUT 56
+#define T1K_CTR_SELECT_LEN 59
 #ifndef T1K_TRUNC_SMALL_HANDOUT
 #define T1K_TRUNC_SMALL_HANDOUT 4
 #endif
@@ -972,7 +981,7 @@ struct t1k_ctx {
                                  // t1k_coverage_selected over the kept lists, or not wanted at all)
   double msAlloc = 0;            // wall time spent in hipMalloc (fresh VRAM is zeroed by the driver: ~35 ms per GB)
   uint64_t bytesAlloc = 0;
-  T1kDevBuf bCand, bExt, bCandStart, bCandCount, bOvlStart, bOvlCount, bCounters, bSlowQueue, bSlowScratch, bSortScratch, bEqTrace, bSortTmp, bJobSort;
+  T1kDevBuf bCand, bExt, bCandStart, bCandCount, bOvlStart, bOvlCount, bCounters, bSlowQueue, bSlowScratch, bSortScratch, bSelClass, bEqTrace, bSortTmp, bJobSort;
   uint64_t nCand = 0, nOvl = 0;
   // pairing
   T1kDevBuf bEnd1, bEnd2, bHasN, bRows, bRowStart, bRowCount, bFragAssigned, bPairScratch, bPairOverflow, bPairBig, bExtractHuge;

@@ -66,6 +66,10 @@ struct SelectArgs {
   int relax;               // --relaxIntronAlign: the relaxed match counts come from the full alignments (else k_select writes them)
   int xl;                  // the window holds reads beyond T1K_MAX_READ_LEN: wider sort-key fields
   unsigned long long *counters;
+  // read-ends by size class (k_select_classes): [class][nReadEnds], dense and ascending; a selection launch gets its own class's list,
+  // the counter word that holds its length and the word it hands positions out from
+  uint32_t *classList;
+  int lenWord, hoWord;
 };
 
 struct FullArgs {
