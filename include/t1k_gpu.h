@@ -476,6 +476,40 @@ int t1k_support_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap,
 int t1k_support_stats(t1k_ctx *ctx, uint64_t *keysEmitted, uint64_t *folds, double *foldMs);
 int t1k_support_end(t1k_ctx *ctx);
 
+/* ---- novel indel evidence per allele, left-aligned (analyzer --indels) -------------------------------------------------
+ * The gap runs of the edit strings t1k_pileup_* counts column by column, taken as events.  alleleText holds the alleles' bases back to
+ * back (A C G T N only, else T1K_ERR_ARG), allele a at alleleText[alleleOff[a] .. alleleOff[a + 1]).  Records as for t1k_pileup_add
+ * (w_all / w_uniq / reserved are ignored and stay untouched); strand[i]: 0 when record i lies on the allele's forward strand, 1 on the
+ * reverse.  Record i books once per entry of bookUniq[bookPtr[i] .. bookPtr[i + 1]) -- one per assignment overlap that points at it; the
+ * entry is 1 when the overlap's fragment has a single assignment, else 0.
+ * An event is a maximal run of columns of one gap op (3 deletion, 2 insertion) that holds neither the first nor the last column of its
+ * edit string.  A run that does is an EDGE run: no event, its columns are only counted (edgeDelBooked / edgeInsBooked).  An insertion run
+ * and a deletion run that touch are two events.  A deletion of L allele bases from p (0-based) on is (DEL, p, L); read bases S (L of them,
+ * as `text` holds them, anything but A/C/G/T taken as N) in front of allele base p are (INS, p, L, S).  Every event is left-normalised
+ * against the allele's bases alone, an N equal to nothing, itself included, with no bound but p == 0:
+ *   DEL: while p > 0 and allele[p-1] == allele[p+L-1]: p -= 1
+ *   INS: while p > 0 and allele[p-1] == S[-1]: S = allele[p-1] + S[:-1]; p -= 1
+ * With every booking the event adds 1 under one key of ONE sparse table of (key, count) runs, ascending by key, every key below 2^63:
+ *   ((((g << 2 | type) << 27 | payload) << 1 | strand) << 1) | (1 - uniq),  g = alleleOff[allele] + p after normalisation;
+ *   type 0: a deletion, payload L (a deletion of 2^27 bases or more: T1K_ERR_CAPACITY);
+ *   type 1: a short insertion -- L <= 13 and every base of the normalised S one of ACGT -- payload (1 << 2L) | the bases, 2 bits each
+ *           (A 0, C 1, G 2, T 3), the first base highest;
+ *   type 2: a long insertion -- L > 13, or an N in the normalised S -- payload min(L, 2^27 - 1): LONG INSERTIONS ARE TOLD APART BY
+ *           POSITION AND LENGTH ONLY.
+ * A uniq booking is stored once, under the even key, as in t1k_sitepile_*: plain = even + odd, _uniq = even.
+ * Nothing is emitted unless the whole call is sound, its sound records included: T1K_ERR_ARG for what t1k_sitepile_add refuses (allele,
+ * ops, walks, bookPtr), a strand > 1, a bookUniq > 1; T1K_ERR_CAPACITY for 2^31 bookings or more on one record and as t1k_sitepile_*;
+ * T1K_ERR_STATE as t1k_sitepile_*.  Pending keys are folded into runs whenever they reach 2^28 (env T1K_INDEL_PENDING) and at _get.
+ * t1k_indel_get: as t1k_sitepile_get.  t1k_indel_stats, over the calls that were taken: events -- the events of distinct records,
+ * bookings not multiplied in; shifted -- those of them whose position moved under normalisation; edgeDelBooked / edgeInsBooked -- the
+ * columns of edge runs x their record's bookings; keysEmitted / folds / foldMs as t1k_sitepile_stats.  All but foldMs are deterministic. */
+int t1k_indel_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff /* [nAlleles + 1] */, const char *alleleText /* [alleleOff[nAlleles]], ACGTN */);
+int t1k_indel_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const uint8_t *strand /* [n]: 0 / 1 */, const uint64_t *bookPtr /* [n + 1] */, const uint8_t *bookUniq,
+                  const char *text, uint64_t textBytes, const int8_t *ops, uint64_t opsBytes, double *kernelMs);
+int t1k_indel_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns);
+int t1k_indel_stats(t1k_ctx *ctx, uint64_t *events, uint64_t *shifted, uint64_t *edgeDelBooked, uint64_t *edgeInsBooked, uint64_t *keysEmitted, uint64_t *folds, double *foldMs);
+int t1k_indel_end(t1k_ctx *ctx);
+
 /* ---- CIGAR, MD:Z and NM:i of alignments (analyzer --sam) -----------------------------------------------------------------
  * Stateless.  Records as for t1k_pileup_add; read_at, w_all and w_uniq are ignored (no read text is read).  alleleText holds the alleles'
  * bases back to back, allele a at alleleText[alleleOff[a] .. alleleOff[a + 1]).  For record i, its edit string walked from allele position

@@ -142,6 +142,11 @@ def lib():
     L.t1k_support_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
     L.t1k_support_stats.argtypes = [vp, u64p, u64p, C.POINTER(C.c_double)]
     L.t1k_support_end.argtypes = [vp]
+    L.t1k_indel_begin.argtypes = [vp, C.c_uint32, vp, vp]
+    L.t1k_indel_add.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_double)]
+    L.t1k_indel_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
+    L.t1k_indel_stats.argtypes = [vp, u64p, u64p, u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]
+    L.t1k_indel_end.argtypes = [vp]
     L.t1k_phase_begin.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp]
     L.t1k_phase_add.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_double)]
     L.t1k_phase_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
@@ -763,6 +768,75 @@ class Context:
             return keys, counts, ms, self.support_stats()[1]
         finally:
             self.support_end()
+
+    # novel indel evidence, left-aligned (t1k_indel_begin / _add / _get / _stats / _end); raw=True returns the status code instead of raising
+    def indel_begin(self, allele_off, allele_text, raw=False):
+        """allele_text: the alleles' bases back to back (bytes or uint8, A C G T N), allele a at allele_text[allele_off[a]:allele_off[a + 1]]"""
+        off = np.ascontiguousarray(allele_off, np.uint64)
+        t = np.frombuffer(allele_text, np.uint8) if isinstance(allele_text, (bytes, bytearray)) else np.ascontiguousarray(allele_text, np.uint8)
+        assert len(off) == 0 or len(t) == int(off[-1])
+        rc = lib().t1k_indel_begin(self.h, max(len(off) - 1, 0), _ptr(off), _ptr(t))
+        if raw:
+            return rc
+        self._check(rc, "t1k_indel_begin")
+
+    def indel_add(self, aln, strand, book_ptr, book_uniq, text, ops, raw=False):
+        """aln: PILEUP_ALN_DTYPE records; strand: one uint8 per record (0 forward, 1 reverse); record i books once per entry of
+        book_uniq[book_ptr[i]:book_ptr[i + 1]] (uint8: 1 when the booking's fragment has a single assignment); text / ops as for pileup_add.
+        Returns the kernels' device time in ms"""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        s = np.ascontiguousarray(strand, np.uint8)
+        bp, bk = np.ascontiguousarray(book_ptr, np.uint64), np.ascontiguousarray(book_uniq, np.uint8)
+        assert len(bp) == len(a) + 1 and len(s) == len(a)
+        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+        o = np.ascontiguousarray(ops, np.int8)
+        ms = C.c_double()
+        rc = lib().t1k_indel_add(self.h, _ptr(a), len(a), _ptr(s), _ptr(bp), _ptr(bk), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
+        if raw:
+            return rc
+        self._check(rc, "t1k_indel_add")
+        return ms.value
+
+    def indel_get(self, raw=False):
+        """the table's runs, ascending: (keys uint64, counts int32); key = ((((g << 2 | type) << 27 | payload) << 1 | strand) << 1) | (1 - uniq)
+        with g = allele_off[allele] + the normalised position, type 0 DEL (payload = length), 1 short INS (payload = 1 << 2 L | bases),
+        2 long INS (payload = length)"""
+        n = C.c_uint64()
+        rc = lib().t1k_indel_get(self.h, None, None, 0, C.byref(n))
+        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
+        if rc == 0 and n.value:
+            rc = lib().t1k_indel_get(self.h, _ptr(keys), _ptr(counts), n.value, C.byref(n))
+        if raw:
+            return rc
+        self._check(rc, "t1k_indel_get")
+        return keys, counts
+
+    def indel_stats(self):
+        """(events, shifted, edge del columns x bookings, edge ins columns x bookings, keys emitted, folds, device ms of the folds) of the open table"""
+        v = [C.c_uint64() for _ in range(6)]
+        ms = C.c_double()
+        self._check(lib().t1k_indel_stats(self.h, *[C.byref(x) for x in v], C.byref(ms)), "t1k_indel_stats")
+        return tuple(x.value for x in v) + (ms.value,)
+
+    def indel_end(self, raw=False):
+        rc = lib().t1k_indel_end(self.h)
+        if raw:
+            return rc
+        self._check(rc, "t1k_indel_end")
+
+    def indel(self, allele_off, allele_text, aln, strand, book_ptr, book_uniq, text, ops, cuts=()):
+        """begin, add (the records split at the indices `cuts` into several calls), get, stats, end: (keys, counts, kernels' ms, stats)"""
+        a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
+        s = np.ascontiguousarray(strand, np.uint8)
+        bp = np.ascontiguousarray(book_ptr, np.uint64)
+        self.indel_begin(allele_off, allele_text)
+        try:
+            edges = [0] + [int(c) for c in cuts] + [len(a)]
+            ms = sum(self.indel_add(a[lo:hi], s[lo:hi], bp[lo:hi + 1], book_uniq, text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
+            keys, counts = self.indel_get()
+            return keys, counts, ms, self.indel_stats()
+        finally:
+            self.indel_end()
 
     # read-backed phasing of site pairs (t1k_phase_begin / _add / _get / _stats / _end; DESIGN §11.5); raw=True returns the status code instead of raising
     def phase_begin(self, allele_off, site_allele, site_pos, raw=False):

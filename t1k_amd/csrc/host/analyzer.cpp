@@ -1,6 +1,8 @@
 // t1k_amd/csrc/host/analyzer.cpp -- t1k_analyzer_main(): the post-analysis stage (Analyzer.cpp:236-733 as run-t1k:438-449 starts it)
 // on top of the job layer: re-assignment to the selected alleles, novel variants, per-barcode summary.
+#include <cerrno>
 #include <numeric>
+#include <tuple>
 #include "job_internal.h"
 
 extern "C" {
@@ -55,6 +57,8 @@ static const char *kPileupHeader = "#allele\tpos\texon_pos\tref\tA\tC\tG\tT\tN\t
 // record of mate 2 or none, uniq), 9 more bytes per assignment.
 // --siteSupport replays them through t1k_support_add: per distinct alignment its read-end's length, front clip and strand
 // (12 bytes), per assignment overlap its flags and its template's extent (12 bytes, plus the 8 bytes of a list pointer per alignment).
+// --indels replays them through t1k_indel_add: per distinct alignment its strand (1 byte, plus the 8 bytes of a list pointer),
+// per assignment overlap whether its fragment has one assignment (1 byte).
 // Any of the flags keeps the pieces; each keeps its own booking lists only.
 struct AnalyzerSitepile {
   struct Piece {
@@ -67,9 +71,12 @@ struct AnalyzerSitepile {
     std::vector<t1k_support_rec> supRec;     // --siteSupport: one per record,
     std::vector<uint64_t> supBookPtr;        // its bookings
     std::vector<t1k_support_book> supBook;   // one per assignment overlap
+    std::vector<uint8_t> indStrand;          // --indels: one per record,
+    std::vector<uint64_t> indBookPtr;        // its bookings
+    std::vector<uint8_t> indBookUniq;        // one per assignment overlap
     uint64_t ops0 = 0, ops1 = 0;   // the piece's edit strings: V.ops[ops0 .. ops1)
   };
-  bool barcodes = false, phase = false, support = false;    // --barcodePileup, --phase, --siteSupport
+  bool barcodes = false, phase = false, support = false, indels = false;    // --barcodePileup, --phase, --siteSupport, --indels
   const std::vector<int> *bcOf = nullptr;  // fragment -> barcode id (--barcodePileup)
   std::vector<Piece> pieces;
   // extra sites of --sites (allele, 0-based position), and the lines of the file that name an allele which is not selected
@@ -88,6 +95,7 @@ struct AnalyzerSam {
 
 static const char *kPhaseHeader = "#allele\tpos1\tpos2\texon_pos1\texon_pos2\tref1\tref2\tvar1\tvar2\tobs1\tobs2\tcount\tcount_uniq\n";
 static const char *kSupportHeader = "#allele\tpos\texon_pos\tref\tvar\tobs\tcount\tcount_uniq\tfwd\trev\tmate1\tmate2\tend_min\tend_med\tnear_end\ttemplates\n";
+static const char *kIndelHeader = "#allele\tpos\texon_pos\ttype\tlen\tseq\tcount\tcount_uniq\tfwd\trev\n";
 static const char *kBarcodePileupHeader ="#barcode\tallele\tpos\texon_pos\tref\tvar\tA\tC\tG\tT\tN\tdel\tins\tA_uniq\tC_uniq\tG_uniq\tT_uniq\tN_uniq\tdel_uniq\tins_uniq\n";
 
 // every fragment's raw row (the reference's list order): cnt[f] entries at rows[rowAt[f]]
@@ -510,9 +518,26 @@ static int analyzerAlignAssignments(t1k_job *job, AnalyzerVariants &V, AnalyzerP
             pc.supBook.resize(pc.supBookPtr[nJ]);
             supFill.assign(pc.supBookPtr.begin(), pc.supBookPtr.end() - 1);
           }
+          std::vector<uint64_t> indFill;
+          if (sp->indels) {
+            // per record the strand, from where supRec takes it
+            pc.indStrand.resize(nJ);
+            pc.indBookPtr.assign(nJ + 1, 0);
+            for (size_t j = 0; j < nJ; ++j) {
+              pc.indStrand[j] = lists[listAt[jobs[j].end] + jobs[j].idx].strand == -1 ? 1 : 0;
+              pc.indBookPtr[j + 1] = pc.indBookPtr[j] + recs[j].w_all;
+            }
+            pc.indBookUniq.resize(pc.indBookPtr[nJ]);
+            indFill.assign(pc.indBookPtr.begin(), pc.indBookPtr.end() - 1);
+          }
           for (uint32_t f = f0; f < f1; ++f) {
             const uint32_t one = V.asgPtr[f + 1] - V.asgPtr[f] == 1 ? 1u : 0u;
             for (uint64_t q = V.asgPtr[f]; q < V.asgPtr[f + 1]; ++q) {
+              if (sp->indels)
+                for (int m = 0; m < 2; ++m) {
+                  const int64_t j = jobOfAsg[m][q - q0];
+                  if (j >= 0) pc.indBookUniq[indFill[j]++] = (uint8_t)one;
+                }
               if (sp->support) {
                 // the template of the assignment: both mates' extent on the allele, and which way the fragment lies (file 1 on the reverse
                 // strand; with a file-2 read-end alone, that one on the forward strand)
@@ -969,6 +994,111 @@ static bool analyzerSupport(t1k_job *job, const std::string &prefix, const Analy
   return true;
 }
 
+// <prefix>_allele_indel.tsv: the kept pieces through t1k_indel_add; the runs that come back ascend by (allele position after
+// normalisation, type, payload, strand, uniq), so the four keys of an event are consecutive.  One line per event with at least minCount
+// bookings, ordered by allele (job->ref.al order), pos, DEL before INS, len, seq.  job == NULL: the header alone
+static bool analyzerIndels(t1k_job *job, const std::string &prefix, const AnalyzerVariants *V, const AnalyzerSitepile *sp, long minCount) {
+  const double t0 = nowMs();
+  struct Line { uint32_t allele, pos, ins, len; std::string seq; int64_t all, uniq, strand[2]; };
+  std::vector<Line> lines;
+  double msKernels = 0, msFold = 0;
+  uint64_t nRecs = 0, nRuns = 0, events = 0, shifted = 0, edgeDel = 0, edgeIns = 0, emitted = 0, folds = 0;
+  std::vector<uint64_t> refOff;
+  if (job) {
+    const RefSet &R = job->ref;
+    const size_t A = R.seqs.size();
+    t1k_ctx *ctx = job->ctx;
+    auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
+    int rc;
+    // the alleles' bases back to back, reduced to A C G T N
+    refOff.assign(A + 1, 0);
+    for (size_t a = 0; a < A; ++a) refOff[a + 1] = refOff[a] + R.seqs[a].size();
+    std::string refText;
+    refText.reserve(refOff.back());
+    for (const std::string &sq : R.seqs)
+      for (char c : sq) { const char u = (char)toupper((unsigned char)c); refText += (u == 'A' || u == 'C' || u == 'G' || u == 'T') ? u : 'N'; }
+    std::vector<uint64_t> keys;
+    std::vector<int32_t> counts;
+    if ((rc = t1k_indel_begin(ctx, (uint32_t)A, refOff.data(), refText.data())) != T1K_OK) return fail(rc);
+    for (const AnalyzerSitepile::Piece &pc : sp->pieces) {
+      double ms = 0;
+      if ((rc = t1k_indel_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), pc.indStrand.data(), pc.indBookPtr.data(), pc.indBookUniq.data(), pc.pat.data(), pc.pat.size(),
+                              V->ops.data() + pc.ops0, pc.ops1 - pc.ops0, &ms)) != T1K_OK) {
+        fail(rc);
+        t1k_indel_end(ctx);
+        return false;
+      }
+      msKernels += ms;
+      nRecs += pc.recs.size();
+    }
+    if ((rc = t1k_indel_get(ctx, nullptr, nullptr, 0, &nRuns)) == T1K_OK && nRuns) {
+      keys.resize(nRuns); counts.resize(nRuns);
+      rc = t1k_indel_get(ctx, keys.data(), counts.data(), nRuns, &nRuns);
+    }
+    if (rc == T1K_OK) rc = t1k_indel_stats(ctx, &events, &shifted, &edgeDel, &edgeIns, &emitted, &folds, &msFold);
+    if (rc != T1K_OK) { fail(rc); t1k_indel_end(ctx); return false; }
+    if ((rc = t1k_indel_end(ctx)) != T1K_OK) return fail(rc);
+    for (size_t i = 0; i < keys.size();) {
+      const uint64_t ev = keys[i] >> 2;  // (g, type, payload): its runs are consecutive
+      Line l{};
+      for (; i < keys.size() && (keys[i] >> 2) == ev; ++i) {
+        const int64_t c = counts[i];
+        l.all += c;                                               // a uniq booking counts in the plain counter as well
+        if ((keys[i] & 1) == 0) l.uniq += c;
+        l.strand[(keys[i] >> 1) & 1] += c;
+      }
+      if (l.all < minCount) continue;
+      const uint64_t g = ev >> 29;
+      const uint32_t type = (uint32_t)(ev >> 27) & 3u, payload = (uint32_t)ev & ((1u << 27) - 1u);
+      l.allele = (uint32_t)(std::upper_bound(refOff.begin(), refOff.end(), g) - refOff.begin() - 1);
+      const uint32_t p = (uint32_t)(g - refOff[l.allele]);
+      l.ins = type ? 1 : 0;
+      l.pos = type ? p : p + 1;                                   // DEL: the first deleted base; INS: the base behind which it is inserted, 0 = in front of the first
+      if (type == 0) { l.len = payload; l.seq = R.seqs[l.allele].substr(p, payload); }
+      else if (type == 1) {
+        for (l.len = 0; (payload >> (2 * l.len)) != 1u; ++l.len) {}
+        for (uint32_t k = 0; k < l.len; ++k) l.seq += "ACGT"[(payload >> (2 * (l.len - 1 - k))) & 3u];
+      } else { l.len = payload; l.seq = "*"; }
+      lines.push_back(std::move(l));
+    }
+    std::sort(lines.begin(), lines.end(), [](const Line &x, const Line &y) { return std::tie(x.allele, x.pos, x.ins, x.len, x.seq) < std::tie(y.allele, y.pos, y.ins, y.len, y.seq); });
+  }
+  const double tw = nowMs();
+  FILE *fp = fopen((prefix + "_allele_indel.tsv").c_str(), "w");
+  if (!fp) { fprintf(stderr, "analyzer: cannot write %s_allele_indel.tsv\n", prefix.c_str()); return false; }
+  fputs(kIndelHeader, fp);
+  std::string out;
+  char num[160];
+  std::vector<int> exonic;  // of the allele being written: exonic bases up to and including each position
+  for (size_t i = 0; i < lines.size(); ++i) {
+    const Line &l = lines[i];
+    const RefSet &R = job->ref;
+    if (i == 0 || lines[i - 1].allele != l.allele) {
+      const std::vector<uint8_t> &mask = R.exon[l.allele];
+      exonic.resize(mask.size());
+      int n = 0;
+      for (size_t p = 0; p < mask.size(); ++p) exonic[p] = (n += mask[p] ? 1 : 0);
+    }
+    out += R.al[l.allele].name;
+    snprintf(num, sizeof num, "\t%u\t", l.pos);
+    out += num;
+    if (l.pos >= 1 && R.exon[l.allele][l.pos - 1]) out += std::to_string(exonic[l.pos - 1]); else out += '.';
+    snprintf(num, sizeof num, "\t%s\t%u\t", l.ins ? "INS" : "DEL", l.len);
+    out += num;
+    out += l.seq;
+    snprintf(num, sizeof num, "\t%lld\t%lld\t%lld\t%lld\n", (long long)l.all, (long long)l.uniq, (long long)l.strand[0], (long long)l.strand[1]);
+    out += num;
+    if (out.size() >= (1u << 20)) { fwrite(out.data(), 1, out.size(), fp); out.clear(); }
+  }
+  fwrite(out.data(), 1, out.size(), fp);
+  fclose(fp);
+  if (job && getenv("T1K_DEBUG_PHASES"))
+    fprintf(stderr, "indels: %llu records, %llu events, %llu shifted, %llu + %llu edge columns, %llu keys emitted, %llu folds, %llu runs, %zu lines; upload %.1f ms, kernels %.1f ms, fold %.1f ms, write %.1f ms\n",
+            (unsigned long long)nRecs, (unsigned long long)events, (unsigned long long)shifted, (unsigned long long)edgeDel, (unsigned long long)edgeIns, (unsigned long long)emitted,
+            (unsigned long long)folds, (unsigned long long)nRuns, lines.size(), std::max(0.0, (tw - t0) - msKernels - msFold), msKernels, msFold, nowMs() - tw);
+  return true;
+}
+
 // --barcodeEM and --umi (§11.2): the lists BarcodeSummary counts.  The summary loop hands every counted fragment's kept
 // list over in file order (bc = its row of the per-barcode table) and, under --umi, its UMI word.  runEM() groups the lists per barcode
 // (identical sorted lists, first appearance first, host threads over barcodes) and runs t1k_barcode_em; --umi sends the same lists
@@ -1249,6 +1379,9 @@ static const char *kAnalyzerUsage =
     "\t--siteSupport: also write prefix_allele_support.tsv, for the positions of prefix_allele.vcf and of --sites one line per observed base, deletion (-) or\n"
     "\t\tinserted base (+): the bookings of --pileup there by strand, by mate, by distance from the read-end's nearer end, and the distinct templates behind them\n"
     "\t--supportEnd INT: bookings fewer than INT bases from an end of their read-end count in the near_end column of --siteSupport, 0 .. 511 (default: 10)\n"
+    "\t--indels: also write prefix_allele_indel.tsv, the insertions and deletions inside the alignments the variant pass holds, one line per event and allele,\n"
+    "\t\tleft-aligned against the allele: its bookings, those of fragments with one assignment, and the bookings by strand (no counterpart in the reference)\n"
+    "\t--indelMinCount INT: print only the lines of --indels whose count reaches INT, 1 .. 2147483647 (default: 1)\n"
     "\t--sites FILE: more sites for --barcodePileup and --phase, and for --siteSupport, one per line as allele_name<TAB>pos (1-based, the pos column of prefix_allele_pileup.tsv); '#' lines,\n"
     "\t\tblank lines and alleles that are not selected are skipped\n"
     "\t--relaxIntronAlign: allow one more mismatch in intronic alignment\n"
@@ -1263,17 +1396,19 @@ int t1k_analyzer_main(int argc, char **argv) {
                                      {"barcodeEM", no_argument, 0, 10011}, {"barcodeEMPrior", required_argument, 0, 10012}, {"umi", required_argument, 0, 10013},
                                      {"umiMismatch", required_argument, 0, 10014}, {"pileup", no_argument, 0, 10015}, {"barcodePileup", no_argument, 0, 10016},
                                      {"sites", required_argument, 0, 10017}, {"phase", no_argument, 0, 10018}, {"sam", no_argument, 0, 10019},
-                                     {"siteSupport", no_argument, 0, 10020}, {"supportEnd", required_argument, 0, 10021}, {0, 0, 0, 0}};
+                                     {"siteSupport", no_argument, 0, 10020}, {"supportEnd", required_argument, 0, 10021}, {"indels", no_argument, 0, 10022},
+                                     {"indelMinCount", required_argument, 0, 10023}, {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
   std::string refFile, alleleFile, prefix = "t1k", barcode;
   std::vector<const char *> f1, f2, single;
   int varMaxGroup = 8;  // Analyzer.cpp:251
-  bool barcodeEM = false, pileup = false, barcodePileup = false, phase = false, samOut = false, siteSupport = false;
+  bool barcodeEM = false, pileup = false, barcodePileup = false, phase = false, samOut = false, siteSupport = false, indels = false;
   double emPrior = 0;
-  const char *emPriorText = nullptr, *umiMismatchText = nullptr, *supportEndText = nullptr;
+  const char *emPriorText = nullptr, *umiMismatchText = nullptr, *supportEndText = nullptr, *indelMinText = nullptr;
   int supportEnd = 10;
+  long indelMinCount = 1;
   std::string umiPath, sitesPath;
   int umiMismatch = 1;
   optind = 1;
@@ -1306,6 +1441,8 @@ int t1k_analyzer_main(int argc, char **argv) {
       case 10019: samOut = true; break;
       case 10020: siteSupport = true; break;
       case 10021: supportEndText = optarg; break;
+      case 10022: indels = true; break;
+      case 10023: indelMinText = optarg; break;
       default: fprintf(stderr, "%s", kAnalyzerUsage); return EXIT_FAILURE;
     }
   }
@@ -1327,6 +1464,14 @@ int t1k_analyzer_main(int argc, char **argv) {
     const long v = strtol(supportEndText, &end, 10);
     if (end == supportEndText || *end || !isdigit((unsigned char)supportEndText[0]) || v < 0 || v > 511) { fprintf(stderr, "--supportEnd needs an integer from 0 to 511.\n"); return EXIT_FAILURE; }
     supportEnd = (int)v;
+  }
+  if (indelMinText && !indels) { fprintf(stderr, "--indelMinCount has no meaning without --indels: ignored.\n"); indelMinText = nullptr; }
+  if (indelMinText) {
+    char *end = nullptr;
+    errno = 0;
+    const long long v = strtoll(indelMinText, &end, 10);
+    if (end == indelMinText || *end || !isdigit((unsigned char)indelMinText[0]) || errno || v < 1 || v > 2147483647ll) { fprintf(stderr, "--indelMinCount needs an integer from 1 to 2147483647.\n"); return EXIT_FAILURE; }
+    indelMinCount = (long)v;
   }
   if (umiMismatchText) {
     if (strcmp(umiMismatchText, "0") && strcmp(umiMismatchText, "1")) { fprintf(stderr, "--umiMismatch needs 0 or 1.\n"); return EXIT_FAILURE; }
@@ -1392,6 +1537,7 @@ int t1k_analyzer_main(int argc, char **argv) {
       fputs(kSupportHeader, fs);
       fclose(fs);
     }
+    if (indels && !analyzerIndels(nullptr, prefix, nullptr, nullptr, indelMinCount)) return EXIT_FAILURE;
     if (samOut) {
       AnalyzerSam sam;
       if (!analyzerSamOpen(nullptr, prefix, sam) || !analyzerSamClose(sam)) return EXIT_FAILURE;
@@ -1407,8 +1553,8 @@ int t1k_analyzer_main(int argc, char **argv) {
     return EXIT_FAILURE;
   }
   job->analyzer = true;
-  std::unique_ptr<AnalyzerSitepile> sp(barcodePileup || phase || siteSupport ? new AnalyzerSitepile : nullptr);
-  if (sp) { sp->barcodes = barcodePileup; sp->phase = phase; sp->support = siteSupport; }
+  std::unique_ptr<AnalyzerSitepile> sp(barcodePileup || phase || siteSupport || indels ? new AnalyzerSitepile : nullptr);
+  if (sp) { sp->barcodes = barcodePileup; sp->phase = phase; sp->support = siteSupport; sp->indels = indels; }
   if (sp && !sitesPath.empty() && !analyzerReadSites(job, sitesPath, *sp)) { t1k_job_destroy(job); return EXIT_FAILURE; }
   const bool paired = !f2.empty();
   const std::vector<const char *> &first = !f1.empty() ? f1 : single;
@@ -1449,7 +1595,7 @@ int t1k_analyzer_main(int argc, char **argv) {
     rc = analyzerCallVariants(job, varMaxGroup, V, pile.get(), sp.get(), sam.get());
     if (rc != T1K_OK) { fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); t1k_job_destroy(job); return EXIT_FAILURE; }
     logLine("Finish allele quantification in %d EM iterations.", V.emIterations);
-  } else if (pileup || sam || (sp && !sp->fileSites.empty())) {
+  } else if (pileup || sam || indels || (sp && !sp->fileSites.empty())) {
     // no variant is called, but the pileup is of the alignments of steps (1) - (3): they run, VariantCaller does not (V.vc stays empty: the
     // VCF is the empty file and the per-barcode table counts the raw lists).  --barcodePileup, --phase and --siteSupport without sites of their own have nothing to book.
     rc = analyzerAlignAssignments(job, V, pile.get(), sp.get(), sam.get());
@@ -1483,6 +1629,7 @@ int t1k_analyzer_main(int argc, char **argv) {
     if (barcodePileup && !analyzerSitepile(job, prefix, V, *sp, siteList, names)) { t1k_job_destroy(job); return EXIT_FAILURE; }
     if (phase && !analyzerPhase(job, prefix, V, *sp, siteList)) { t1k_job_destroy(job); return EXIT_FAILURE; }
     if (siteSupport && !analyzerSupport(job, prefix, V, *sp, siteList, supportEnd)) { t1k_job_destroy(job); return EXIT_FAILURE; }
+    if (indels && !analyzerIndels(job, prefix, &V, sp.get(), indelMinCount)) { t1k_job_destroy(job); return EXIT_FAILURE; }
     sp.reset();
   }
   if (in.hasBarcode) {

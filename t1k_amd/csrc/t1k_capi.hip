@@ -315,7 +315,8 @@ void t1k_ctx_destroy(t1k_ctx *ctx) {
                       &ctx->bHasN, &ctx->bRows, &ctx->bRowStart, &ctx->bRowCount, &ctx->bFragAssigned, &ctx->bPairScratch, &ctx->bPairOverflow, &ctx->bPairBig, &ctx->bExtractHuge, &ctx->bEmRowPtr, &ctx->bEmEc,
                       &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bExtract, &ctx->bPileup, &ctx->bPileupIn, &ctx->spMap.buf, &ctx->spTab.keys, &ctx->spTab.vals, &ctx->spTab.work, &ctx->bSpIn,
                       &ctx->phMap.buf, &ctx->phTab.keys, &ctx->phTab.vals, &ctx->phTab.work, &ctx->bPhIn, &ctx->bPhObs, &ctx->bPhArena,
-                      &ctx->supMap.buf, &ctx->supTab.keys, &ctx->supTab.vals, &ctx->supTab.work, &ctx->bSupIn};
+                      &ctx->supMap.buf, &ctx->supTab.keys, &ctx->supTab.vals, &ctx->supTab.work, &ctx->bSupIn,
+                      &ctx->indTab.keys, &ctx->indTab.vals, &ctx->indTab.work, &ctx->bIndRef, &ctx->bIndIn};
   for (auto *b : all) freeBuf(*b);
   for (auto &slot : ctx->storeChunks)
     for (auto &b : slot) freeBuf(b);
@@ -336,7 +337,8 @@ uint64_t t1k_ctx_mem_report(t1k_ctx *ctx, const char *tag, int print) {
     B(bWgStage), B(bWgBig), B(bWgCache), B(bLists), B(bCand), B(bExt), B(bCandStart), B(bCandCount), B(bListPtr), B(bListCount), B(bOvlWork), B(bOvlUpload), B(bDedupScratch), B(bDedupBases), B(bDedupN),
     B(bDedupLen), B(bDedupWeight), B(bOvlStart), B(bOvlCount), B(bCounters), B(bSlowQueue), B(bSlowScratch), B(bSortScratch), B(bSelClass), B(bEqTrace), B(bSortTmp), B(bJobSort), B(bEnd1),
     B(bEnd2), B(bHasN), B(bRows), B(bRowStart), B(bRowCount), B(bFragAssigned), B(bPairScratch), B(bPairOverflow), B(bPairBig), B(bExtractHuge), B(bEmRowPtr), B(bEmEc), B(bEmCount),
-    B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract), B(bPileup), B(bPileupIn), B(bSpIn), B(bPhIn), B(bPhObs), B(bPhArena), B(bSupIn),
+    B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract), B(bPileup), B(bPileupIn), B(bSpIn), B(bPhIn), B(bPhObs), B(bPhArena), B(bSupIn), B(bIndRef), B(bIndIn),
+    {"bIndKeys", &ctx->indTab.keys}, {"bIndVals", &ctx->indTab.vals}, {"bIndWork", &ctx->indTab.work},
     {"bSupSites", &ctx->supMap.buf}, {"bSupKeys", &ctx->supTab.keys}, {"bSupVals", &ctx->supTab.vals}, {"bSupWork", &ctx->supTab.work},
     {"bSpSites", &ctx->spMap.buf}, {"bSpKeys", &ctx->spTab.keys}, {"bSpVals", &ctx->spTab.vals}, {"bSpWork", &ctx->spTab.work},
     {"bPhSites", &ctx->phMap.buf}, {"bPhKeys", &ctx->phTab.keys}, {"bPhVals", &ctx->phTab.vals}, {"bPhWork", &ctx->phTab.work}};

@@ -1034,6 +1034,14 @@ struct t1k_ctx {
   T1kCountTable supTab;
   T1kDevBuf bSupIn;
   bool supOpen = false;
+  // novel indel evidence (t1k_indel.hip), open from t1k_indel_begin to _end: the block [alleleOff | alleleText] (the text at indTextAt), the
+  // allele offsets on the host, its one table, the staging block of one _add call, and what _stats reports of the calls that were taken
+  T1kCountTable indTab;
+  T1kDevBuf bIndRef, bIndIn;
+  bool indOpen = false;
+  size_t indTextAt = 0;
+  std::vector<uint64_t> indOff;
+  uint64_t indEvents = 0, indShifted = 0, indEdgeDel = 0, indEdgeIns = 0;
   // read-backed phasing of site pairs (t1k_phase.hip), open from t1k_phase_begin to _end: its sites, its table of (site pair, state pair,
   // uniq) cells, the staging block of one _add call, that call's observation words and merge arena, and what _stats reports
   T1kSiteMap phMap;
