@@ -85,6 +85,22 @@ int orc_pair_rows(void *h, const int *l1, const double *s1, int n1, const int *l
   return (int)row.size();
 }
 
+// the posting list of one k-mer (k bases of ACGT) as buildIndex made it: the alleles of its postings in list order (allele, then offset),
+// at most cap of them written.  Returns the list's length, -1 for a k-mer of another length or with another letter.
+int orc_kmer_postings(void *h, const char *kmer, int *alleles, int cap) {
+  Oracle *o = (Oracle *)h;
+  const int k = o->prm.k;
+  if ((int)strlen(kmer) != k) return -1;
+  uint64_t code = 0;
+  for (int i = 0; i < k; ++i) {
+    const char c = kmer[i];
+    const int b = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
+    if (b < 0) return -1;
+    code = code << 2 | (uint64_t)b;
+  }
+  return o->kmerPostings(code, alleles, cap);
+}
+
 // per-base coverage of the allele's own base (the only counter GetSeqMissingBaseCoverage reads, SeqSet.hpp:2729)
 int orc_coverage(void *h, int allele, int *out, int cap) {
   Oracle *o = (Oracle *)h;

@@ -134,6 +134,11 @@ class Oracle {
   bool separatorInRange(int s, int e, int seqIdx) const;  // SeqSet.hpp:487-498
   int missingBaseCoverage(int seqIdx, double ratio) const;  // SeqSet.hpp:2717-2755
   void parseAlleleName(const std::string &allele, std::string &gene, std::string &major) const;  // Genotyper.hpp:63-131
+  int kmerPostings(uint64_t code, int *alleles, int cap) const {  // the alleles of a k-mer's postings in list order; returns the list's length
+    const uint32_t s = idxStart[code], e = idxStart[code + 1];
+    for (uint32_t j = s; j < e && (int)(j - s) < cap; ++j) alleles[j - s] = (int)idxPost[j].allele;
+    return (int)(e - s);
+  }
 
   // Genotyper::EMupdate (372-421) with the classes' lengths as an argument (their number is its size): what quantify's updates run
   static double emUpdate(const std::vector<double> &x0, std::vector<double> &x1, std::vector<double> &n,
