@@ -540,6 +540,28 @@ int t1k_cigar_batch(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const u
                     uint64_t *cigarPtr /* [n + 1] */, char *cigar, uint64_t cigarCap, uint64_t *mdPtr /* [n + 1] */, char *md, uint64_t mdCap,
                     uint32_t *nm /* [n] */, uint32_t *refSpan /* [n] */, double *kernelMs /* may be NULL */);
 
+/* ---- runner-up evidence per called allele (genotyper --alternatives) ----------------------------------------------------------
+ * Stateless; all pointers are host pointers.  The read groups as a CSR: group g holds the alleles entryAllele[groupPtr[g] .. groupPtr[g + 1]),
+ * strictly ascending, and weighs q[g] (the job: llrint(count[g] * 2^20), count[g] the group's count in the EM).  alleleGene[a] < nGenes is the
+ * gene of allele a; slotOf[a] = 2 * alleleGene[a] + k where a is the allele called in slot k (0 / 1) of its gene, 0xFFFFFFFF for every other
+ * allele; a slot belongs to at most one allele.  tables = four arrays of nAlleles sums of q, one after the other, over the groups that hold b:
+ *   total[b]    all of them;
+ *   both0[b]    those that also hold the allele of slot 0 of b's gene (none when the slot is empty; the called allele itself: its total);
+ *   both1[b]    the same for slot 1;
+ *   neither[b]  those that hold no called allele of b's gene.
+ * The sums are 64-bit integers (global atomic adds): the same bits for every launch shape, piece size and run.  The entries are uploaded in
+ * pieces cut at group boundaries, 2^24 entries each (env T1K_ALT_PIECE, in entries, read by every call); a group longer than a piece is a
+ * piece of its own.  t1k_alt_pieces: how many pieces a call with this groupPtr makes.
+ * Nothing is written unless the whole call is sound.  T1K_ERR_ARG: groupPtr[0] != 0 or a groupPtr that decreases; an entry >= nAlleles; the
+ * entries of a group not strictly ascending (a duplicate would count twice); an alleleGene >= nGenes; a slotOf that is neither 0xFFFFFFFF
+ * nor 2 * alleleGene[a] + {0, 1}; two alleles with one slotOf; a NULL array that would be read.  T1K_ERR_CAPACITY: the sum of q over all
+ * groups -- the bound of every cell -- could reach 2^63; 2^32 groups or more; more than 65536 genes (the slot bitsets of a workgroup, four
+ * of 2 * nGenes bits, must fit 64 KB of LDS).  nGroups == 0: T1K_OK, the tables are zeroed.  kernelMs (may be NULL): device time of the
+ * pieces' kernels. */
+int t1k_alt_batch(t1k_ctx *ctx, uint64_t nGroups, const uint64_t *groupPtr /* [nGroups + 1] */, const uint32_t *entryAllele, const uint64_t *q /* [nGroups] */, uint32_t nAlleles,
+                  const uint32_t *alleleGene /* [nAlleles] */, uint32_t nGenes, const uint32_t *slotOf /* [nAlleles] */, uint64_t *tables /* [4 * nAlleles] */, double *kernelMs /* may be NULL */);
+uint64_t t1k_alt_pieces(uint64_t nGroups, const uint64_t *groupPtr);
+
 /* ---- profiling counters of the last t1k_assign_batch (algorithmic-traffic terms of SURVEY.md 8d) --------------- */
 typedef struct {
   uint64_t read_ends, lookups, postings, hits, groups, candidates, extended, near_best, dp_calls, rows, batches;
@@ -613,6 +635,7 @@ typedef struct {
   int32_t device;                                                     /* GPU ordinal; -1 = host-only job (group bookkeeping only, cannot run) */
   int32_t output_read_assignment;                                     /* --outputReadAssignment */
   int32_t batch_fragments;                                            /* fragments per device batch (0 = default) */
+  int32_t alternatives;                                               /* --alternatives: alternatives listed per called allele, 1 .. 1000; 0 = no table */
 } t1k_job_params;
 void t1k_job_params_default(t1k_job_params *p);
 
@@ -652,10 +675,14 @@ int t1k_job_run(t1k_job *job);
 /* optional, before t1k_job_run: the *_aligned*.fa files (which only need the fragmentAssigned flags) are then written by background
  * threads while the classes are built and the EM runs; t1k_job_write_outputs with the same prefix waits for them */
 int t1k_job_set_output_prefix(t1k_job *job, const char *prefix);
-/* <prefix>_genotype.tsv, _allele.tsv, _aligned*.fa, (_assign.tsv) (Genotyper.cpp:653-718) */
+/* <prefix>_genotype.tsv, _allele.tsv, _aligned*.fa, (_assign.tsv) (Genotyper.cpp:653-718), (_alternatives.tsv: prm.alternatives > 0) */
 int t1k_job_write_outputs(t1k_job *job, const char *prefix);
 /* results in memory: one line per gene, same text as _genotype.tsv */
 int t1k_job_genotype_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
+/* after t1k_job_run of a job with prm.alternatives > 0 (the rank that writes the tables): the text of <prefix>_alternatives.tsv */
+int t1k_job_alternatives_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
+/* per allele of the job's reference, in its order: the gene (index into the lines of _genotype.tsv) and, after t1k_job_run, the abundance; either may be NULL */
+int t1k_job_allele_table(t1k_job *job, int32_t *gene, double *abundance, uint32_t *nAlleles);
 int t1k_job_counts(t1k_job *job, uint64_t *fragments, uint64_t *assignedFragments, uint64_t *groups, uint64_t *ecs, int32_t *emIterations);
 int t1k_job_stats(t1k_job *job, t1k_stats *out);
 t1k_ctx *t1k_job_ctx(t1k_job *job);

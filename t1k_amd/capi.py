@@ -31,7 +31,7 @@ class JobParams(C.Structure):
     _fields_ = [("dev", Params), ("filter_frac", C.c_double), ("filter_cov", C.c_double),
                 ("cross_gene_rate", C.c_double), ("squarem_min_alpha", C.c_double), ("allele_digit_units", C.c_int32),
                 ("allele_delimiter", C.c_char), ("threads", C.c_int32), ("device", C.c_int32),
-                ("output_read_assignment", C.c_int32), ("batch_fragments", C.c_int32)]
+                ("output_read_assignment", C.c_int32), ("batch_fragments", C.c_int32), ("alternatives", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -84,6 +84,8 @@ ROUTE_REC_DTYPE = np.dtype([("read_end", "<u4"), ("allele", "<u4"), ("n", "<u4")
 ROUTE_NAMES = ("general_lane", "wave_small", "wave_large", "big_by_size", "big_by_scratch")
 assert ROUTE_REC_DTYPE.itemsize == 20
 CIGAR_FILL = 0xAB  # what Context.cigar_batch fills its output arrays with before the call
+ALT_FILL = 0xCD    # what Context.alt_batch fills its tables with before the call
+ALT_EMPTY = 0xFFFFFFFF  # slotOf of an allele that is not called
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_void_p)
 
@@ -153,6 +155,11 @@ def lib():
     L.t1k_phase_stats.argtypes = [vp, u64p, u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]
     L.t1k_phase_end.argtypes = [vp]
     L.t1k_cigar_batch.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.POINTER(C.c_double)]
+    L.t1k_alt_batch.argtypes = [vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.POINTER(C.c_double)]
+    L.t1k_alt_pieces.argtypes = [C.c_uint64, vp]
+    L.t1k_alt_pieces.restype = C.c_uint64
+    L.t1k_job_alternatives_text.argtypes = [vp, C.c_char_p, C.c_uint64, u64p]
+    L.t1k_job_allele_table.argtypes = [vp, vp, vp, u32p]
     L.t1k_extract_batch.argtypes = [vp, C.c_uint32, vp, vp]
     L.t1k_extractor_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_stats_get.argtypes = [vp, C.POINTER(Stats)]
@@ -606,6 +613,26 @@ class Context:
         finally:
             self.pileup_end()
 
+    # runner-up evidence per called allele (t1k_alt_batch)
+    def alt_batch(self, group_ptr, entry_allele, q, allele_gene, n_genes, slot_of, raw=False):
+        """the read groups as a CSR (uint64 group_ptr [G + 1], uint32 entry_allele), uint64 q [G], uint32 allele_gene / slot_of [A] (ALT_EMPTY:
+        not called) -> (tables uint64 [4, A]: total, both0, both1, neither; the kernels' device time in ms).  raw=True: (status code, tables, ms)
+        without raising; the tables are filled with ALT_FILL bytes before the call."""
+        gp = np.ascontiguousarray(group_ptr, np.uint64)
+        ent = np.ascontiguousarray(entry_allele, np.uint32)
+        qq = np.ascontiguousarray(q, np.uint64)
+        ag = np.ascontiguousarray(allele_gene, np.uint32)
+        so = np.ascontiguousarray(slot_of, np.uint32)
+        assert len(ag) == len(so) and len(gp) == len(qq) + 1
+        tables = np.empty((4, len(ag)), np.uint64)
+        tables.view(np.uint8)[:] = ALT_FILL
+        ms = C.c_double()
+        rc = lib().t1k_alt_batch(self.h, len(qq), _ptr(gp), _ptr(ent), _ptr(qq), len(ag), _ptr(ag), n_genes, _ptr(so), _ptr(tables), C.byref(ms))
+        if raw:
+            return rc, tables, ms.value
+        self._check(rc, "t1k_alt_batch")
+        return tables, ms.value
+
     # CIGAR / MD / NM of alignments (t1k_cigar_batch; DESIGN §11.6)
     def cigar_batch(self, aln, ops, allele_off, allele_text, clip=None, cigar_cap=None, md_cap=None, raw=False):
         """aln: PILEUP_ALN_DTYPE records (read_at and the weights are ignored); ops: int8 edit columns; allele_text: the alleles' bases back
@@ -906,6 +933,12 @@ class Context:
             self.phase_end()
 
 
+def alt_pieces(group_ptr):
+    """pieces a t1k_alt_batch call with this group_ptr uploads its entries in (env T1K_ALT_PIECE as the call itself reads it)"""
+    gp = np.ascontiguousarray(group_ptr, np.uint64)
+    return int(lib().t1k_alt_pieces(max(len(gp) - 1, 0), _ptr(gp)))
+
+
 def pair_limits():
     """(LDS join capacity, first launch's fragment capacity, rank-sort tile, records per streamed round) of the pairing kernel as built"""
     out = np.zeros(4, dtype=np.uint32)
@@ -1162,6 +1195,22 @@ class Job:
         buf = C.create_string_buffer(need.value + 1)
         self._check(lib().t1k_job_genotype_text(self.h, buf, need.value + 1, C.byref(need)), "t1k_job_genotype_text")
         return buf.value.decode()
+
+    def alternatives_text(self):
+        """the text of <prefix>_alternatives.tsv (a job created with alternatives=N, after run())"""
+        need = C.c_uint64()
+        self._check(lib().t1k_job_alternatives_text(self.h, None, 0, C.byref(need)), "t1k_job_alternatives_text")
+        buf = C.create_string_buffer(need.value + 1)
+        self._check(lib().t1k_job_alternatives_text(self.h, buf, need.value + 1, C.byref(need)), "t1k_job_alternatives_text")
+        return buf.value.decode()
+
+    def allele_table(self):
+        """(gene int32 [A], abundance float64 [A]) of the job's alleles, in the order of its reference"""
+        n = C.c_uint32()
+        self._check(lib().t1k_job_allele_table(self.h, None, None, C.byref(n)), "t1k_job_allele_table")
+        gene, ab = np.zeros(n.value, np.int32), np.zeros(n.value, np.float64)
+        self._check(lib().t1k_job_allele_table(self.h, _ptr(gene), _ptr(ab), C.byref(n)), "t1k_job_allele_table")
+        return gene, ab
 
     def counts(self):
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()

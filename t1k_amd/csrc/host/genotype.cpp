@@ -721,4 +721,90 @@ std::string Genotyper::alleleLines() const {
   return out;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// --alternatives: runner-up evidence per called allele (t1k_alt.hip)
+// ------------------------------------------------------------------------------------------------------------------
+void Genotyper::calledAlleles(int gene, int called[2]) const {
+  const RefSet &R = *ref;
+  called[0] = called[1] = -1;
+  std::vector<char> shown(R.majorName.size(), 0);  // as geneLine: a major allele is printed once
+  int firstQual = -1;
+  for (int type = 0; type < 2; ++type) {
+    if (type == 1 && firstQual == 0) std::fill(shown.begin(), shown.end(), 0);
+    const std::vector<char> before = shown;
+    int qual = -1;
+    for (auto &s : selected[gene]) {
+      if (s.second != type) continue;
+      const AlleleMeta &m = R.al[s.first];
+      if (!shown[m.major]) { qual = m.quality; shown[m.major] = 1; }
+      if (before[m.major]) continue;
+      const int c = called[type];
+      if (c == -1 || R.al[c].ecAbundance < m.ecAbundance || (R.al[c].ecAbundance == m.ecAbundance && s.first < c)) called[type] = s.first;
+    }
+    if (qual < 0) called[type] = -1;  // (cannot differ from "no candidate"; kept beside geneLine's own test)
+    if (type == 0) firstQual = qual;
+  }
+}
+
+void Genotyper::alternativesInput(std::vector<uint32_t, NoInitAlloc<uint32_t>> &ent, std::vector<uint64_t> &q, std::vector<uint32_t> &alleleGene, std::vector<uint32_t> &slotOf,
+                                  std::vector<int> &called) const {
+  const RefSet &R = *ref;
+  const size_t A = R.al.size(), G = nGroups(), nGenes = R.geneName.size();
+  // q[g]: the count of the group's EM row (the largest weight of the row, as quantify forms it) in units of 2^-20
+  ent.resize(G ? groupPtr[G] : 0);
+  q.resize(G);
+  parallelFor(G, [&](size_t g) {
+    float c = groupEnt[groupPtr[g]].weight;
+    for (uint64_t p = groupPtr[g]; p < groupPtr[g + 1]; ++p) {
+      if (groupEnt[p].weight > c) c = groupEnt[p].weight;
+      ent[p] = (uint32_t)groupEnt[p].allele;
+    }
+    q[g] = (uint64_t)llrint((double)c * 1048576.0);
+  }, 8192);
+  alleleGene.resize(A);
+  slotOf.assign(A, 0xFFFFFFFFu);
+  for (size_t a = 0; a < A; ++a) alleleGene[a] = (uint32_t)R.al[a].gene;
+  called.assign(2 * nGenes, -1);
+  for (size_t g = 0; g < nGenes; ++g) {
+    calledAlleles((int)g, &called[2 * g]);
+    for (int k = 0; k < 2; ++k)
+      if (called[2 * g + k] >= 0) slotOf[called[2 * g + k]] = (uint32_t)(2 * g + k);
+  }
+}
+
+std::string Genotyper::alternativesText(const uint64_t *tab, const std::vector<int> &called, int top) const {
+  const RefSet &R = *ref;
+  const size_t A = R.al.size(), nGenes = R.geneName.size();
+  const uint64_t *total = tab, *both[2] = {tab + A, tab + 2 * A}, *neither = tab + 3 * A;
+  std::vector<std::vector<int>> ofGene(nGenes);
+  for (size_t a = 0; a < A; ++a) ofGene[R.al[a].gene].push_back((int)a);
+  std::string text = "#gene\tcalled\tslot\trank\talt\ttotal_called\ttotal_alt\tshared\tlost\tgained\tunexplained\talt_abundance\tidentical\n";
+  auto w = [](uint64_t v) { char b[64]; snprintf(b, sizeof b, "%.3f", (double)v / 1048576.0); return std::string(b); };
+  struct Alt { uint64_t lost, gained; int allele; };
+  char num[64];
+  for (size_t g = 0; g < nGenes; ++g)
+    for (int k = 0; k < 2; ++k) {
+      const int s = called[2 * g + k];
+      if (s < 0) continue;
+      std::vector<Alt> alts;
+      size_t identical = 0;
+      for (int b : ofGene[g]) {
+        if (b == s || total[b] == 0) continue;
+        const uint64_t shared = both[k][b], lost = total[s] - shared, gained = total[b] - shared;
+        if (lost == 0 && gained == 0) { ++identical; continue; }
+        alts.push_back(Alt{lost, gained, b});
+      }
+      std::sort(alts.begin(), alts.end(), [](const Alt &x, const Alt &y) { return x.lost != y.lost ? x.lost < y.lost : x.gained != y.gained ? x.gained > y.gained : x.allele < y.allele; });
+      const std::string head = R.geneName[g] + "\t" + R.al[s].name + "\t" + std::to_string(k) + "\t";
+      if (alts.empty()) text += head + "0\t.\t" + w(total[s]) + "\t" + w(0) + "\t" + w(0) + "\t" + w(0) + "\t" + w(0) + "\t" + w(0) + "\t0.000000\t" + std::to_string(identical) + "\n";
+      for (size_t i = 0; i < alts.size() && i < (size_t)top; ++i) {
+        const int b = alts[i].allele;
+        snprintf(num, sizeof(num), "%lf", R.al[b].abundance);
+        text += head + std::to_string(i + 1) + "\t" + R.al[b].name + "\t" + w(total[s]) + "\t" + w(total[b]) + "\t" + w(both[k][b]) + "\t" + w(alts[i].lost) + "\t" + w(alts[i].gained) + "\t" +
+                w(neither[b]) + "\t" + num + "\t" + std::to_string(identical) + "\n";
+      }
+    }
+  return text;
+}
+
 }  // namespace t1k

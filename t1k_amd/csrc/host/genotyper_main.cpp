@@ -44,6 +44,7 @@ static const char *kUsage =
     "\t--alleleDigitUnits INT: number of name units in the genotyping result (default: automatic)\n"
     "\t--alleleDelimiter CHR: delimiter of the name units (default: automatic)\n"
     "\t--outputReadAssignment: write prefix_assign.tsv\n"
+    "\t--alternatives [INT]: write prefix_alternatives.tsv, the INT closest other alleles of every called allele (default: 5; 1 to 1000)\n"
     "\t--squaremMinAlpha FLOAT: lower bound (negative) of the SQUAREM step length\n"
     "\t--device INT: GPU ordinal (default: $T1K_DEVICE or 0)\n"
     "\t--gpus INT: shard the fragments over the first INT GPUs ($T1K_GPUS=0,1,.. names them; a GPU may be named twice)\n";
@@ -55,7 +56,8 @@ int t1k_genotyper_main(int argc, char **argv) {
                                      {"barcode", required_argument, 0, 1003}, {"relaxIntronAlign", no_argument, 0, 1004},
                                      {"alleleDigitUnits", required_argument, 0, 1005}, {"alleleDelimiter", required_argument, 0, 1006},
                                      {"alleleWhitelist", required_argument, 0, 1007}, {"outputReadAssignment", no_argument, 0, 1008},
-                                     {"squaremMinAlpha", required_argument, 0, 1009}, {"device", required_argument, 0, 1010}, {"gpus", required_argument, 0, 1011}, {0, 0, 0, 0}};
+                                     {"squaremMinAlpha", required_argument, 0, 1009}, {"device", required_argument, 0, 1010}, {"gpus", required_argument, 0, 1011},
+                                     {"alternatives", optional_argument, 0, 1012}, {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
@@ -88,6 +90,15 @@ int t1k_genotyper_main(int argc, char **argv) {
       case 1009: p.squarem_min_alpha = atof(optarg); break;
       case 1010: p.device = atoi(optarg); break;
       case 1011: nGpus = atoi(optarg); break;
+      case 1012: {  // "--alternatives", "--alternatives=INT" or "--alternatives INT": the next word is the value unless it is an option
+        const char *v = optarg;
+        if (!v && optind < argc && argv[optind][0] != '-') v = argv[optind++];
+        char *end = nullptr;
+        const long n = v ? strtol(v, &end, 10) : 5;
+        if (v && (end == v || *end || n < 1 || n > 1000)) { fprintf(stderr, "genotyper: --alternatives takes an integer from 1 to 1000\n%s", kUsage); return EXIT_FAILURE; }
+        p.alternatives = (int32_t)n;
+        break;
+      }
       default: fprintf(stderr, "%s", kUsage); return EXIT_FAILURE;
     }
   }

@@ -3,6 +3,28 @@
 // points of the analyzer stage (host/variants.cpp behind the C ABI) and the job's result getters.
 #include "job_internal.h"
 
+// --alternatives: the four tables of t1k_alt_batch over the job's read groups and calls, ranked and formatted by the genotyper
+static int jobAlternatives(t1k_job *job) {
+  const double t0 = nowMs();
+  const Genotyper &gt = job->gt;
+  std::vector<uint32_t, NoInitAlloc<uint32_t>> ent;
+  std::vector<uint64_t> q;
+  std::vector<uint32_t> alleleGene, slotOf;
+  std::vector<int> called;
+  gt.alternativesInput(ent, q, alleleGene, slotOf, called);
+  const uint64_t G = gt.nGroups();
+  std::vector<uint64_t> tab(4 * alleleGene.size(), 0);
+  double kernelMs = 0;
+  const int rc = t1k_alt_batch(job->ctx, G, gt.groupPtr.data(), ent.data(), q.data(), (uint32_t)alleleGene.size(), alleleGene.data(), (uint32_t)job->ref.geneName.size(), slotOf.data(),
+                               tab.data(), &kernelMs);
+  if (rc != T1K_OK) return jobFail(job, rc, t1k_last_error(job->ctx));
+  job->altText = gt.alternativesText(tab.data(), called, job->prm.alternatives);
+  if (getenv("T1K_DEBUG_PHASES"))
+    fprintf(stderr, "[t1k job] alternatives: %llu groups, %llu entries, %llu pieces, kernel %.3f ms, total %.1f ms\n", (unsigned long long)G, (unsigned long long)ent.size(),
+            (unsigned long long)t1k_alt_pieces(G, gt.groupPtr.data()), kernelMs, nowMs() - t0);
+  return T1K_OK;
+}
+
 extern "C" {
 
 int t1k_job_finish(t1k_job *job) {
@@ -76,6 +98,11 @@ int t1k_job_finish(t1k_job *job) {
   gt.missingCoverageHook = nullptr;
   if (gt.hookFailed) return jobFail(job, hookRc != T1K_OK ? hookRc : T1K_ERR_INTERNAL, job->err);
   double t5 = nowMs();
+  job->altText.clear();
+  if (job->prm.alternatives > 0 && job->rank == 0) {  // the rank that writes _genotype.tsv, from the merged groups it holds: no exchange
+    if (job->prm.alternatives > 1000) return jobFail(job, T1K_ERR_ARG, "alternatives: 1 .. 1000 per called allele");
+    if ((rc = jobAlternatives(job)) != T1K_OK) return rc;
+  }
   job->msHost += (t3 - t2) + (t5 - t4); job->msEm = t4 - t3;
   job->stats.ms_total = job->msLoad + job->msDevice + job->msCoalesce + job->msHost + job->msEm;
   job->stats.ms_em = job->msEm;
@@ -270,6 +297,26 @@ int t1k_job_genotype_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *neede
   if (needed) *needed = s.size();
   if (buf && cap > s.size()) { memcpy(buf, s.data(), s.size()); buf[s.size()] = 0; }
   else if (buf) return T1K_ERR_ARG;
+  return T1K_OK;
+}
+
+int t1k_job_alternatives_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed) {
+  if (!job || !job->ran) return jobFail(job, T1K_ERR_STATE, "the job has not run");
+  if (job->prm.alternatives <= 0 || job->rank != 0) return jobFail(job, T1K_ERR_STATE, "the job keeps no alternatives table");
+  const std::string &s = job->altText;
+  if (needed) *needed = s.size();
+  if (buf && cap > s.size()) { memcpy(buf, s.data(), s.size()); buf[s.size()] = 0; }
+  else if (buf) return T1K_ERR_ARG;
+  return T1K_OK;
+}
+
+int t1k_job_allele_table(t1k_job *job, int32_t *gene, double *abundance, uint32_t *nAlleles) {
+  if (!job) return T1K_ERR_ARG;
+  if (nAlleles) *nAlleles = (uint32_t)job->ref.al.size();
+  for (size_t a = 0; a < job->ref.al.size(); ++a) {
+    if (gene) gene[a] = job->ref.al[a].gene;
+    if (abundance) abundance[a] = job->ref.al[a].abundance;
+  }
   return T1K_OK;
 }
 

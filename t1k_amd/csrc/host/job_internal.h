@@ -58,6 +58,7 @@ struct t1k_job {
   std::vector<char> whitelist;      // per allele, empty = everything allowed
   std::string abundanceFile;
   std::string assignText;           // --outputReadAssignment rows
+  std::string altText;              // --alternatives: the table (on the rank that writes _genotype.tsv)
   t1k_stats stats{};
   uint64_t distinctReadEnds = 0, readEnds = 0;
   double msLoad = 0, msDevice = 0, msHost = 0, msEm = 0, msCoalesce = 0, msWrite = 0;

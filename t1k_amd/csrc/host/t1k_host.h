@@ -200,6 +200,16 @@ struct Genotyper {
   std::string alleleLines() const;                           // OutputRepresentativeAlleles (2180-2229)
   void setAbundance(const double *ecReadCount, const std::vector<int> &ecLen);  // SetAlleleAbundance (957-1014)
   int geneTypes(int gene) const;                             // GetGeneAlleleTypes (1053-1069)
+  // --alternatives (no counterpart in the reference).  called[k]: the allele that stands for slot k of the gene -- among the
+  // selected alleles of type k whose major allele geneLine prints in field k, the one with the largest class abundance, the smallest index
+  // among equals (the allele _allele.tsv names for the type when its quality is not 0) -- or -1 where geneLine prints "."
+  void calledAlleles(int gene, int called[2]) const;
+  // what t1k_alt_batch takes, from this job's read groups and calls (called[2 * gene + k] as calledAlleles), and the text of
+  // <prefix>_alternatives.tsv from its four tables, `top` alternatives per called allele.  (The call itself is made by the job layer:
+  // this file stays free of device entry points other than the EM's.)
+  void alternativesInput(std::vector<uint32_t, NoInitAlloc<uint32_t>> &ent, std::vector<uint64_t> &q, std::vector<uint32_t> &alleleGene, std::vector<uint32_t> &slotOf,
+                         std::vector<int> &called) const;
+  std::string alternativesText(const uint64_t *tables, const std::vector<int> &called, int top) const;
 };
 
 // host/variants.cpp: novel-variant calling of the analyzer stage (VariantCaller.hpp), host code over the fragments' assignment lists and
