@@ -156,6 +156,8 @@ def lib():
     L.t1k_phase_end.argtypes = [vp]
     L.t1k_cigar_batch.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.POINTER(C.c_double)]
     L.t1k_alt_batch.argtypes = [vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.POINTER(C.c_double)]
+    L.t1k_ctx_mem_report.argtypes = [vp, C.c_char_p, C.c_int]
+    L.t1k_ctx_mem_report.restype = C.c_uint64
     L.t1k_alt_pieces.argtypes = [C.c_uint64, vp]
     L.t1k_alt_pieces.restype = C.c_uint64
     L.t1k_job_alternatives_text.argtypes = [vp, C.c_char_p, C.c_uint64, u64p]
@@ -260,6 +262,17 @@ def lib():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _u8(text):
+    """bytes, a bytearray or an array as a uint8 array"""
+    return np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+
+
+def _pieces(cuts, n):
+    """the (lo, hi) pieces of 0 .. n split at the indices `cuts`"""
+    edges = [0] + [int(c) for c in cuts] + [int(n)]
+    return zip(edges[:-1], edges[1:])
 
 
 def _concat(seqs):
@@ -581,8 +594,7 @@ class Context:
         """aln: PILEUP_ALN_DTYPE records; text: bytes (or uint8 array) of strand-corrected read bases; ops: int8 edit columns.  Returns the
         kernels' device time in ms"""
         a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
-        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
-        o = np.ascontiguousarray(ops, np.int8)
+        t, o = _u8(text), np.ascontiguousarray(ops, np.int8)
         ms = C.c_double()
         rc = lib().t1k_pileup_add(self.h, _ptr(a), len(a), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
         if raw:
@@ -607,8 +619,7 @@ class Context:
         a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
         self.pileup_begin(allele_off)
         try:
-            edges = [0] + [int(c) for c in cuts] + [len(a)]
-            ms = sum(self.pileup_add(a[lo:hi], text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
+            ms = sum(self.pileup_add(a[lo:hi], text, ops) for lo, hi in _pieces(cuts, len(a)))
             return self.pileup_get(), ms
         finally:
             self.pileup_end()
@@ -644,7 +655,7 @@ class Context:
         n = len(a)
         o = np.ascontiguousarray(ops, np.int8)
         off = np.ascontiguousarray(allele_off, np.uint64)
-        t = np.frombuffer(allele_text, np.uint8) if isinstance(allele_text, (bytes, bytearray)) else np.ascontiguousarray(allele_text, np.uint8)
+        t = _u8(allele_text)
         c = None if clip is None else np.ascontiguousarray(clip, np.uint32).reshape(-1)
         assert c is None or len(c) == 2 * n
         n_ops = a["n_ops"].astype(np.int64)
@@ -666,15 +677,62 @@ class Context:
         out["md"] = out["md"][:int(out["md_ptr"][n])]
         return out
 
-    # per-barcode pileup at sites (t1k_sitepile_begin / _add / _get / _end); raw=True returns the status code instead of raising
-    def sitepile_begin(self, allele_off, site_allele, site_pos, n_barcodes, raw=False):
+    # ---- the four sparse-table stages (sitepile, support, indel, phase): what their methods below share ----
+    def _done(self, rc, what, raw, value=None):
+        """the tail of a call: the status code as it is (raw), or checked, and then `value`"""
+        if raw:
+            return rc
+        self._check(rc, what)
+        return value
+
+    def _stage_begin(self, stage, allele_off, site_allele, site_pos, *more, raw=False):
         off = np.ascontiguousarray(allele_off, np.uint64)
         sa, sp = np.ascontiguousarray(site_allele, np.uint32), np.ascontiguousarray(site_pos, np.uint32)
         assert len(sa) == len(sp)
-        rc = lib().t1k_sitepile_begin(self.h, max(len(off) - 1, 0), _ptr(off), len(sa), _ptr(sa), _ptr(sp), int(n_barcodes))
-        if raw:
-            return rc
-        self._check(rc, "t1k_sitepile_begin")
+        what = "t1k_%s_begin" % stage
+        return self._done(getattr(lib(), what)(self.h, max(len(off) - 1, 0), _ptr(off), len(sa), _ptr(sa), _ptr(sp), *more), what, raw)
+
+    def _stage_add(self, stage, a, mid, text, ops, raw):
+        """mid: the stage's own arguments between (aln, n) and (text, textBytes, ops, opsBytes, kernelMs).  The kernels' device time in ms"""
+        t, o = _u8(text), np.ascontiguousarray(ops, np.int8)
+        ms = C.c_double()
+        what = "t1k_%s_add" % stage
+        rc = getattr(lib(), what)(self.h, _ptr(a), len(a), *mid, _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
+        return self._done(rc, what, raw, ms.value)
+
+    def _stage_get(self, stage, raw):
+        """the size query, then the runs: (keys uint64, counts int32)"""
+        get = getattr(lib(), "t1k_%s_get" % stage)
+        n = C.c_uint64()
+        rc = get(self.h, None, None, 0, C.byref(n))
+        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
+        if rc == 0 and n.value:
+            rc = get(self.h, _ptr(keys), _ptr(counts), n.value, C.byref(n))
+        return self._done(rc, "t1k_%s_get" % stage, raw, (keys, counts))
+
+    def _stage_stats(self, stage, n_counts, raw=False):
+        """the n_counts uint64 of t1k_<stage>_stats and its fold ms"""
+        v = [C.c_uint64() for _ in range(n_counts)]
+        ms = C.c_double()
+        rc = getattr(lib(), "t1k_%s_stats" % stage)(self.h, *[C.byref(x) for x in v], C.byref(ms))
+        return self._done(rc, "t1k_%s_stats" % stage, raw, tuple(x.value for x in v) + (ms.value,))
+
+    def _stage_end(self, stage, raw):
+        return self._done(getattr(lib(), "t1k_%s_end" % stage)(self.h), "t1k_%s_end" % stage, raw)
+
+    def _stage_run(self, stage, n, add, stats, cuts):
+        """behind the stage's _begin: add(lo, hi) for each piece of 0 .. n split at `cuts`, get, stats(), end: (keys, counts, summed ms, what
+        stats() gives)"""
+        try:
+            ms = sum(add(lo, hi) for lo, hi in _pieces(cuts, n))
+            keys, counts = self._stage_get(stage, False)
+            return keys, counts, ms, stats()
+        finally:
+            self._stage_end(stage, False)
+
+    # per-barcode pileup at sites (t1k_sitepile_begin / _add / _get / _end; DESIGN §11.4); raw=True returns the status code instead of raising
+    def sitepile_begin(self, allele_off, site_allele, site_pos, n_barcodes, raw=False):
+        return self._stage_begin("sitepile", allele_off, site_allele, site_pos, int(n_barcodes), raw=raw)
 
     def sitepile_add(self, aln, book_ptr, book, text, ops, raw=False):
         """aln: PILEUP_ALN_DTYPE records; record i books once per entry of book[book_ptr[i]:book_ptr[i + 1]] (barcode << 1 | uniq); text / ops
@@ -682,62 +740,31 @@ class Context:
         a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
         bp, bk = np.ascontiguousarray(book_ptr, np.uint64), np.ascontiguousarray(book, np.uint32)
         assert len(bp) == len(a) + 1
-        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
-        o = np.ascontiguousarray(ops, np.int8)
-        ms = C.c_double()
-        rc = lib().t1k_sitepile_add(self.h, _ptr(a), len(a), _ptr(bp), _ptr(bk), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
-        if raw:
-            return rc
-        self._check(rc, "t1k_sitepile_add")
-        return ms.value
+        return self._stage_add("sitepile", a, (_ptr(bp), _ptr(bk)), text, ops, raw)
 
     def sitepile_get(self, raw=False):
         """the table's runs, ascending: (keys uint64, counts int32); key = ((barcode * nSites + site) * 7 + plane) * 2 + (1 - uniq)"""
-        n = C.c_uint64()
-        rc = lib().t1k_sitepile_get(self.h, None, None, 0, C.byref(n))
-        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
-        if rc == 0 and n.value:
-            rc = lib().t1k_sitepile_get(self.h, _ptr(keys), _ptr(counts), n.value, C.byref(n))
-        if raw:
-            return rc
-        self._check(rc, "t1k_sitepile_get")
-        return keys, counts
+        return self._stage_get("sitepile", raw)
 
     def sitepile_stats(self):
         """(keys emitted, folds, device ms of the folds) of the open table"""
-        k, f, ms = C.c_uint64(), C.c_uint64(), C.c_double()
-        self._check(lib().t1k_sitepile_stats(self.h, C.byref(k), C.byref(f), C.byref(ms)), "t1k_sitepile_stats")
-        return k.value, f.value, ms.value
+        return self._stage_stats("sitepile", 2)
 
     def sitepile_end(self, raw=False):
-        rc = lib().t1k_sitepile_end(self.h)
-        if raw:
-            return rc
-        self._check(rc, "t1k_sitepile_end")
+        return self._stage_end("sitepile", raw)
 
     def sitepile(self, allele_off, site_allele, site_pos, n_barcodes, aln, book_ptr, book, text, ops, cuts=()):
         """begin, add (the records split at the indices `cuts` into several calls), get, end: (keys, counts, kernels' ms, folds)"""
         a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
         bp = np.ascontiguousarray(book_ptr, np.uint64)
         self.sitepile_begin(allele_off, site_allele, site_pos, n_barcodes)
-        try:
-            edges = [0] + [int(c) for c in cuts] + [len(a)]
-            ms = sum(self.sitepile_add(a[lo:hi], bp[lo:hi + 1], book, text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
-            keys, counts = self.sitepile_get()
-            return keys, counts, ms, self.sitepile_stats()[1]
-        finally:
-            self.sitepile_end()
+        return self._stage_run("sitepile", len(a),
+                               lambda lo, hi: self.sitepile_add(a[lo:hi], bp[lo:hi + 1], book, text, ops), lambda: self.sitepile_stats()[1], cuts)
 
     # strand / mate / end-distance / template support at sites (t1k_support_begin / _add / _get / _stats / _end; DESIGN §11.7); raw=True returns the status
     # code instead of raising
     def support_begin(self, allele_off, site_allele, site_pos, raw=False):
-        off = np.ascontiguousarray(allele_off, np.uint64)
-        sa, sp = np.ascontiguousarray(site_allele, np.uint32), np.ascontiguousarray(site_pos, np.uint32)
-        assert len(sa) == len(sp)
-        rc = lib().t1k_support_begin(self.h, max(len(off) - 1, 0), _ptr(off), len(sa), _ptr(sa), _ptr(sp))
-        if raw:
-            return rc
-        self._check(rc, "t1k_support_begin")
+        return self._stage_begin("support", allele_off, site_allele, site_pos, raw=raw)
 
     def support_add(self, aln, rec, book_ptr, book, text, ops, raw=False):
         """aln: PILEUP_ALN_DTYPE records; rec: one SUPPORT_REC_DTYPE per record (its read-end's length, the bases in front of the window, the
@@ -747,40 +774,20 @@ class Context:
         rc_ = np.ascontiguousarray(rec, SUPPORT_REC_DTYPE)
         bp, bk = np.ascontiguousarray(book_ptr, np.uint64), np.ascontiguousarray(book, SUPPORT_BOOK_DTYPE)
         assert len(bp) == len(a) + 1 and len(rc_) == len(a)
-        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
-        o = np.ascontiguousarray(ops, np.int8)
-        ms = C.c_double()
-        rc = lib().t1k_support_add(self.h, _ptr(a), len(a), _ptr(rc_), _ptr(bp), _ptr(bk), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
-        if raw:
-            return rc
-        self._check(rc, "t1k_support_add")
-        return ms.value
+        return self._stage_add("support", a, (_ptr(rc_), _ptr(bp), _ptr(bk)), text, ops, raw)
 
     def support_get(self, raw=False):
         """the table's runs, ascending: (keys uint64, counts int32).  Below SUPPORT_FAMILY_B: key = ((((site * 7 + state) * 2 + strand) * 2 + mate)
         * 512 + d) * 2 + (1 - uniq); from there on: SUPPORT_FAMILY_B | ((site * 7 + state) * 2 + orient) << 24 | dStart << 12 | dEnd, one run per
         distinct template"""
-        n = C.c_uint64()
-        rc = lib().t1k_support_get(self.h, None, None, 0, C.byref(n))
-        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
-        if rc == 0 and n.value:
-            rc = lib().t1k_support_get(self.h, _ptr(keys), _ptr(counts), n.value, C.byref(n))
-        if raw:
-            return rc
-        self._check(rc, "t1k_support_get")
-        return keys, counts
+        return self._stage_get("support", raw)
 
     def support_stats(self):
         """(keys emitted, folds, device ms of the folds) of the open table"""
-        k, f, ms = C.c_uint64(), C.c_uint64(), C.c_double()
-        self._check(lib().t1k_support_stats(self.h, C.byref(k), C.byref(f), C.byref(ms)), "t1k_support_stats")
-        return k.value, f.value, ms.value
+        return self._stage_stats("support", 2)
 
     def support_end(self, raw=False):
-        rc = lib().t1k_support_end(self.h)
-        if raw:
-            return rc
-        self._check(rc, "t1k_support_end")
+        return self._stage_end("support", raw)
 
     def support(self, allele_off, site_allele, site_pos, aln, rec, book_ptr, book, text, ops, cuts=()):
         """begin, add (the records split at the indices `cuts` into several calls), get, end: (keys, counts, kernels' ms, folds)"""
@@ -788,24 +795,16 @@ class Context:
         rc_ = np.ascontiguousarray(rec, SUPPORT_REC_DTYPE)
         bp = np.ascontiguousarray(book_ptr, np.uint64)
         self.support_begin(allele_off, site_allele, site_pos)
-        try:
-            edges = [0] + [int(c) for c in cuts] + [len(a)]
-            ms = sum(self.support_add(a[lo:hi], rc_[lo:hi], bp[lo:hi + 1], book, text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
-            keys, counts = self.support_get()
-            return keys, counts, ms, self.support_stats()[1]
-        finally:
-            self.support_end()
+        return self._stage_run("support", len(a),
+                               lambda lo, hi: self.support_add(a[lo:hi], rc_[lo:hi], bp[lo:hi + 1], book, text, ops), lambda: self.support_stats()[1], cuts)
 
     # novel indel evidence, left-aligned (t1k_indel_begin / _add / _get / _stats / _end); raw=True returns the status code instead of raising
     def indel_begin(self, allele_off, allele_text, raw=False):
         """allele_text: the alleles' bases back to back (bytes or uint8, A C G T N), allele a at allele_text[allele_off[a]:allele_off[a + 1]]"""
         off = np.ascontiguousarray(allele_off, np.uint64)
-        t = np.frombuffer(allele_text, np.uint8) if isinstance(allele_text, (bytes, bytearray)) else np.ascontiguousarray(allele_text, np.uint8)
+        t = _u8(allele_text)
         assert len(off) == 0 or len(t) == int(off[-1])
-        rc = lib().t1k_indel_begin(self.h, max(len(off) - 1, 0), _ptr(off), _ptr(t))
-        if raw:
-            return rc
-        self._check(rc, "t1k_indel_begin")
+        return self._done(lib().t1k_indel_begin(self.h, max(len(off) - 1, 0), _ptr(off), _ptr(t)), "t1k_indel_begin", raw)
 
     def indel_add(self, aln, strand, book_ptr, book_uniq, text, ops, raw=False):
         """aln: PILEUP_ALN_DTYPE records; strand: one uint8 per record (0 forward, 1 reverse); record i books once per entry of
@@ -815,41 +814,20 @@ class Context:
         s = np.ascontiguousarray(strand, np.uint8)
         bp, bk = np.ascontiguousarray(book_ptr, np.uint64), np.ascontiguousarray(book_uniq, np.uint8)
         assert len(bp) == len(a) + 1 and len(s) == len(a)
-        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
-        o = np.ascontiguousarray(ops, np.int8)
-        ms = C.c_double()
-        rc = lib().t1k_indel_add(self.h, _ptr(a), len(a), _ptr(s), _ptr(bp), _ptr(bk), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
-        if raw:
-            return rc
-        self._check(rc, "t1k_indel_add")
-        return ms.value
+        return self._stage_add("indel", a, (_ptr(s), _ptr(bp), _ptr(bk)), text, ops, raw)
 
     def indel_get(self, raw=False):
         """the table's runs, ascending: (keys uint64, counts int32); key = ((((g << 2 | type) << 27 | payload) << 1 | strand) << 1) | (1 - uniq)
         with g = allele_off[allele] + the normalised position, type 0 DEL (payload = length), 1 short INS (payload = 1 << 2 L | bases),
         2 long INS (payload = length)"""
-        n = C.c_uint64()
-        rc = lib().t1k_indel_get(self.h, None, None, 0, C.byref(n))
-        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
-        if rc == 0 and n.value:
-            rc = lib().t1k_indel_get(self.h, _ptr(keys), _ptr(counts), n.value, C.byref(n))
-        if raw:
-            return rc
-        self._check(rc, "t1k_indel_get")
-        return keys, counts
+        return self._stage_get("indel", raw)
 
     def indel_stats(self):
         """(events, shifted, edge del columns x bookings, edge ins columns x bookings, keys emitted, folds, device ms of the folds) of the open table"""
-        v = [C.c_uint64() for _ in range(6)]
-        ms = C.c_double()
-        self._check(lib().t1k_indel_stats(self.h, *[C.byref(x) for x in v], C.byref(ms)), "t1k_indel_stats")
-        return tuple(x.value for x in v) + (ms.value,)
+        return self._stage_stats("indel", 6)
 
     def indel_end(self, raw=False):
-        rc = lib().t1k_indel_end(self.h)
-        if raw:
-            return rc
-        self._check(rc, "t1k_indel_end")
+        return self._stage_end("indel", raw)
 
     def indel(self, allele_off, allele_text, aln, strand, book_ptr, book_uniq, text, ops, cuts=()):
         """begin, add (the records split at the indices `cuts` into several calls), get, stats, end: (keys, counts, kernels' ms, stats)"""
@@ -857,23 +835,12 @@ class Context:
         s = np.ascontiguousarray(strand, np.uint8)
         bp = np.ascontiguousarray(book_ptr, np.uint64)
         self.indel_begin(allele_off, allele_text)
-        try:
-            edges = [0] + [int(c) for c in cuts] + [len(a)]
-            ms = sum(self.indel_add(a[lo:hi], s[lo:hi], bp[lo:hi + 1], book_uniq, text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
-            keys, counts = self.indel_get()
-            return keys, counts, ms, self.indel_stats()
-        finally:
-            self.indel_end()
+        return self._stage_run("indel", len(a),
+                               lambda lo, hi: self.indel_add(a[lo:hi], s[lo:hi], bp[lo:hi + 1], book_uniq, text, ops), self.indel_stats, cuts)
 
     # read-backed phasing of site pairs (t1k_phase_begin / _add / _get / _stats / _end); raw=True returns the status code instead of raising
     def phase_begin(self, allele_off, site_allele, site_pos, raw=False):
-        off = np.ascontiguousarray(allele_off, np.uint64)
-        sa, sp = np.ascontiguousarray(site_allele, np.uint32), np.ascontiguousarray(site_pos, np.uint32)
-        assert len(sa) == len(sp)
-        rc = lib().t1k_phase_begin(self.h, max(len(off) - 1, 0), _ptr(off), len(sa), _ptr(sa), _ptr(sp))
-        if raw:
-            return rc
-        self._check(rc, "t1k_phase_begin")
+        return self._stage_begin("phase", allele_off, site_allele, site_pos, raw=raw)
 
     def phase_add(self, aln, book_rec, book_uniq, text, ops, raw=False):
         """aln: PILEUP_ALN_DTYPE records; booking b is the fragment-assignment of records book_rec[b] = (rec1, rec2 or PHASE_NO_MATE), both
@@ -882,55 +849,31 @@ class Context:
         a = np.ascontiguousarray(aln, PILEUP_ALN_DTYPE)
         br, bu = np.ascontiguousarray(book_rec, np.uint32).reshape(-1, 2), np.ascontiguousarray(book_uniq, np.uint8)
         assert len(br) == len(bu)
-        t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
-        o = np.ascontiguousarray(ops, np.int8)
-        ms = C.c_double()
-        rc = lib().t1k_phase_add(self.h, _ptr(a), len(a), len(bu), _ptr(br), _ptr(bu), _ptr(t), len(t), _ptr(o), len(o), C.byref(ms))
-        if raw:
-            return rc
-        self._check(rc, "t1k_phase_add")
-        return ms.value
+        return self._stage_add("phase", a, (len(bu), _ptr(br), _ptr(bu)), text, ops, raw)
 
     def phase_get(self, raw=False):
         """the table's runs, ascending: (keys uint64, counts int32); key = (((s * nSites + t) * 36 + x * 6 + y) << 1) | (1 - uniq)"""
-        n = C.c_uint64()
-        rc = lib().t1k_phase_get(self.h, None, None, 0, C.byref(n))
-        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
-        if rc == 0 and n.value:
-            rc = lib().t1k_phase_get(self.h, _ptr(keys), _ptr(counts), n.value, C.byref(n))
-        if raw:
-            return rc
-        self._check(rc, "t1k_phase_get")
-        return keys, counts
+        return self._stage_get("phase", raw)
 
     def phase_stats(self, raw=False):
         """{observations, bookings (with two observed sites or more), keys, discordant, folds, fold_ms} of the open table"""
-        v = [C.c_uint64() for _ in range(5)]
-        ms = C.c_double()
-        rc = lib().t1k_phase_stats(self.h, *[C.byref(x) for x in v], C.byref(ms))
-        if raw:
-            return rc
-        self._check(rc, "t1k_phase_stats")
-        return dict(zip(("observations", "bookings", "keys", "discordant", "folds"), (x.value for x in v)), fold_ms=ms.value)
+        v = self._stage_stats("phase", 5, raw)
+        return v if raw else dict(zip(("observations", "bookings", "keys", "discordant", "folds", "fold_ms"), v))
 
     def phase_end(self, raw=False):
-        rc = lib().t1k_phase_end(self.h)
-        if raw:
-            return rc
-        self._check(rc, "t1k_phase_end")
+        return self._stage_end("phase", raw)
 
     def phase(self, allele_off, site_allele, site_pos, aln, book_rec, book_uniq, text, ops, cuts=()):
         """begin, add, get, end: (keys, counts, kernels' ms, stats).  cuts: booking indices at which the bookings are split into several
         calls; every call gets all the records"""
         br, bu = np.ascontiguousarray(book_rec, np.uint32).reshape(-1, 2), np.ascontiguousarray(book_uniq, np.uint8)
         self.phase_begin(allele_off, site_allele, site_pos)
-        try:
-            edges = [0] + [int(c) for c in cuts] + [len(bu)]
-            ms = sum(self.phase_add(aln, br[lo:hi], bu[lo:hi], text, ops) for lo, hi in zip(edges[:-1], edges[1:]))
-            keys, counts = self.phase_get()
-            return keys, counts, ms, self.phase_stats()
-        finally:
-            self.phase_end()
+        return self._stage_run("phase", len(bu),
+                               lambda lo, hi: self.phase_add(aln, br[lo:hi], bu[lo:hi], text, ops), self.phase_stats, cuts)
+
+    def mem_bytes(self):
+        """bytes of device memory the context holds right now (t1k_ctx_mem_report, nothing printed)"""
+        return int(lib().t1k_ctx_mem_report(self.h, None, 0))
 
 
 def alt_pieces(group_ptr):

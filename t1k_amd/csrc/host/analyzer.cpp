@@ -1,6 +1,7 @@
 // t1k_amd/csrc/host/analyzer.cpp -- t1k_analyzer_main(): the post-analysis stage (Analyzer.cpp:236-733 as run-t1k:438-449 starts it)
 // on top of the job layer: re-assignment to the selected alleles, novel variants, per-barcode summary.
 #include <cerrno>
+#include <functional>
 #include <numeric>
 #include <tuple>
 #include "job_internal.h"
@@ -738,6 +739,37 @@ AnalyzerSiteList::AnalyzerSiteList(t1k_job *job, const AnalyzerVariants &V, cons
   }
 }
 
+// the replay session of the four sparse-table stages, behind the stage's _begin (rcBegin: what it returned): every kept piece
+// through add(piece, &ms), the stage's _add; then its two-call _get, stats() and its _end.  keys / counts: the table's runs; msKernels, nRecs:
+// summed over the pieces.  A failure is the job's (jobFail) and closes the session if it was open
+static bool analyzerReplay(t1k_job *job, int rcBegin, const AnalyzerSitepile &sp, const std::function<int(const AnalyzerSitepile::Piece &, double *)> &add,
+                           int (*get)(t1k_ctx *, uint64_t *, int32_t *, uint64_t, uint64_t *), const std::function<int()> &stats, int (*end)(t1k_ctx *), std::vector<uint64_t> &keys,
+                           std::vector<int32_t> &counts, double &msKernels, uint64_t &nRecs) {
+  t1k_ctx *ctx = job->ctx;
+  auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
+  int rc = rcBegin;
+  if (rc != T1K_OK) return fail(rc);
+  for (const AnalyzerSitepile::Piece &pc : sp.pieces) {
+    double ms = 0;
+    if ((rc = add(pc, &ms)) != T1K_OK) {
+      fail(rc);
+      end(ctx);
+      return false;
+    }
+    msKernels += ms;
+    nRecs += pc.recs.size();
+  }
+  uint64_t nRuns = 0;
+  if ((rc = get(ctx, nullptr, nullptr, 0, &nRuns)) == T1K_OK && nRuns) {
+    keys.resize(nRuns); counts.resize(nRuns);
+    rc = get(ctx, keys.data(), counts.data(), nRuns, &nRuns);
+  }
+  if (rc == T1K_OK) rc = stats();
+  if (rc != T1K_OK) { fail(rc); end(ctx); return false; }
+  if ((rc = end(ctx)) != T1K_OK) return fail(rc);
+  return true;
+}
+
 // <prefix>_barcode_pileup.tsv: the kept pieces through t1k_sitepile_add at the sites, the runs that come back merged per (barcode, site)
 // and written in barcode id order (the order of the lines of _barcode_expr.tsv), then allele, then pos
 static bool analyzerSitepile(t1k_job *job, const std::string &prefix, const AnalyzerVariants &V, const AnalyzerSitepile &sp, const AnalyzerSiteList &L,
@@ -749,32 +781,14 @@ static bool analyzerSitepile(t1k_job *job, const std::string &prefix, const Anal
   const std::vector<uint64_t> &refOff = L.refOff;
   const std::vector<int> &exonPos = L.exonPos;
   t1k_ctx *ctx = job->ctx;
-  auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
-  int rc;
   double msKernels = 0, msFold = 0;
-  uint64_t nRecs = 0, nRuns = 0, emitted = 0, folds = 0;
+  uint64_t nRecs = 0, emitted = 0, folds = 0;
   std::vector<uint64_t> keys;
   std::vector<int32_t> counts;
-  if (nSites) {
-    if ((rc = t1k_sitepile_begin(ctx, (uint32_t)A, refOff.data(), nSites, siteAllele.data(), sitePos.data(), barcodeNames.size())) != T1K_OK) return fail(rc);
-    for (const AnalyzerSitepile::Piece &pc : sp.pieces) {
-      double ms = 0;
-      if ((rc = t1k_sitepile_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), pc.bookPtr.data(), pc.book.data(), pc.pat.data(), pc.pat.size(), V.ops.data() + pc.ops0, pc.ops1 - pc.ops0, &ms)) != T1K_OK) {
-        fail(rc);
-        t1k_sitepile_end(ctx);
-        return false;
-      }
-      msKernels += ms;
-      nRecs += pc.recs.size();
-    }
-    if ((rc = t1k_sitepile_get(ctx, nullptr, nullptr, 0, &nRuns)) == T1K_OK && nRuns) {
-      keys.resize(nRuns); counts.resize(nRuns);
-      rc = t1k_sitepile_get(ctx, keys.data(), counts.data(), nRuns, &nRuns);
-    }
-    if (rc == T1K_OK) rc = t1k_sitepile_stats(ctx, &emitted, &folds, &msFold);
-    if (rc != T1K_OK) { fail(rc); t1k_sitepile_end(ctx); return false; }
-    if ((rc = t1k_sitepile_end(ctx)) != T1K_OK) return fail(rc);
-  }
+  if (nSites && !analyzerReplay(job, t1k_sitepile_begin(ctx, (uint32_t)A, refOff.data(), nSites, siteAllele.data(), sitePos.data(), barcodeNames.size()), sp,
+        [&](const AnalyzerSitepile::Piece &pc, double *ms) {
+          return t1k_sitepile_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), pc.bookPtr.data(), pc.book.data(), pc.pat.data(), pc.pat.size(), V.ops.data() + pc.ops0, pc.ops1 - pc.ops0, ms);
+        }, t1k_sitepile_get, [&] { return t1k_sitepile_stats(ctx, &emitted, &folds, &msFold); }, t1k_sitepile_end, keys, counts, msKernels, nRecs)) return false;
   const double tw = nowMs();
   FILE *fp = fopen((prefix + "_barcode_pileup.tsv").c_str(), "w");
   if (!fp) { fprintf(stderr, "analyzer: cannot write %s_barcode_pileup.tsv\n", prefix.c_str()); return false; }
@@ -824,34 +838,16 @@ static bool analyzerPhase(t1k_job *job, const std::string &prefix, const Analyze
   const RefSet &R = job->ref;
   const size_t A = R.seqs.size(), nSites = L.sites.size();
   t1k_ctx *ctx = job->ctx;
-  auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
-  int rc;
   double msKernels = 0, msFold = 0;
-  uint64_t nRecs = 0, nBook = 0, nRuns = 0, nObs = 0, nPaired = 0, emitted = 0, discordant = 0, folds = 0;
+  uint64_t nRecs = 0, nBook = 0, nObs = 0, nPaired = 0, emitted = 0, discordant = 0, folds = 0;
   std::vector<uint64_t> keys;
   std::vector<int32_t> counts;
-  if (nSites) {
-    if ((rc = t1k_phase_begin(ctx, (uint32_t)A, L.refOff.data(), nSites, L.siteAllele.data(), L.sitePos.data())) != T1K_OK) return fail(rc);
-    for (const AnalyzerSitepile::Piece &pc : sp.pieces) {
-      double ms = 0;
-      if ((rc = t1k_phase_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), (uint32_t)pc.asgUniq.size(), pc.asgRec.data(), pc.asgUniq.data(), pc.pat.data(), pc.pat.size(),
-                              V.ops.data() + pc.ops0, pc.ops1 - pc.ops0, &ms)) != T1K_OK) {
-        fail(rc);
-        t1k_phase_end(ctx);
-        return false;
-      }
-      msKernels += ms;
-      nRecs += pc.recs.size();
-      nBook += pc.asgUniq.size();
-    }
-    if ((rc = t1k_phase_get(ctx, nullptr, nullptr, 0, &nRuns)) == T1K_OK && nRuns) {
-      keys.resize(nRuns); counts.resize(nRuns);
-      rc = t1k_phase_get(ctx, keys.data(), counts.data(), nRuns, &nRuns);
-    }
-    if (rc == T1K_OK) rc = t1k_phase_stats(ctx, &nObs, &nPaired, &emitted, &discordant, &folds, &msFold);
-    if (rc != T1K_OK) { fail(rc); t1k_phase_end(ctx); return false; }
-    if ((rc = t1k_phase_end(ctx)) != T1K_OK) return fail(rc);
-  }
+  if (nSites && !analyzerReplay(job, t1k_phase_begin(ctx, (uint32_t)A, L.refOff.data(), nSites, L.siteAllele.data(), L.sitePos.data()), sp,
+        [&](const AnalyzerSitepile::Piece &pc, double *ms) {
+          nBook += pc.asgUniq.size();
+          return t1k_phase_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), (uint32_t)pc.asgUniq.size(), pc.asgRec.data(), pc.asgUniq.data(), pc.pat.data(), pc.pat.size(),
+                               V.ops.data() + pc.ops0, pc.ops1 - pc.ops0, ms);
+        }, t1k_phase_get, [&] { return t1k_phase_stats(ctx, &nObs, &nPaired, &emitted, &discordant, &folds, &msFold); }, t1k_phase_end, keys, counts, msKernels, nRecs)) return false;
   const double tw = nowMs();
   FILE *fp = fopen((prefix + "_allele_phase.tsv").c_str(), "w");
   if (!fp) { fprintf(stderr, "analyzer: cannot write %s_allele_phase.tsv\n", prefix.c_str()); return false; }
@@ -902,34 +898,17 @@ static bool analyzerSupport(t1k_job *job, const std::string &prefix, const Analy
   const RefSet &R = job->ref;
   const size_t A = R.seqs.size(), nSites = L.sites.size();
   t1k_ctx *ctx = job->ctx;
-  auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
-  int rc;
   double msKernels = 0, msFold = 0;
-  uint64_t nRecs = 0, nBook = 0, nRuns = 0, emitted = 0, folds = 0;
+  uint64_t nRecs = 0, nBook = 0, emitted = 0, folds = 0;
   std::vector<uint64_t> keys;
   std::vector<int32_t> counts;
-  if (nSites) {
-    if ((rc = t1k_support_begin(ctx, (uint32_t)A, L.refOff.data(), nSites, L.siteAllele.data(), L.sitePos.data())) != T1K_OK) return fail(rc);
-    for (const AnalyzerSitepile::Piece &pc : sp.pieces) {
-      double ms = 0;
-      if ((rc = t1k_support_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), pc.supRec.data(), pc.supBookPtr.data(), pc.supBook.data(), pc.pat.data(), pc.pat.size(),
-                                V.ops.data() + pc.ops0, pc.ops1 - pc.ops0, &ms)) != T1K_OK) {
-        fail(rc);
-        t1k_support_end(ctx);
-        return false;
-      }
-      msKernels += ms;
-      nRecs += pc.recs.size();
-      nBook += pc.supBook.size();
-    }
-    if ((rc = t1k_support_get(ctx, nullptr, nullptr, 0, &nRuns)) == T1K_OK && nRuns) {
-      keys.resize(nRuns); counts.resize(nRuns);
-      rc = t1k_support_get(ctx, keys.data(), counts.data(), nRuns, &nRuns);
-    }
-    if (rc == T1K_OK) rc = t1k_support_stats(ctx, &emitted, &folds, &msFold);
-    if (rc != T1K_OK) { fail(rc); t1k_support_end(ctx); return false; }
-    if ((rc = t1k_support_end(ctx)) != T1K_OK) return fail(rc);
-  }
+  if (nSites && !analyzerReplay(job, t1k_support_begin(ctx, (uint32_t)A, L.refOff.data(), nSites, L.siteAllele.data(), L.sitePos.data()), sp,
+        [&](const AnalyzerSitepile::Piece &pc, double *ms) {
+          nBook += pc.supBook.size();
+          return t1k_support_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), pc.supRec.data(), pc.supBookPtr.data(), pc.supBook.data(), pc.pat.data(), pc.pat.size(),
+                                 V.ops.data() + pc.ops0, pc.ops1 - pc.ops0, ms);
+        }, t1k_support_get, [&] { return t1k_support_stats(ctx, &emitted, &folds, &msFold); }, t1k_support_end, keys, counts, msKernels, nRecs)) return false;
+  const uint64_t nRuns = keys.size();
   const double tw = nowMs();
   FILE *fp = fopen((prefix + "_allele_support.tsv").c_str(), "w");
   if (!fp) { fprintf(stderr, "analyzer: cannot write %s_allele_support.tsv\n", prefix.c_str()); return false; }
@@ -1008,8 +987,6 @@ static bool analyzerIndels(t1k_job *job, const std::string &prefix, const Analyz
     const RefSet &R = job->ref;
     const size_t A = R.seqs.size();
     t1k_ctx *ctx = job->ctx;
-    auto fail = [&](int rc) { jobFail(job, rc, std::string("analyzer: ") + t1k_last_error(ctx)); fprintf(stderr, "analyzer: %s\n", t1k_job_last_error(job)); return false; };
-    int rc;
     // the alleles' bases back to back, reduced to A C G T N
     refOff.assign(A + 1, 0);
     for (size_t a = 0; a < A; ++a) refOff[a + 1] = refOff[a] + R.seqs[a].size();
@@ -1019,25 +996,12 @@ static bool analyzerIndels(t1k_job *job, const std::string &prefix, const Analyz
       for (char c : sq) { const char u = (char)toupper((unsigned char)c); refText += (u == 'A' || u == 'C' || u == 'G' || u == 'T') ? u : 'N'; }
     std::vector<uint64_t> keys;
     std::vector<int32_t> counts;
-    if ((rc = t1k_indel_begin(ctx, (uint32_t)A, refOff.data(), refText.data())) != T1K_OK) return fail(rc);
-    for (const AnalyzerSitepile::Piece &pc : sp->pieces) {
-      double ms = 0;
-      if ((rc = t1k_indel_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), pc.indStrand.data(), pc.indBookPtr.data(), pc.indBookUniq.data(), pc.pat.data(), pc.pat.size(),
-                              V->ops.data() + pc.ops0, pc.ops1 - pc.ops0, &ms)) != T1K_OK) {
-        fail(rc);
-        t1k_indel_end(ctx);
-        return false;
-      }
-      msKernels += ms;
-      nRecs += pc.recs.size();
-    }
-    if ((rc = t1k_indel_get(ctx, nullptr, nullptr, 0, &nRuns)) == T1K_OK && nRuns) {
-      keys.resize(nRuns); counts.resize(nRuns);
-      rc = t1k_indel_get(ctx, keys.data(), counts.data(), nRuns, &nRuns);
-    }
-    if (rc == T1K_OK) rc = t1k_indel_stats(ctx, &events, &shifted, &edgeDel, &edgeIns, &emitted, &folds, &msFold);
-    if (rc != T1K_OK) { fail(rc); t1k_indel_end(ctx); return false; }
-    if ((rc = t1k_indel_end(ctx)) != T1K_OK) return fail(rc);
+    if (!analyzerReplay(job, t1k_indel_begin(ctx, (uint32_t)A, refOff.data(), refText.data()), *sp,
+          [&](const AnalyzerSitepile::Piece &pc, double *ms) {
+            return t1k_indel_add(ctx, pc.recs.data(), (uint32_t)pc.recs.size(), pc.indStrand.data(), pc.indBookPtr.data(), pc.indBookUniq.data(), pc.pat.data(), pc.pat.size(),
+                                 V->ops.data() + pc.ops0, pc.ops1 - pc.ops0, ms);
+          }, t1k_indel_get, [&] { return t1k_indel_stats(ctx, &events, &shifted, &edgeDel, &edgeIns, &emitted, &folds, &msFold); }, t1k_indel_end, keys, counts, msKernels, nRecs)) return false;
+    nRuns = keys.size();
     for (size_t i = 0; i < keys.size();) {
       const uint64_t ev = keys[i] >> 2;  // (g, type, payload): its runs are consecutive
       Line l{};

@@ -313,11 +313,9 @@ void t1k_ctx_destroy(t1k_ctx *ctx) {
                       &ctx->bWgStage, &ctx->bWgBig, &ctx->bWgCache, &ctx->bLists, &ctx->bCand, &ctx->bExt, &ctx->bCandStart, &ctx->bCandCount, &ctx->bListPtr, &ctx->bListCount,
                       &ctx->bOvlWork, &ctx->bOvlUpload, &ctx->bDedupScratch, &ctx->bDedupBases, &ctx->bDedupN, &ctx->bDedupLen, &ctx->bDedupWeight, &ctx->bOvlStart, &ctx->bOvlCount, &ctx->bCounters, &ctx->bSlowQueue, &ctx->bSlowScratch, &ctx->bSortScratch, &ctx->bSelClass, &ctx->bEqTrace, &ctx->bSortTmp, &ctx->bJobSort, &ctx->bEnd1, &ctx->bEnd2,
                       &ctx->bHasN, &ctx->bRows, &ctx->bRowStart, &ctx->bRowCount, &ctx->bFragAssigned, &ctx->bPairScratch, &ctx->bPairOverflow, &ctx->bPairBig, &ctx->bExtractHuge, &ctx->bEmRowPtr, &ctx->bEmEc,
-                      &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bExtract, &ctx->bPileup, &ctx->bPileupIn, &ctx->spMap.buf, &ctx->spTab.keys, &ctx->spTab.vals, &ctx->spTab.work, &ctx->bSpIn,
-                      &ctx->phMap.buf, &ctx->phTab.keys, &ctx->phTab.vals, &ctx->phTab.work, &ctx->bPhIn, &ctx->bPhObs, &ctx->bPhArena,
-                      &ctx->supMap.buf, &ctx->supTab.keys, &ctx->supTab.vals, &ctx->supTab.work, &ctx->bSupIn,
-                      &ctx->indTab.keys, &ctx->indTab.vals, &ctx->indTab.work, &ctx->bIndRef, &ctx->bIndIn};
+                      &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bExtract, &ctx->bPileup, &ctx->bPileupIn};
   for (auto *b : all) freeBuf(*b);
+  for (T1kStage *s : {&ctx->sp, &ctx->sup, &ctx->ind, &ctx->ph}) t1k_stage_blocks(*s, [](const std::string &, T1kDevBuf &b) { freeBuf(b); });
   for (auto &slot : ctx->storeChunks)
     for (auto &b : slot) freeBuf(b);
   for (auto &b : ctx->bAlign) freeBuf(b);
@@ -337,15 +335,17 @@ uint64_t t1k_ctx_mem_report(t1k_ctx *ctx, const char *tag, int print) {
     B(bWgStage), B(bWgBig), B(bWgCache), B(bLists), B(bCand), B(bExt), B(bCandStart), B(bCandCount), B(bListPtr), B(bListCount), B(bOvlWork), B(bOvlUpload), B(bDedupScratch), B(bDedupBases), B(bDedupN),
     B(bDedupLen), B(bDedupWeight), B(bOvlStart), B(bOvlCount), B(bCounters), B(bSlowQueue), B(bSlowScratch), B(bSortScratch), B(bSelClass), B(bEqTrace), B(bSortTmp), B(bJobSort), B(bEnd1),
     B(bEnd2), B(bHasN), B(bRows), B(bRowStart), B(bRowCount), B(bFragAssigned), B(bPairScratch), B(bPairOverflow), B(bPairBig), B(bExtractHuge), B(bEmRowPtr), B(bEmEc), B(bEmCount),
-    B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract), B(bPileup), B(bPileupIn), B(bSpIn), B(bPhIn), B(bPhObs), B(bPhArena), B(bSupIn), B(bIndRef), B(bIndIn),
-    {"bIndKeys", &ctx->indTab.keys}, {"bIndVals", &ctx->indTab.vals}, {"bIndWork", &ctx->indTab.work},
-    {"bSupSites", &ctx->supMap.buf}, {"bSupKeys", &ctx->supTab.keys}, {"bSupVals", &ctx->supTab.vals}, {"bSupWork", &ctx->supTab.work},
-    {"bSpSites", &ctx->spMap.buf}, {"bSpKeys", &ctx->spTab.keys}, {"bSpVals", &ctx->spTab.vals}, {"bSpWork", &ctx->spTab.work},
-    {"bPhSites", &ctx->phMap.buf}, {"bPhKeys", &ctx->phTab.keys}, {"bPhVals", &ctx->phTab.vals}, {"bPhWork", &ctx->phTab.work}};
+    B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract), B(bPileup), B(bPileupIn)};
 #undef B
   uint64_t tot = 0, ref = 0, store = 0, align = 0;
   std::string line;
-  for (auto &e : all) if (e.b->p) { tot += e.b->bytes; if (e.b->bytes >= (64u << 20)) { char t[96]; snprintf(t, sizeof t, " %s %.0f", e.name + 1, e.b->bytes / 1048576.0); line += t; } }
+  auto named = [&](const std::string &name, const T1kDevBuf &b) {
+    if (!b.p) return;
+    tot += b.bytes;
+    if (b.bytes >= (64u << 20)) { char t[96]; snprintf(t, sizeof t, " %s %.0f", name.c_str(), b.bytes / 1048576.0); line += t; }
+  };
+  for (auto &e : all) named(e.name + 1, *e.b);
+  for (T1kStage *s : {&ctx->sp, &ctx->sup, &ctx->ind, &ctx->ph}) t1k_stage_blocks(*s, named);
   for (auto &b : ctx->refBufs) if (b.p) ref += b.bytes;
   for (auto &slot : ctx->storeChunks) for (auto &b : slot) if (b.p) store += b.bytes;
   for (auto &b : ctx->bAlign) if (b.p) align += b.bytes;

@@ -916,12 +916,11 @@ struct T1kDevBuf {
 };
 
 // what the sparse analyzer stages keep between their _begin and _end (t1k_table.h)
-// a set of sites: one device block [site bitmap | rank directory | alleleOff], its pieces at `at`; off: alleleOff on the host
+// a set of sites: one device block [site bitmap | rank directory | alleleOff], its pieces at `at`
 struct T1kSiteMap {
   T1kDevBuf buf;
   size_t at[3] = {0, 0, 0};
   uint64_t nSites = 0;
-  std::vector<uint64_t> off;
 };
 // a sparse count table: `runs` folded (key, count) pairs, then `pending` keys of count 1, room for `cap`; the fold's scratch; the pending
 // keys that start a fold; keys taken and folds run so far, the folds' device time; the bits of the largest possible key
@@ -931,6 +930,34 @@ struct T1kCountTable {
   int endBit = 64;
   double foldMs = 0;
 };
+// one stage's session (t1k_table.h): who: the head of its messages ("t1k_support"); boundEnv: the variable that overrides its table's
+// pending bound; tag: the head of its blocks' names in the T1K_DEBUG_MEM report ("Sup"); more: the device blocks the stage keeps besides
+// the common ones, freed at _end; in: the staging block of one _add call; off: alleleOff on the host; map: the sites of a stage that has
+// sites (built by t1k_stage_open_sites alone)
+struct T1kStageBuf {
+  const char *name;
+  T1kDevBuf b;
+};
+struct T1kStage {
+  const char *who, *boundEnv, *tag;
+  std::vector<T1kStageBuf> more;
+  T1kCountTable tab;
+  T1kDevBuf in;
+  bool open = false;
+  std::vector<uint64_t> off;
+  T1kSiteMap map;
+};
+// every device block of the stage with its name in the T1K_DEBUG_MEM report: f(name, block)
+template <class F>
+inline void t1k_stage_blocks(T1kStage &s, F &&f) {
+  const std::string tag(s.tag);
+  f(tag + "In", s.in);
+  f(tag + "Sites", s.map.buf);
+  f(tag + "Keys", s.tab.keys);
+  f(tag + "Vals", s.tab.vals);
+  f(tag + "Work", s.tab.work);
+  for (T1kStageBuf &m : s.more) f(std::string(m.name), m.b);
+}
 
 struct t1k_ctx {
   int device = 0;
@@ -1021,33 +1048,20 @@ struct t1k_ctx {
   T1kDevBuf bPileup, bPileupIn;
   bool pileupOpen = false;
   std::vector<uint64_t> pileupOff, pileupLoad;
-  // per-barcode pileup at sites (t1k_sitepile.hip), open from t1k_sitepile_begin to _end: its sites, its table of (barcode, site, plane,
-  // uniq) cells and the staging block of one _add call
-  T1kSiteMap spMap;
-  T1kCountTable spTab;
-  T1kDevBuf bSpIn;
-  bool spOpen = false;
+  // the four sparse-table stages, each open from its _begin to its _end (T1kStage), and beside each what only that stage keeps
+  // per-barcode pileup at sites (t1k_sitepile.hip): a table of (barcode, site, plane, uniq) cells; the barcodes a booking may name
+  T1kStage sp{"t1k_sitepile", "T1K_SITEPILE_PENDING", "Sp"};
   uint64_t spBarcodes = 0;
-  // strand / mate / end-distance / template support at sites (t1k_support.hip), open from t1k_support_begin to _end: its sites, its one
-  // table of both key families and the staging block of one _add call
-  T1kSiteMap supMap;
-  T1kCountTable supTab;
-  T1kDevBuf bSupIn;
-  bool supOpen = false;
-  // novel indel evidence (t1k_indel.hip), open from t1k_indel_begin to _end: the block [alleleOff | alleleText] (the text at indTextAt), the
-  // allele offsets on the host, its one table, the staging block of one _add call, and what _stats reports of the calls that were taken
-  T1kCountTable indTab;
-  T1kDevBuf bIndRef, bIndIn;
-  bool indOpen = false;
+  // strand / mate / end-distance / template support at sites (t1k_support.hip): one table of both key families
+  T1kStage sup{"t1k_support", "T1K_SUPPORT_PENDING", "Sup"};
+  // novel indel evidence (t1k_indel.hip): no sites; the block [alleleOff | alleleText] (the text at indTextAt) and what _stats reports of
+  // the calls that were taken
+  T1kStage ind{"t1k_indel", "T1K_INDEL_PENDING", "Ind", {{"IndRef"}}};
   size_t indTextAt = 0;
-  std::vector<uint64_t> indOff;
   uint64_t indEvents = 0, indShifted = 0, indEdgeDel = 0, indEdgeIns = 0;
-  // read-backed phasing of site pairs (t1k_phase.hip), open from t1k_phase_begin to _end: its sites, its table of (site pair, state pair,
-  // uniq) cells, the staging block of one _add call, that call's observation words and merge arena, and what _stats reports
-  T1kSiteMap phMap;
-  T1kCountTable phTab;
-  T1kDevBuf bPhIn, bPhObs, bPhArena;
-  bool phOpen = false;
+  // read-backed phasing of site pairs (t1k_phase.hip): a table of (site pair, state pair, uniq) cells, one _add call's observation words
+  // and merge arena, and what _stats reports
+  T1kStage ph{"t1k_phase", "T1K_PHASE_PENDING", "Ph", {{"PhObs"}, {"PhArena"}}};
   uint64_t phObs = 0, phBookings = 0, phDiscordant = 0;
   t1k_stats stats{};
 };

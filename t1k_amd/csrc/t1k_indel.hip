@@ -31,6 +31,10 @@
 // No LDS, no scratch, no atomics on data (the flag word of the check excepted).  The table and its fold are a T1kCountTable (t1k_table.h),
 // folded whenever the pending keys reach a bound (2^28, env T1K_INDEL_PENDING) and at _get.  The four statistics are sums of the
 // per-record words (t1k_exclusive_sum_u64): they do not depend on the order in which waves finish.
+// Shared with the other sparse stages, and not written out here: the session (ctx->ind, a T1kStage without sites: state checks, _get, the
+// table part of _stats, _end) and the end of an _add call (t1k_stage_done) in t1k_table.h; the checks of records and booking lists
+// (pileupBookLists) and the staging (pileupStage) in t1k_walk.h.  The sequence of _add stays here: it sums four rows in one scan, tells a
+// too long deletion from the walk's faults, emits for events without bookings and scans a second time -- t1k_stage_two_pass does none of it.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -39,6 +43,7 @@
 #include "t1k_table.h"
 #include "t1k_walk.h"
 
+enum { INDEL_REF = 0 };  // of ctx->ind.more: the block [alleleOff | alleleText]
 enum { INDEL_SHORT_MAX = 13, INDEL_PAYLOAD_BITS = 27, INDEL_BAD_DEL_LEN = 16, INDEL_WORDS = 5 };  // (the flag bit behind PILEUP_BAD_*)
 static const uint32_t INDEL_PAYLOAD_MAX = (1u << INDEL_PAYLOAD_BITS) - 1u;
 
@@ -178,8 +183,10 @@ extern "C" {
 
 int t1k_indel_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff, const char *alleleText) {
   if (!ctx) return T1K_ERR_ARG;
-  if (ctx->indOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_indel_begin: a table is open already (t1k_indel_end first)");
+  T1kStage &s = ctx->ind;
+  T1kDevBuf &ref = s.more[INDEL_REF].b;
   int rc;
+  if ((rc = t1k_stage_closed(ctx, s))) return rc;
   if ((rc = pileupCheckOffsets(ctx, "t1k_indel_begin", "NULL arrays, or alleleOff not starting at 0", nAlleles, alleleOff))) return rc;
   const uint64_t total = alleleOff[nAlleles];
   if (total && !alleleText) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_indel_begin: bad arguments (NULL arrays, or alleleOff not starting at 0)");
@@ -192,16 +199,14 @@ int t1k_indel_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff, 
   const size_t oOff = piece(8ull * (nAlleles + 1ull)), oText = piece(total);
   (void)oOff;
   T1K_HIP(ctx, hipSetDevice(ctx->device));
-  if ((rc = t1k_ensure(ctx, ctx->bIndRef, piece.off))) return rc;
-  char *D = (char *)ctx->bIndRef.p;
+  if ((rc = t1k_ensure(ctx, ref, piece.off))) return rc;
+  char *D = (char *)ref.p;
   T1K_HIP(ctx, hipMemcpyAsync(D, alleleOff, 8ull * (nAlleles + 1ull), hipMemcpyHostToDevice, ctx->stream));
   if (total) T1K_HIP(ctx, hipMemcpyAsync(D + oText, alleleText, total, hipMemcpyHostToDevice, ctx->stream));
   T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));  // alleleOff / alleleText are the caller's again
-  ctx->indOff.assign(alleleOff, alleleOff + nAlleles + 1);
   ctx->indTextAt = oText;
   ctx->indEvents = ctx->indShifted = ctx->indEdgeDel = ctx->indEdgeIns = 0;
-  t1k_table_open(ctx->indTab, (1ull << 63) - 1ull, "T1K_INDEL_PENDING");
-  ctx->indOpen = true;
+  t1k_stage_open(s, nAlleles, alleleOff, (1ull << 63) - 1ull);
   return T1K_OK;
 }
 
@@ -209,40 +214,35 @@ int t1k_indel_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const uin
                   const int8_t *ops, uint64_t opsBytes, double *kernelMs) {
   if (!ctx) return T1K_ERR_ARG;
   if (kernelMs) *kernelMs = 0;
-  if (!ctx->indOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_indel_add: no table is open (t1k_indel_begin first)");
+  T1kStage &s = ctx->ind;
+  const T1kDevBuf &ref = s.more[INDEL_REF].b;
+  int rc;
+  if ((rc = t1k_stage_opened(ctx, s, "_add", "_begin"))) return rc;
   if (n == 0) return T1K_OK;
   if (!aln || !strand || !bookPtr || (textBytes && !text) || (opsBytes && !ops)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_indel_add: bad arguments (NULL arrays)");
   // what the host can tell from the records and the booking lists alone; the strings themselves are walked on the device before anything is emitted
-  const std::vector<uint64_t> &off = ctx->indOff;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (bookPtr[i + 1] < bookPtr[i]) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_indel_add: bookPtr decreases at record " + std::to_string(i));
-    if (bookPtr[i + 1] - bookPtr[i] >= (1ull << 31)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_indel_add: record " + std::to_string(i) + " has 2^31 bookings or more");
-    const std::string fault = pileupRecordFault(aln[i], i, off, textBytes, opsBytes);
-    if (!fault.empty()) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_indel_add: " + fault);
-    if (strand[i] > 1) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_indel_add: record " + std::to_string(i) + " has a strand other than 0 or 1");
-  }
-  const uint64_t book0 = bookPtr[0], nBook = bookPtr[n] - book0;
-  if (nBook && !bookUniq) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_indel_add: bad arguments (NULL bookUniq)");
+  std::vector<uint64_t> bp;
+  if ((rc = pileupBookLists(ctx, "t1k_indel_add", aln, n, s.off, textBytes, opsBytes, bookPtr, 31, bookUniq, "bookUniq", [&](uint32_t i) {
+        return strand[i] > 1 ? "record " + std::to_string(i) + " has a strand other than 0 or 1" : std::string();
+      }, bp))) return rc;
+  const uint64_t book0 = bookPtr[0], nBook = bp[n];
   for (uint64_t j = book0; j < book0 + nBook; ++j)
     if (bookUniq[j] > 1) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_indel_add: booking " + std::to_string(j) + " has a uniq other than 0 or 1");
-  std::vector<uint64_t> bp(n + 1);
-  for (uint32_t i = 0; i <= n; ++i) bp[i] = bookPtr[i] - book0;
   T1K_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   IndelArgs a{};
-  a.in = PileupBatch{aln, n, text, textBytes, ops, (const unsigned long long *)ctx->bIndRef.p, nullptr};
+  a.in = PileupBatch{aln, n, text, textBytes, ops, (const unsigned long long *)ref.p, nullptr};
   const uint64_t row = (uint64_t)n + 1;
   size_t oStrand = 0, oBp = 0, oBook = 0, oWord = 0;
-  int rc;
-  if ((rc = pileupStage(ctx, ctx->bIndIn, opsBytes, [&](T1kCarve &piece) {
+  if ((rc = pileupStage(ctx, s.in, opsBytes, [&](T1kCarve &piece) {
         oStrand = piece(n); oBp = piece(8ull * row); oBook = piece(nBook); oWord = piece(8ull * INDEL_WORDS * row);
       }, a.in))) return rc;
-  char *D = (char *)ctx->bIndIn.p;
+  char *D = (char *)s.in.p;
   T1K_HIP(ctx, hipMemcpyAsync(D + oStrand, strand, n, hipMemcpyHostToDevice, st));
   T1K_HIP(ctx, hipMemcpyAsync(D + oBp, bp.data(), 8ull * row, hipMemcpyHostToDevice, st));
   if (nBook) T1K_HIP(ctx, hipMemcpyAsync(D + oBook, bookUniq + book0, nBook, hipMemcpyHostToDevice, st));
   T1K_HIP(ctx, hipMemsetAsync(D + oWord, 0, 8ull * INDEL_WORDS * row, st));
-  a.allele = (const char *)ctx->bIndRef.p + ctx->indTextAt;
+  a.allele = (const char *)ref.p + ctx->indTextAt;
   a.strand = (const uint8_t *)(D + oStrand);
   a.bookPtr = (const unsigned long long *)(D + oBp); a.bookUniq = (const uint8_t *)(D + oBook);
   a.word = (unsigned long long *)(D + oWord);
@@ -263,54 +263,31 @@ int t1k_indel_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const uin
   const uint64_t emit = upTo[0], events = upTo[1] - upTo[0], edgeDel = upTo[2] - upTo[1], edgeIns = upTo[3] - upTo[2];
   unsigned long long shifted = 0;
   if (events) {  // (records without a booking take part: their events may move as well)
-    if (emit && (rc = t1k_table_room(ctx, "t1k_indel", ctx->indTab, emit, "lower T1K_INDEL_PENDING, or add fewer records per call", &a.keys, &a.vals))) return rc;
+    if (emit && (rc = t1k_table_room(ctx, s.who, s.tab, emit, "lower T1K_INDEL_PENDING, or add fewer records per call", &a.keys, &a.vals))) return rc;
     hipLaunchKernelGGL(k_indel<true>, dim3(grid), dim3(256), 0, st, a);
     T1K_HIP(ctx, hipGetLastError());
     unsigned long long *moved = a.word + 4 * row;
     if ((rc = t1k_exclusive_sum_u64(ctx, moved, moved, row))) return rc;
     T1K_HIP(ctx, hipMemcpyAsync(&shifted, moved + n, 8, hipMemcpyDeviceToHost, st));
   }
-  T1K_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-  T1K_HIP(ctx, hipStreamSynchronize(st));  // text / ops / bookUniq are the caller's again, the staging block the next call's
-  float ms = 0;
-  if (kernelMs && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) *kernelMs = ms;
-  if (emit && (rc = t1k_table_commit(ctx, "t1k_indel", ctx->indTab, emit))) return rc;
+  if ((rc = t1k_stage_done(ctx, kernelMs))) return rc;
+  if (emit && (rc = t1k_table_commit(ctx, s.who, s.tab, emit))) return rc;
   ctx->indEvents += events; ctx->indShifted += shifted; ctx->indEdgeDel += edgeDel; ctx->indEdgeIns += edgeIns;
   return T1K_OK;
 }
 
-int t1k_indel_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (nRuns) *nRuns = 0;
-  if (!ctx->indOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_indel_get: no table is open");
-  T1K_HIP(ctx, hipSetDevice(ctx->device));
-  return t1k_table_get(ctx, "t1k_indel", ctx->indTab, keys, counts, cap, nRuns);
-}
+int t1k_indel_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) { return t1k_stage_get(ctx, &t1k_ctx::ind, keys, counts, cap, nRuns); }
 
 int t1k_indel_stats(t1k_ctx *ctx, uint64_t *events, uint64_t *shifted, uint64_t *edgeDelBooked, uint64_t *edgeInsBooked, uint64_t *keysEmitted, uint64_t *folds, double *foldMs) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (!ctx->indOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_indel_stats: no table is open");
+  int rc;
+  if ((rc = t1k_stage_stats(ctx, &t1k_ctx::ind, keysEmitted, folds, foldMs))) return rc;
   if (events) *events = ctx->indEvents;
   if (shifted) *shifted = ctx->indShifted;
   if (edgeDelBooked) *edgeDelBooked = ctx->indEdgeDel;
   if (edgeInsBooked) *edgeInsBooked = ctx->indEdgeIns;
-  if (keysEmitted) *keysEmitted = ctx->indTab.emitted;
-  if (folds) *folds = ctx->indTab.folds;
-  if (foldMs) *foldMs = ctx->indTab.foldMs;
   return T1K_OK;
 }
 
-int t1k_indel_end(t1k_ctx *ctx) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (!ctx->indOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_indel_end: no table is open");
-  ctx->indOpen = false;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  t1k_table_close(ctx->indTab);
-  for (T1kDevBuf *b : {&ctx->bIndRef, &ctx->bIndIn})
-    if (b->p) { (void)t1k_dev_free(b->p); b->p = nullptr; b->bytes = 0; }
-  ctx->indOff.clear();
-  return T1K_OK;
-}
+int t1k_indel_end(t1k_ctx *ctx) { return t1k_stage_end(ctx, &t1k_ctx::ind); }
 
 }  // extern "C"

@@ -28,6 +28,10 @@
 //                       the lanes of a row write consecutive keys.  No LDS, and nothing bounds a list's length.
 // The table and its fold are a T1kCountTable (t1k_table.h), folded whenever the pending keys reach a bound (2^28, env T1K_PHASE_PENDING)
 // and at _get.  Pairs grow with the square of a booking's observed sites; the table refuses what would pass 2^31 entries (T1K_ERR_CAPACITY).
+// Shared with the other sparse stages, and not written out here: the session (ctx->ph, a T1kStage: state checks, _get, the table part of
+// _stats, _end, the site arguments of _begin) and the end of an _add call (t1k_stage_done) in t1k_table.h; the record checks and the
+// staging (pileupStage) in t1k_walk.h.  _add is this stage's own: its bookings name records instead of hanging off them, and its pipeline
+// is five kernels with three sums between them.
 #include <algorithm>
 #include <cstdlib>
 #include "t1k_dev.h"
@@ -36,6 +40,7 @@
 #include "t1k_walk.h"
 
 enum { PHASE_STATES = 6 };
+enum { PHASE_OBS = 0, PHASE_ARENA = 1 };  // of ctx->ph.more: one _add call's observation words and its merge arena
 static const uint32_t PHASE_NO_MATE = 0xFFFFFFFFu;
 
 struct PhaseArgs {
@@ -195,43 +200,33 @@ __global__ __launch_bounds__(256) void k_phase_pairs(PhaseArgs P) {
   }
 }
 
-// stops the event pair of an _add call and reports its device time
-static int phaseDone(t1k_ctx *ctx, double *kernelMs) {
-  T1K_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-  T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));  // text / ops / the bookings are the caller's again, the staging block the next call's
-  float ms = 0;
-  if (kernelMs && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) *kernelMs = ms;
-  return T1K_OK;
-}
-
 extern "C" {
 
 int t1k_phase_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos) {
   if (!ctx) return T1K_ERR_ARG;
-  if (ctx->phOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_phase_begin: a table is open already (t1k_phase_end first)");
+  T1kStage &s = ctx->ph;
+  int rc;
+  if ((rc = t1k_stage_closed(ctx, s))) return rc;
   // a site index takes 28 bits of an observation word, and the largest key, nSites^2 * 72 - 1, stays below 2^63
   if (nSites > (1ull << 28)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_phase_begin: more than 2^28 sites");
-  if (nSites && (!siteAllele || !sitePos)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_phase_begin: bad arguments (NULL arrays, or alleleOff not starting at 0)");
-  int rc;
-  if ((rc = pileupCheckOffsets(ctx, "t1k_phase_begin", "NULL arrays, or alleleOff not starting at 0", nAlleles, alleleOff))) return rc;
-  if (nSites > alleleOff[nAlleles]) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_phase_begin: more sites than allele positions (the sites are not strictly ascending)");
-  if ((rc = t1k_sites_build(ctx, "t1k_phase_begin", ctx->phMap, nAlleles, alleleOff, nSites, siteAllele, sitePos))) return rc;
+  if ((rc = t1k_stage_site_args(ctx, s, nAlleles, alleleOff, nSites, siteAllele, sitePos))) return rc;
   const unsigned long long space = nSites * nSites * (2ull * PHASE_STATES * PHASE_STATES);
-  t1k_table_open(ctx->phTab, space ? space - 1 : 0ull, "T1K_PHASE_PENDING");
   ctx->phObs = ctx->phBookings = ctx->phDiscordant = 0;
-  ctx->phOpen = true;
-  return T1K_OK;
+  return t1k_stage_open_sites(ctx, s, nAlleles, alleleOff, nSites, siteAllele, sitePos, space ? space - 1 : 0ull);
 }
 
 int t1k_phase_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, uint32_t nBook, const uint32_t *bookRec, const uint8_t *bookUniq, const char *text, uint64_t textBytes,
                   const int8_t *ops, uint64_t opsBytes, double *kernelMs) {
   if (!ctx) return T1K_ERR_ARG;
   if (kernelMs) *kernelMs = 0;
-  if (!ctx->phOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_phase_add: no table is open (t1k_phase_begin first)");
+  T1kStage &s = ctx->ph;
+  T1kDevBuf &bObs = s.more[PHASE_OBS].b, &bArena = s.more[PHASE_ARENA].b;
+  int rc;
+  if ((rc = t1k_stage_opened(ctx, s, "_add", "_begin"))) return rc;
   if ((n && !aln) || (nBook && (!bookRec || !bookUniq)) || (textBytes && !text) || (opsBytes && !ops)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_phase_add: bad arguments (NULL arrays)");
   // what the host can tell from the records and the bookings alone; the strings themselves are walked on the device before anything is emitted
   for (uint32_t i = 0; i < n; ++i) {
-    const std::string fault = pileupRecordFault(aln[i], i, ctx->phMap.off, textBytes, opsBytes);
+    const std::string fault = pileupRecordFault(aln[i], i, s.off, textBytes, opsBytes);
     if (!fault.empty()) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_phase_add: " + fault);
   }
   for (uint32_t b = 0; b < nBook; ++b) {
@@ -243,21 +238,20 @@ int t1k_phase_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, uint32_t 
   T1K_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   PhaseArgs a{};
-  a.in = PileupBatch{aln, n, text, textBytes, ops, t1k_sites_offsets(ctx->phMap), nullptr};
+  a.in = PileupBatch{aln, n, text, textBytes, ops, t1k_sites_offsets(s.map), nullptr};
   size_t oRec = 0, oUniq = 0, oObsPtr = 0, oNeed = 0, oM = 0, oPairs = 0, oStat = 0;
-  int rc;
-  if ((rc = pileupStage(ctx, ctx->bPhIn, opsBytes, [&](T1kCarve &piece) {
+  if ((rc = pileupStage(ctx, s.in, opsBytes, [&](T1kCarve &piece) {
         oRec = piece(8ull * nBook); oUniq = piece(nBook); oObsPtr = piece(8ull * (n + 1ull)); oNeed = piece(8ull * (nBook + 1ull)); oM = piece(4ull * nBook);
         oPairs = piece(8ull * (nBook + 1ull)); oStat = piece(8ull * (nBook + 1ull));
       }, a.in))) return rc;
-  char *D = (char *)ctx->bPhIn.p;
+  char *D = (char *)s.in.p;
   if (nBook) {
     T1K_HIP(ctx, hipMemcpyAsync(D + oRec, bookRec, 8ull * nBook, hipMemcpyHostToDevice, st));
     T1K_HIP(ctx, hipMemcpyAsync(D + oUniq, bookUniq, nBook, hipMemcpyHostToDevice, st));
   }
   T1K_HIP(ctx, hipMemsetAsync(D + oObsPtr, 0, 8ull * (n + 1ull), st));
-  a.sites = t1k_sites_view(ctx->phMap);
-  a.nSites = ctx->phMap.nSites;
+  a.sites = t1k_sites_view(s.map);
+  a.nSites = s.map.nSites;
   a.obsPtr = (unsigned long long *)(D + oObsPtr);
   a.nBook = nBook;
   a.bookRec = (const uint32_t *)(D + oRec); a.bookUniq = (const uint8_t *)(D + oUniq);
@@ -276,8 +270,8 @@ int t1k_phase_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, uint32_t 
   if (nObs >= (1ull << 31)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_phase_add: 2^31 observations or more in one call (add fewer records per call)");
   unsigned long long nArena = 0, emit = 0, stat = 0;
   if (nObs && nBook) {
-    if ((rc = t1k_ensure(ctx, ctx->bPhObs, 4ull * nObs))) return rc;
-    a.obs = (uint32_t *)ctx->bPhObs.p;
+    if ((rc = t1k_ensure(ctx, bObs, 4ull * nObs))) return rc;
+    a.obs = (uint32_t *)bObs.p;
     hipLaunchKernelGGL(k_phase_obs<true>, dim3(gridRec), dim3(256), 0, st, a);
     T1K_HIP(ctx, hipGetLastError());
     T1K_HIP(ctx, hipMemsetAsync(a.need + nBook, 0, 8, st));
@@ -292,8 +286,8 @@ int t1k_phase_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, uint32_t 
   if (nArena >= (1ull << 31))
     return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_phase_add: the bookings of one call observe 2^31 sites or more (fewer sites, or add fewer records per call)");
   if (nArena) {
-    if ((rc = t1k_ensure(ctx, ctx->bPhArena, 4ull * nArena))) return rc;
-    a.arena = (uint32_t *)ctx->bPhArena.p;
+    if ((rc = t1k_ensure(ctx, bArena, 4ull * nArena))) return rc;
+    a.arena = (uint32_t *)bArena.p;
     hipLaunchKernelGGL(k_phase_merge, dim3(gridBook), dim3(256), 0, st, a);
     T1K_HIP(ctx, hipGetLastError());
     if ((rc = t1k_exclusive_sum_u64(ctx, a.pairs, a.pairs, (uint64_t)nBook + 1))) return rc;
@@ -304,51 +298,31 @@ int t1k_phase_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, uint32_t 
   }
   if (emit) {
     // (the bookings' observed sites add up to less than 2^31, so the sum of their m (m - 1) / 2 is far from wrapping)
-    if ((rc = t1k_table_room(ctx, "t1k_phase", ctx->phTab, emit,
+    if ((rc = t1k_table_room(ctx, s.who, s.tab, emit,
                              "pairs grow with the square of a booking's observed sites: fewer sites, a lower T1K_PHASE_PENDING, or fewer records per call", &a.keys, &a.vals)))
       return rc;
     hipLaunchKernelGGL(k_phase_pairs, dim3(gridBook), dim3(256), 0, st, a);
     T1K_HIP(ctx, hipGetLastError());
   }
-  if ((rc = phaseDone(ctx, kernelMs))) return rc;
-  if (emit && (rc = t1k_table_commit(ctx, "t1k_phase", ctx->phTab, emit))) return rc;
+  if ((rc = t1k_stage_done(ctx, kernelMs))) return rc;
+  if (emit && (rc = t1k_table_commit(ctx, s.who, s.tab, emit))) return rc;
   ctx->phObs += nObs;
   ctx->phBookings += stat >> 32;
   ctx->phDiscordant += stat & 0xFFFFFFFFull;
   return T1K_OK;
 }
 
-int t1k_phase_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (nRuns) *nRuns = 0;
-  if (!ctx->phOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_phase_get: no table is open");
-  T1K_HIP(ctx, hipSetDevice(ctx->device));
-  return t1k_table_get(ctx, "t1k_phase", ctx->phTab, keys, counts, cap, nRuns);
-}
+int t1k_phase_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) { return t1k_stage_get(ctx, &t1k_ctx::ph, keys, counts, cap, nRuns); }
 
 int t1k_phase_stats(t1k_ctx *ctx, uint64_t *observations, uint64_t *bookings, uint64_t *keysEmitted, uint64_t *discordant, uint64_t *folds, double *foldMs) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (!ctx->phOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_phase_stats: no table is open");
+  int rc;
+  if ((rc = t1k_stage_stats(ctx, &t1k_ctx::ph, keysEmitted, folds, foldMs))) return rc;
   if (observations) *observations = ctx->phObs;
   if (bookings) *bookings = ctx->phBookings;
-  if (keysEmitted) *keysEmitted = ctx->phTab.emitted;
   if (discordant) *discordant = ctx->phDiscordant;
-  if (folds) *folds = ctx->phTab.folds;
-  if (foldMs) *foldMs = ctx->phTab.foldMs;
   return T1K_OK;
 }
 
-int t1k_phase_end(t1k_ctx *ctx) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (!ctx->phOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_phase_end: no table is open");
-  ctx->phOpen = false;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  t1k_sites_close(ctx->phMap);
-  t1k_table_close(ctx->phTab);
-  for (T1kDevBuf *b : {&ctx->bPhIn, &ctx->bPhObs, &ctx->bPhArena})
-    if (b->p) { (void)t1k_dev_free(b->p); b->p = nullptr; b->bytes = 0; }
-  return T1K_OK;
-}
+int t1k_phase_end(t1k_ctx *ctx) { return t1k_stage_end(ctx, &t1k_ctx::ph); }
 
 }  // extern "C"

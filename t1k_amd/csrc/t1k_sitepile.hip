@@ -15,6 +15,9 @@
 // cell to its plain counter (plain = even + odd, _uniq = even).  So no booking is ever stored twice.
 // The table and its fold are a T1kCountTable (t1k_table.h): (key, count) pairs followed by the pending keys (count 1), folded whenever the
 // pending keys reach a bound (2^28, env T1K_SITEPILE_PENDING) and at _get.
+// Shared with the other sparse stages, and not written out here: the session (ctx->sp, a T1kStage: state checks, _get, _stats, _end, the
+// site arguments of _begin) and the check / sum / emit sequence of _add (t1k_stage_two_pass) in t1k_table.h; the checks of records and
+// booking lists (pileupBookLists) and the staging (pileupStage) in t1k_walk.h.  Here: the kernel, the key's bounds, the barcode checks.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -83,112 +86,56 @@ extern "C" {
 
 int t1k_sitepile_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos, uint64_t nBarcodes) {
   if (!ctx) return T1K_ERR_ARG;
-  if (ctx->spOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_sitepile_begin: a table is open already (t1k_sitepile_end first)");
-  if (nSites && (!siteAllele || !sitePos)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_begin: bad arguments (NULL arrays, or alleleOff not starting at 0)");
+  T1kStage &s = ctx->sp;
   int rc;
-  if ((rc = pileupCheckOffsets(ctx, "t1k_sitepile_begin", "NULL arrays, or alleleOff not starting at 0", nAlleles, alleleOff))) return rc;
-  if (nSites > alleleOff[nAlleles]) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_begin: more sites than allele positions (the sites are not strictly ascending)");
+  if ((rc = t1k_stage_closed(ctx, s))) return rc;
+  if ((rc = t1k_stage_site_args(ctx, s, nAlleles, alleleOff, nSites, siteAllele, sitePos))) return rc;
   // a booking names its barcode in 31 bits; the largest key, nBarcodes * nSites * 14 - 1, must leave the top bit of the 64 alone
   if (nBarcodes > (1ull << 31)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_sitepile_begin: more than 2^31 barcodes");
   const unsigned __int128 space = (unsigned __int128)nBarcodes * nSites * (2 * SITEPILE_BASE_PLANES);
   if (space >= ((unsigned __int128)1 << 63)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_sitepile_begin: nBarcodes * nSites * 14 does not fit the key (2^63)");
-  if ((rc = t1k_sites_build(ctx, "t1k_sitepile_begin", ctx->spMap, nAlleles, alleleOff, nSites, siteAllele, sitePos))) return rc;
   ctx->spBarcodes = nBarcodes;
-  t1k_table_open(ctx->spTab, space ? (unsigned long long)(space - 1) : 0ull, "T1K_SITEPILE_PENDING");
-  ctx->spOpen = true;
-  return T1K_OK;
+  return t1k_stage_open_sites(ctx, s, nAlleles, alleleOff, nSites, siteAllele, sitePos, space ? (unsigned long long)(space - 1) : 0ull);
 }
 
 int t1k_sitepile_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const uint64_t *bookPtr, const uint32_t *book, const char *text, uint64_t textBytes, const int8_t *ops,
                      uint64_t opsBytes, double *kernelMs) {
   if (!ctx) return T1K_ERR_ARG;
   if (kernelMs) *kernelMs = 0;
-  if (!ctx->spOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_sitepile_add: no table is open (t1k_sitepile_begin first)");
+  T1kStage &s = ctx->sp;
+  int rc;
+  if ((rc = t1k_stage_opened(ctx, s, "_add", "_begin"))) return rc;
   if (n == 0) return T1K_OK;
   if (!aln || !bookPtr || (textBytes && !text) || (opsBytes && !ops)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: bad arguments (NULL arrays)");
   // what the host can tell from the records and the booking lists alone; the strings themselves are walked on the device before anything is emitted
-  for (uint32_t i = 0; i < n; ++i) {
-    if (bookPtr[i + 1] < bookPtr[i]) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: bookPtr decreases at record " + std::to_string(i));
-    if (bookPtr[i + 1] - bookPtr[i] >= (1ull << 32)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_sitepile_add: record " + std::to_string(i) + " has 2^32 bookings or more");
-    const std::string fault = pileupRecordFault(aln[i], i, ctx->spMap.off, textBytes, opsBytes);
-    if (!fault.empty()) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: " + fault);
-  }
-  const uint64_t book0 = bookPtr[0], nBook = bookPtr[n] - book0;
-  if (nBook && !book) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: bad arguments (NULL book)");
+  std::vector<uint64_t> bp;
+  if ((rc = pileupBookLists(ctx, "t1k_sitepile_add", aln, n, s.off, textBytes, opsBytes, bookPtr, 32, book, "book", [](uint32_t) { return std::string(); }, bp))) return rc;
+  const uint64_t book0 = bookPtr[0], nBook = bp[n];
   for (uint64_t j = 0; j < nBook; ++j)
     if ((book[book0 + j] >> 1) >= ctx->spBarcodes) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_sitepile_add: booking " + std::to_string(book0 + j) + " names an unknown barcode");
-  std::vector<uint64_t> bp(n + 1);
-  for (uint32_t i = 0; i <= n; ++i) bp[i] = bookPtr[i] - book0;
   T1K_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   SitepileArgs a{};
-  a.in = PileupBatch{aln, n, text, textBytes, ops, t1k_sites_offsets(ctx->spMap), nullptr};
+  a.in = PileupBatch{aln, n, text, textBytes, ops, t1k_sites_offsets(s.map), nullptr};
   size_t oBp = 0, oBook = 0, oCount = 0;
-  int rc;
-  if ((rc = pileupStage(ctx, ctx->bSpIn, opsBytes, [&](T1kCarve &piece) { oBp = piece(8ull * (n + 1ull)); oBook = piece(4 * nBook); oCount = piece(8ull * (n + 1ull)); }, a.in))) return rc;
-  char *D = (char *)ctx->bSpIn.p;
+  if ((rc = pileupStage(ctx, s.in, opsBytes, [&](T1kCarve &piece) { oBp = piece(8ull * (n + 1ull)); oBook = piece(4 * nBook); oCount = piece(8ull * (n + 1ull)); }, a.in))) return rc;
+  char *D = (char *)s.in.p;
   T1K_HIP(ctx, hipMemcpyAsync(D + oBp, bp.data(), 8ull * (n + 1ull), hipMemcpyHostToDevice, st));
   if (nBook) T1K_HIP(ctx, hipMemcpyAsync(D + oBook, book + book0, 4 * nBook, hipMemcpyHostToDevice, st));
   T1K_HIP(ctx, hipMemsetAsync(D + oCount, 0, 8ull * (n + 1ull), st));
-  a.sites = t1k_sites_view(ctx->spMap);
-  a.nSites = ctx->spMap.nSites;
+  a.sites = t1k_sites_view(s.map);
+  a.nSites = s.map.nSites;
   a.bookPtr = (const unsigned long long *)(D + oBp); a.book = (const uint32_t *)(D + oBook);
   a.count = (unsigned long long *)(D + oCount);
   const unsigned grid = t1k_grid(ctx, n, 4);
-  T1K_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-  hipLaunchKernelGGL(k_sitepile<false>, dim3(grid), dim3(256), 0, st, a);
-  T1K_HIP(ctx, hipGetLastError());
-  if ((rc = t1k_exclusive_sum_u64(ctx, a.count, a.count, (uint64_t)n + 1))) return rc;  // (in place: every tile is read before it is written)
-  uint32_t flag = 0;
-  unsigned long long emit = 0;
-  T1K_HIP(ctx, hipMemcpyAsync(&flag, a.in.flag, 4, hipMemcpyDeviceToHost, st));
-  T1K_HIP(ctx, hipMemcpyAsync(&emit, a.count + n, 8, hipMemcpyDeviceToHost, st));
-  T1K_HIP(ctx, hipStreamSynchronize(st));
-  if (flag) return t1k_fail(ctx, T1K_ERR_ARG, pileupRefusal("t1k_sitepile_add", "nothing emitted", flag));
-  if (emit == 0) {
-    T1K_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    T1K_HIP(ctx, hipStreamSynchronize(st));
-    float ms0 = 0;
-    if (kernelMs && hipEventElapsedTime(&ms0, ctx->ev[0], ctx->ev[1]) == hipSuccess) *kernelMs = ms0;
-    return T1K_OK;
-  }
-  if ((rc = t1k_table_room(ctx, "t1k_sitepile", ctx->spTab, emit, "lower T1K_SITEPILE_PENDING, or add fewer records per call", &a.keys, &a.vals))) return rc;
-  hipLaunchKernelGGL(k_sitepile<true>, dim3(grid), dim3(256), 0, st, a);
-  T1K_HIP(ctx, hipGetLastError());
-  T1K_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-  T1K_HIP(ctx, hipStreamSynchronize(st));  // text / ops / book are the caller's again, the staging block the next call's
-  float ms = 0;
-  if (kernelMs && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) *kernelMs = ms;
-  return t1k_table_commit(ctx, "t1k_sitepile", ctx->spTab, emit);
+  return t1k_stage_two_pass(ctx, s, n, a.in.flag, a.count, kernelMs, [&] { hipLaunchKernelGGL(k_sitepile<false>, dim3(grid), dim3(256), 0, st, a); },
+                            [&](unsigned long long *keys, uint32_t *vals) { a.keys = keys; a.vals = vals; hipLaunchKernelGGL(k_sitepile<true>, dim3(grid), dim3(256), 0, st, a); });
 }
 
-int t1k_sitepile_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (nRuns) *nRuns = 0;
-  if (!ctx->spOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_sitepile_get: no table is open");
-  T1K_HIP(ctx, hipSetDevice(ctx->device));
-  return t1k_table_get(ctx, "t1k_sitepile", ctx->spTab, keys, counts, cap, nRuns);
-}
+int t1k_sitepile_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) { return t1k_stage_get(ctx, &t1k_ctx::sp, keys, counts, cap, nRuns); }
 
-int t1k_sitepile_stats(t1k_ctx *ctx, uint64_t *keysEmitted, uint64_t *folds, double *foldMs) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (!ctx->spOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_sitepile_stats: no table is open");
-  if (keysEmitted) *keysEmitted = ctx->spTab.emitted;
-  if (folds) *folds = ctx->spTab.folds;
-  if (foldMs) *foldMs = ctx->spTab.foldMs;
-  return T1K_OK;
-}
+int t1k_sitepile_stats(t1k_ctx *ctx, uint64_t *keysEmitted, uint64_t *folds, double *foldMs) { return t1k_stage_stats(ctx, &t1k_ctx::sp, keysEmitted, folds, foldMs); }
 
-int t1k_sitepile_end(t1k_ctx *ctx) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (!ctx->spOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_sitepile_end: no table is open");
-  ctx->spOpen = false;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  t1k_sites_close(ctx->spMap);
-  t1k_table_close(ctx->spTab);
-  if (ctx->bSpIn.p) { (void)t1k_dev_free(ctx->bSpIn.p); ctx->bSpIn.p = nullptr; ctx->bSpIn.bytes = 0; }
-  return T1K_OK;
-}
+int t1k_sitepile_end(t1k_ctx *ctx) { return t1k_stage_end(ctx, &t1k_ctx::sp); }
 
 }  // extern "C"

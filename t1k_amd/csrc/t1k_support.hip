@@ -29,6 +29,10 @@
 // No LDS, no atomics on data (the flag word of the check excepted).  The table and its fold are a T1kCountTable (t1k_table.h), folded
 // whenever the pending keys reach a bound (2^28, env T1K_SUPPORT_PENDING) and at _get.  One table for both families keeps a call atomic:
 // one t1k_table_room, one t1k_table_commit, one fold.
+// Shared with the other sparse stages, and not written out here: the session (ctx->sup, a T1kStage: state checks, _get, _stats, _end, the
+// site arguments of _begin) and the check / sum / emit sequence of _add (t1k_stage_two_pass) in t1k_table.h; the checks of records and
+// booking lists (pileupBookLists) and the staging (pileupStage) in t1k_walk.h.  Here: the kernel, the key families' bounds, the checks of
+// a record's t1k_support_rec and of a booking's template.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -111,39 +115,34 @@ extern "C" {
 
 int t1k_support_begin(t1k_ctx *ctx, uint32_t nAlleles, const uint64_t *alleleOff, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos) {
   if (!ctx) return T1K_ERR_ARG;
-  if (ctx->supOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_support_begin: a table is open already (t1k_support_end first)");
+  T1kStage &s = ctx->sup;
+  int rc;
+  if ((rc = t1k_stage_closed(ctx, s))) return rc;
   // (site * 7 + state) takes 31 bits at most: family A stays below 2^57, family B below 2^58
   if (nSites > (1ull << 28)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_support_begin: more than 2^28 sites");
-  if (nSites && (!siteAllele || !sitePos)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_begin: bad arguments (NULL arrays, or alleleOff not starting at 0)");
-  int rc;
-  if ((rc = pileupCheckOffsets(ctx, "t1k_support_begin", "NULL arrays, or alleleOff not starting at 0", nAlleles, alleleOff))) return rc;
-  if (nSites > alleleOff[nAlleles]) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_begin: more sites than allele positions (the sites are not strictly ascending)");
-  if ((rc = t1k_sites_build(ctx, "t1k_support_begin", ctx->supMap, nAlleles, alleleOff, nSites, siteAllele, sitePos))) return rc;
-  t1k_table_open(ctx->supTab, (SUPPORT_FAMILY_B << 1) - 1ull, "T1K_SUPPORT_PENDING");
-  ctx->supOpen = true;
-  return T1K_OK;
+  if ((rc = t1k_stage_site_args(ctx, s, nAlleles, alleleOff, nSites, siteAllele, sitePos))) return rc;
+  return t1k_stage_open_sites(ctx, s, nAlleles, alleleOff, nSites, siteAllele, sitePos, (SUPPORT_FAMILY_B << 1) - 1ull);
 }
 
 int t1k_support_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const t1k_support_rec *rec, const uint64_t *bookPtr, const t1k_support_book *book, const char *text,
                     uint64_t textBytes, const int8_t *ops, uint64_t opsBytes, double *kernelMs) {
   if (!ctx) return T1K_ERR_ARG;
   if (kernelMs) *kernelMs = 0;
-  if (!ctx->supOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_support_add: no table is open (t1k_support_begin first)");
+  T1kStage &s = ctx->sup;
+  int rc;
+  if ((rc = t1k_stage_opened(ctx, s, "_add", "_begin"))) return rc;
   if (n == 0) return T1K_OK;
   if (!aln || !rec || !bookPtr || (textBytes && !text) || (opsBytes && !ops)) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_add: bad arguments (NULL arrays)");
   // what the host can tell from the records and the booking lists alone; the strings themselves are walked on the device before anything is emitted
-  const std::vector<uint64_t> &off = ctx->supMap.off;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (bookPtr[i + 1] < bookPtr[i]) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_add: bookPtr decreases at record " + std::to_string(i));
-    if (bookPtr[i + 1] - bookPtr[i] >= (1ull << 31)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_support_add: record " + std::to_string(i) + " has 2^31 bookings or more");
-    const std::string fault = pileupRecordFault(aln[i], i, off, textBytes, opsBytes);
-    if (!fault.empty()) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_add: " + fault);
-    if (rec[i].strand > 1) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_add: record " + std::to_string(i) + " has a strand other than 0 or 1");
-    if (rec[i].read_len == 0 || rec[i].read_len > SUPPORT_MAX_READ) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_add: the read length of record " + std::to_string(i) + " lies outside 1 .. 65535");
-    if (rec[i].clip_front > rec[i].read_len) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_add: the read window of record " + std::to_string(i) + " starts behind its read");
-  }
-  const uint64_t book0 = bookPtr[0], nBook = bookPtr[n] - book0;
-  if (nBook && !book) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_add: bad arguments (NULL book)");
+  const std::vector<uint64_t> &off = s.off;
+  std::vector<uint64_t> bp;
+  if ((rc = pileupBookLists(ctx, "t1k_support_add", aln, n, off, textBytes, opsBytes, bookPtr, 31, book, "book", [&](uint32_t i) -> std::string {
+        if (rec[i].strand > 1) return "record " + std::to_string(i) + " has a strand other than 0 or 1";
+        if (rec[i].read_len == 0 || rec[i].read_len > SUPPORT_MAX_READ) return "the read length of record " + std::to_string(i) + " lies outside 1 .. 65535";
+        if (rec[i].clip_front > rec[i].read_len) return "the read window of record " + std::to_string(i) + " starts behind its read";
+        return std::string();
+      }, bp))) return rc;
+  const uint64_t book0 = bookPtr[0], nBook = bp[n];
   for (uint32_t i = 0; i < n; ++i) {
     const uint64_t alleleLen = off[aln[i].allele + 1] - off[aln[i].allele];
     for (uint64_t j = bookPtr[i]; j < bookPtr[i + 1]; ++j) {
@@ -153,82 +152,32 @@ int t1k_support_add(t1k_ctx *ctx, const t1k_pileup_aln *aln, uint32_t n, const t
       if (e.t_end >= alleleLen) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_support_add: the template of booking " + std::to_string(j) + " leaves its allele");
     }
   }
-  std::vector<uint64_t> bp(n + 1);
-  for (uint32_t i = 0; i <= n; ++i) bp[i] = bookPtr[i] - book0;
   T1K_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   SupportArgs a{};
-  a.in = PileupBatch{aln, n, text, textBytes, ops, t1k_sites_offsets(ctx->supMap), nullptr};
+  a.in = PileupBatch{aln, n, text, textBytes, ops, t1k_sites_offsets(s.map), nullptr};
   size_t oRec = 0, oBp = 0, oBook = 0, oCount = 0;
-  int rc;
-  if ((rc = pileupStage(ctx, ctx->bSupIn, opsBytes, [&](T1kCarve &piece) {
+  if ((rc = pileupStage(ctx, s.in, opsBytes, [&](T1kCarve &piece) {
         oRec = piece(sizeof(t1k_support_rec) * (size_t)n); oBp = piece(8ull * (n + 1ull)); oBook = piece(sizeof(t1k_support_book) * nBook); oCount = piece(8ull * (n + 1ull));
       }, a.in))) return rc;
-  char *D = (char *)ctx->bSupIn.p;
+  char *D = (char *)s.in.p;
   T1K_HIP(ctx, hipMemcpyAsync(D + oRec, rec, sizeof(t1k_support_rec) * (size_t)n, hipMemcpyHostToDevice, st));
   T1K_HIP(ctx, hipMemcpyAsync(D + oBp, bp.data(), 8ull * (n + 1ull), hipMemcpyHostToDevice, st));
   if (nBook) T1K_HIP(ctx, hipMemcpyAsync(D + oBook, book + book0, sizeof(t1k_support_book) * nBook, hipMemcpyHostToDevice, st));
   T1K_HIP(ctx, hipMemsetAsync(D + oCount, 0, 8ull * (n + 1ull), st));
-  a.sites = t1k_sites_view(ctx->supMap);
+  a.sites = t1k_sites_view(s.map);
   a.rec = (const t1k_support_rec *)(D + oRec);
   a.bookPtr = (const unsigned long long *)(D + oBp); a.book = (const t1k_support_book *)(D + oBook);
   a.count = (unsigned long long *)(D + oCount);
   const unsigned grid = t1k_grid(ctx, n, 4);
-  T1K_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-  hipLaunchKernelGGL(k_support<false>, dim3(grid), dim3(256), 0, st, a);
-  T1K_HIP(ctx, hipGetLastError());
-  uint32_t flag = 0;
-  T1K_HIP(ctx, hipMemcpyAsync(&flag, a.in.flag, 4, hipMemcpyDeviceToHost, st));
-  T1K_HIP(ctx, hipStreamSynchronize(st));
-  if (flag) return t1k_fail(ctx, T1K_ERR_ARG, pileupRefusal("t1k_support_add", "nothing emitted", flag));
-  if ((rc = t1k_exclusive_sum_u64(ctx, a.count, a.count, (uint64_t)n + 1))) return rc;  // (in place: every tile is read before it is written)
-  unsigned long long emit = 0;
-  T1K_HIP(ctx, hipMemcpyAsync(&emit, a.count + n, 8, hipMemcpyDeviceToHost, st));
-  T1K_HIP(ctx, hipStreamSynchronize(st));
-  if (emit == 0) {
-    T1K_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    T1K_HIP(ctx, hipStreamSynchronize(st));
-    float ms0 = 0;
-    if (kernelMs && hipEventElapsedTime(&ms0, ctx->ev[0], ctx->ev[1]) == hipSuccess) *kernelMs = ms0;
-    return T1K_OK;
-  }
-  if ((rc = t1k_table_room(ctx, "t1k_support", ctx->supTab, emit, "lower T1K_SUPPORT_PENDING, or add fewer records per call", &a.keys, &a.vals))) return rc;
-  hipLaunchKernelGGL(k_support<true>, dim3(grid), dim3(256), 0, st, a);
-  T1K_HIP(ctx, hipGetLastError());
-  T1K_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-  T1K_HIP(ctx, hipStreamSynchronize(st));  // text / ops / book are the caller's again, the staging block the next call's
-  float ms = 0;
-  if (kernelMs && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) *kernelMs = ms;
-  return t1k_table_commit(ctx, "t1k_support", ctx->supTab, emit);
+  return t1k_stage_two_pass(ctx, s, n, a.in.flag, a.count, kernelMs, [&] { hipLaunchKernelGGL(k_support<false>, dim3(grid), dim3(256), 0, st, a); },
+                            [&](unsigned long long *keys, uint32_t *vals) { a.keys = keys; a.vals = vals; hipLaunchKernelGGL(k_support<true>, dim3(grid), dim3(256), 0, st, a); });
 }
 
-int t1k_support_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (nRuns) *nRuns = 0;
-  if (!ctx->supOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_support_get: no table is open");
-  T1K_HIP(ctx, hipSetDevice(ctx->device));
-  return t1k_table_get(ctx, "t1k_support", ctx->supTab, keys, counts, cap, nRuns);
-}
+int t1k_support_get(t1k_ctx *ctx, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) { return t1k_stage_get(ctx, &t1k_ctx::sup, keys, counts, cap, nRuns); }
 
-int t1k_support_stats(t1k_ctx *ctx, uint64_t *keysEmitted, uint64_t *folds, double *foldMs) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (!ctx->supOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_support_stats: no table is open");
-  if (keysEmitted) *keysEmitted = ctx->supTab.emitted;
-  if (folds) *folds = ctx->supTab.folds;
-  if (foldMs) *foldMs = ctx->supTab.foldMs;
-  return T1K_OK;
-}
+int t1k_support_stats(t1k_ctx *ctx, uint64_t *keysEmitted, uint64_t *folds, double *foldMs) { return t1k_stage_stats(ctx, &t1k_ctx::sup, keysEmitted, folds, foldMs); }
 
-int t1k_support_end(t1k_ctx *ctx) {
-  if (!ctx) return T1K_ERR_ARG;
-  if (!ctx->supOpen) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_support_end: no table is open");
-  ctx->supOpen = false;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  t1k_sites_close(ctx->supMap);
-  t1k_table_close(ctx->supTab);
-  if (ctx->bSupIn.p) { (void)t1k_dev_free(ctx->bSupIn.p); ctx->bSupIn.p = nullptr; ctx->bSupIn.bytes = 0; }
-  return T1K_OK;
-}
+int t1k_support_end(t1k_ctx *ctx) { return t1k_stage_end(ctx, &t1k_ctx::sup); }
 
 }  // extern "C"

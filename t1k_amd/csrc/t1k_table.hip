@@ -1,5 +1,5 @@
-// t1k_amd/csrc/t1k_table.hip -- the host side of t1k_table.h: the site map's builder and the sparse count table's reserve / fold / read,
-// shared by t1k_sitepile.hip, t1k_support.hip and t1k_phase.hip.
+// t1k_amd/csrc/t1k_table.hip -- the host side of t1k_table.h: the site map's builder, the sparse count table's reserve / fold / read and
+// the session around them (T1kStage), shared by t1k_sitepile.hip, t1k_support.hip, t1k_phase.hip and t1k_indel.hip.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -15,7 +15,8 @@ __global__ __launch_bounds__(256) void k_table_counts(const uint32_t *incl, cons
   }
 }
 
-int t1k_sites_build(t1k_ctx *ctx, const char *who, T1kSiteMap &m, uint32_t nAlleles, const uint64_t *alleleOff, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos) {
+// (what t1k_stage_open_sites says of the sites; who: the _begin's name)
+static int sitesBuild(t1k_ctx *ctx, const char *who, T1kSiteMap &m, uint32_t nAlleles, const uint64_t *alleleOff, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos) {
   const std::string W(who);
   const uint64_t words = alleleOff[nAlleles] / 64 + 1;
   std::vector<uint64_t> bits(words, 0);
@@ -40,7 +41,6 @@ int t1k_sites_build(t1k_ctx *ctx, const char *who, T1kSiteMap &m, uint32_t nAlle
   T1K_HIP(ctx, hipMemcpyAsync(D + oRank, rank.data(), 4 * words, hipMemcpyHostToDevice, ctx->stream));
   T1K_HIP(ctx, hipMemcpyAsync(D + oOff, alleleOff, 8ull * (nAlleles + 1), hipMemcpyHostToDevice, ctx->stream));
   T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  m.off.assign(alleleOff, alleleOff + nAlleles + 1);
   m.at[0] = oBits; m.at[1] = oRank; m.at[2] = oOff;
   m.nSites = nSites;
   return T1K_OK;
@@ -50,13 +50,8 @@ static void tableFree(T1kDevBuf &b) {
   if (b.p) { (void)t1k_dev_free(b.p); b.p = nullptr; b.bytes = 0; }
 }
 
-void t1k_sites_close(T1kSiteMap &m) {
-  m.off.clear();
-  m.nSites = 0;
-  tableFree(m.buf);
-}
-
-void t1k_table_open(T1kCountTable &t, unsigned long long largestKey, const char *boundEnv) {
+// an empty table whose keys are all <= largestKey; boundEnv: the environment variable that overrides the pending bound of 2^28
+static void tableOpen(T1kCountTable &t, unsigned long long largestKey, const char *boundEnv) {
   t.endBit = t1k_bits(largestKey);
   t.runs = t.pending = t.emitted = t.folds = 0;
   t.foldMs = 0;
@@ -152,19 +147,89 @@ int t1k_table_commit(t1k_ctx *ctx, const char *who, T1kCountTable &t, uint64_t e
   return T1K_OK;
 }
 
-int t1k_table_get(t1k_ctx *ctx, const char *who, T1kCountTable &t, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) {
+// ---- the session ----
+static int stageState(t1k_ctx *ctx, const T1kStage &s, const char *fn, const std::string &what) { return t1k_fail(ctx, T1K_ERR_STATE, std::string(s.who) + fn + ": " + what); }
+
+int t1k_stage_closed(t1k_ctx *ctx, const T1kStage &s) {
+  return s.open ? stageState(ctx, s, "_begin", std::string("a table is open already (") + s.who + "_end first)") : T1K_OK;
+}
+
+int t1k_stage_opened(t1k_ctx *ctx, const T1kStage &s, const char *fn, const char *hint) {
+  if (s.open) return T1K_OK;
+  return stageState(ctx, s, fn, hint ? std::string("no table is open (") + s.who + hint + " first)" : std::string("no table is open"));
+}
+
+int t1k_stage_site_args(t1k_ctx *ctx, const T1kStage &s, uint32_t nAlleles, const uint64_t *alleleOff, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos) {
+  const std::string begin = std::string(s.who) + "_begin";
+  if (nSites && (!siteAllele || !sitePos)) return t1k_fail(ctx, T1K_ERR_ARG, begin + ": bad arguments (NULL arrays, or alleleOff not starting at 0)");
   int rc;
-  if ((rc = tableFold(ctx, who, t)) != T1K_OK) return rc;
+  if ((rc = pileupCheckOffsets(ctx, begin.c_str(), "NULL arrays, or alleleOff not starting at 0", nAlleles, alleleOff))) return rc;
+  if (nSites > alleleOff[nAlleles]) return t1k_fail(ctx, T1K_ERR_ARG, begin + ": more sites than allele positions (the sites are not strictly ascending)");
+  return T1K_OK;
+}
+
+void t1k_stage_open(T1kStage &s, uint32_t nAlleles, const uint64_t *alleleOff, unsigned long long largestKey) {
+  s.off.assign(alleleOff, alleleOff + nAlleles + 1);
+  tableOpen(s.tab, largestKey, s.boundEnv);
+  s.open = true;
+}
+
+int t1k_stage_open_sites(t1k_ctx *ctx, T1kStage &s, uint32_t nAlleles, const uint64_t *alleleOff, uint64_t nSites, const uint32_t *siteAllele, const uint32_t *sitePos,
+                         unsigned long long largestKey) {
+  int rc;
+  if ((rc = sitesBuild(ctx, (std::string(s.who) + "_begin").c_str(), s.map, nAlleles, alleleOff, nSites, siteAllele, sitePos))) return rc;
+  t1k_stage_open(s, nAlleles, alleleOff, largestKey);
+  return T1K_OK;
+}
+
+int t1k_stage_get(t1k_ctx *ctx, T1kStage t1k_ctx::*which, uint64_t *keys, int32_t *counts, uint64_t cap, uint64_t *nRuns) {
+  if (!ctx) return T1K_ERR_ARG;
+  if (nRuns) *nRuns = 0;
+  T1kStage &s = ctx->*which;
+  T1kCountTable &t = s.tab;
+  int rc;
+  if ((rc = t1k_stage_opened(ctx, s, "_get"))) return rc;
+  T1K_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = tableFold(ctx, s.who, t)) != T1K_OK) return rc;
   if (nRuns) *nRuns = t.runs;
   if (!keys || !counts || !t.runs) return T1K_OK;  // the size query
-  if (cap < t.runs) return t1k_fail(ctx, T1K_ERR_ARG, std::string(who) + "_get: the buffers are too small");
+  if (cap < t.runs) return t1k_fail(ctx, T1K_ERR_ARG, std::string(s.who) + "_get: the buffers are too small");
   T1K_HIP(ctx, hipMemcpyAsync(keys, t.keys.p, 8 * t.runs, hipMemcpyDeviceToHost, ctx->stream));
   T1K_HIP(ctx, hipMemcpyAsync(counts, t.vals.p, 4 * t.runs, hipMemcpyDeviceToHost, ctx->stream));
   T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return T1K_OK;
 }
 
-void t1k_table_close(T1kCountTable &t) {
-  t.runs = t.pending = t.cap = 0;
-  for (T1kDevBuf *b : {&t.keys, &t.vals, &t.work}) tableFree(*b);
+int t1k_stage_stats(t1k_ctx *ctx, T1kStage t1k_ctx::*which, uint64_t *keysEmitted, uint64_t *folds, double *foldMs) {
+  if (!ctx) return T1K_ERR_ARG;
+  const T1kStage &s = ctx->*which;
+  int rc;
+  if ((rc = t1k_stage_opened(ctx, s, "_stats"))) return rc;
+  if (keysEmitted) *keysEmitted = s.tab.emitted;
+  if (folds) *folds = s.tab.folds;
+  if (foldMs) *foldMs = s.tab.foldMs;
+  return T1K_OK;
+}
+
+int t1k_stage_end(t1k_ctx *ctx, T1kStage t1k_ctx::*which) {
+  if (!ctx) return T1K_ERR_ARG;
+  T1kStage &s = ctx->*which;
+  int rc;
+  if ((rc = t1k_stage_opened(ctx, s, "_end"))) return rc;
+  s.open = false;
+  (void)hipSetDevice(ctx->device);
+  (void)hipStreamSynchronize(ctx->stream);
+  s.off.clear();
+  s.map.nSites = 0;
+  s.tab.runs = s.tab.pending = s.tab.cap = 0;
+  t1k_stage_blocks(s, [](const std::string &, T1kDevBuf &b) { tableFree(b); });
+  return T1K_OK;
+}
+
+int t1k_stage_done(t1k_ctx *ctx, double *kernelMs) {
+  T1K_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+  T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float ms = 0;
+  if (kernelMs && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) *kernelMs = ms;
+  return T1K_OK;
 }

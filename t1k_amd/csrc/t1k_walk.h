@@ -6,7 +6,8 @@
 // walks the string.  The loop control is wave-uniform, so the per-column callback runs with all 64 lanes converged and may itself use
 // cross-lane operations.
 // Host: the front end of a batch of t1k_pileup_aln records -- the allele offsets of a _begin call, the per-record checks of an _add call,
-// the staging of aln / text / ops / the flag word, and the message of a batch the device refused.
+// the checks of its booking lists (t1k_sitepile.hip, t1k_support.hip, t1k_indel.hip), the staging of aln / text / ops / the flag word, and
+// the message of a batch the device refused.
 #pragma once
 #include <string>
 #include <vector>
@@ -113,6 +114,27 @@ static inline std::string pileupRecordFault(const t1k_pileup_aln &r, uint32_t i,
   if (r.read_at > textBytes) return "the read window of record " + std::to_string(i) + " starts behind `text`";
   if (r.seq_start > off[r.allele + 1] - off[r.allele]) return "record " + std::to_string(i) + " starts behind its allele";
   return std::string();
+}
+
+// the booking lists of an _add call whose record i books once per entry of book[bookPtr[i] .. bookPtr[i + 1]), and with them the records:
+// per record, in this order, bookPtr decreases (T1K_ERR_ARG), 2^bookBits bookings or more (T1K_ERR_CAPACITY), pileupRecordFault, and the
+// stage's own checks of the record, own(i): the fault in words, T1K_ERR_ARG, or empty; then bookings without a `book` (bookName: the
+// argument's name).  bp: bookPtr rebased to the call's first booking, bp[n] the call's bookings
+template <class Own>
+static inline int pileupBookLists(t1k_ctx *ctx, const std::string &who, const t1k_pileup_aln *aln, uint32_t n, const std::vector<uint64_t> &off, uint64_t textBytes, uint64_t opsBytes,
+                                  const uint64_t *bookPtr, int bookBits, const void *book, const char *bookName, Own &&own, std::vector<uint64_t> &bp) {
+  for (uint32_t i = 0; i < n; ++i) {
+    if (bookPtr[i + 1] < bookPtr[i]) return t1k_fail(ctx, T1K_ERR_ARG, who + ": bookPtr decreases at record " + std::to_string(i));
+    if (bookPtr[i + 1] - bookPtr[i] >= (1ull << bookBits))
+      return t1k_fail(ctx, T1K_ERR_CAPACITY, who + ": record " + std::to_string(i) + " has 2^" + std::to_string(bookBits) + " bookings or more");
+    std::string fault = pileupRecordFault(aln[i], i, off, textBytes, opsBytes);
+    if (fault.empty()) fault = own(i);
+    if (!fault.empty()) return t1k_fail(ctx, T1K_ERR_ARG, who + ": " + fault);
+  }
+  if (bookPtr[n] != bookPtr[0] && !book) return t1k_fail(ctx, T1K_ERR_ARG, who + ": bad arguments (NULL " + bookName + ")");
+  bp.resize((size_t)n + 1);
+  for (uint32_t i = 0; i <= n; ++i) bp[i] = bookPtr[i] - bookPtr[0];
+  return T1K_OK;
 }
 
 // in: the caller's aln / n / text / textBytes / ops and the device's alleleOff.  Copies the three arrays into `buf` -- [aln | text | ops |

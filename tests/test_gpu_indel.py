@@ -165,6 +165,16 @@ def test_fold_merges_a_folded_count_with_pending_keys(ctx, monkeypatch):
     assert keys == [_key(90, 0, 4, 0, 1), _key(90, 0, 4, 0, 0)] and counts == [1, 512] and stats[:6] == (2, 0, 0, 0, 513, 2)
 
 
+def test_a_second_session_holds_no_more_device_memory(ctx):
+    """_end frees every block of the stage: what the context holds behind one begin / add / get / end (its scan and sort scratch stays, by
+    design) is what it holds behind the next"""
+    args = _edge([(30, [("M", 60), ("D", 4), ("M", 10)])], [[1]])
+    ctx.indel(*args)
+    held = ctx.mem_bytes()
+    ctx.indel(*args)
+    assert ctx.mem_bytes() == held
+
+
 # ---- 4. argument errors --------------------------------------------------------------------------------------------------------------
 def test_argument_errors_emit_nothing(built):
     c = t1k_amd.Context()
@@ -184,7 +194,7 @@ def test_argument_errors_emit_nothing(built):
         def table():
             return ref.from_runs(*c.indel_get())
         one = (u8(0), np.array([0, 1], np.uint64), u8(1))
-        assert c.indel_add(rec(), *one, text, ops, raw=True) == ERR_STATE                          # add / get / end before begin
+        assert c.indel_add(rec(), *one, text, ops, raw=True) == ERR_STATE and c.last_error().startswith("t1k_indel_add: ")   # add / get / end before begin
         assert c.indel_get(raw=True) == ERR_STATE and c.indel_end(raw=True) == ERR_STATE
         assert c.indel_begin(off, b"ACGTACGT" + b"GGnCC", raw=True) == ERR_ARG                     # a byte outside ACGTN
         assert c.indel_begin(off, b"ACGTACGT" + b"GG-CC", raw=True) == ERR_ARG
@@ -203,6 +213,7 @@ def test_argument_errors_emit_nothing(built):
         def refused(bad, strand=0, ptr=(3, 4), uniq=(0,), code=ERR_ARG):
             p = np.concatenate([gp, np.array(ptr[1:], np.uint64)])
             assert c.indel_add(np.concatenate([good, bad]), np.concatenate([gs, u8(strand)]), p, np.concatenate([gu, u8(*uniq)]), text, ops, raw=True) == code
+            assert c.last_error().startswith("t1k_indel_add: ")                                   # whoever refused it, host or device
             assert table() == before and c.indel_stats()[:5] == ref.stats(sound) + (5,)          # the sound records of the call emit nothing either
         # what pileupRecordFault and the device check refuse
         refused(rec(ops_at=6, n_ops=3))                   # op value 4

@@ -186,6 +186,17 @@ def test_fold_merges_a_folded_count_with_pending_keys(ctx, monkeypatch):
     assert stats["folds"] == 2 and sorted(c.tolist() for c in want.values()) == [[4, 0], [4, 0], [5, 1]]
 
 
+def test_a_second_session_holds_no_more_device_memory(ctx):
+    """_end frees every block of the stage: what the context holds behind one begin / add / get / end (its scan and sort scratch stays, by
+    design) is what it holds behind the next"""
+    t = Edges()
+    t.book(t.rec(0, 0, 3))
+    _kernel(ctx, t.done())
+    held = ctx.mem_bytes()
+    _kernel(ctx, t)
+    assert ctx.mem_bytes() == held
+
+
 # ---- 3. argument errors --------------------------------------------------------------------------------------------------------------
 def test_argument_errors_leave_the_table_alone(built):
     c = t1k_amd.Context()
@@ -200,7 +211,7 @@ def test_argument_errors_leave_the_table_alone(built):
 
         def table():
             return ref.from_runs(*c.phase_get(), len(sa))
-        assert c.phase_add(rec(), [[0, NO]], [1], text, ops, raw=True) == ERR_STATE              # add / get / stats / end before begin
+        assert c.phase_add(rec(), [[0, NO]], [1], text, ops, raw=True) == ERR_STATE and c.last_error().startswith("t1k_phase_add: ")   # add / get / stats / end before begin
         assert c.phase_get(raw=True) == ERR_STATE and c.phase_stats(raw=True) == ERR_STATE and c.phase_end(raw=True) == ERR_STATE
         for bad_a, bad_p in (([0, 0], [7, 1]), ([1, 0], [0, 1]), ([0, 0], [3, 3]), ([0], [8]), ([2], [0])):
             assert c.phase_begin(off, np.array(bad_a, np.uint32), np.array(bad_p, np.uint32), raw=True) == ERR_ARG
@@ -220,6 +231,7 @@ def test_argument_errors_leave_the_table_alone(built):
 
         def refused(bad, book=(3, NO), code=ERR_ARG):
             assert c.phase_add(np.concatenate([good, bad]), gr + [list(book)], gu + [0], text, ops, raw=True) == code   # the sound bookings of the call emit nothing either
+            assert c.last_error().startswith("t1k_phase_add: ")                                   # whoever refused it, host or device
             assert ref.same(table(), before) and c.phase_stats() == stats
         refused(rec(), book=(4, NO))                      # a record index equal to n
         refused(rec(), book=(3, 4))                       # ... as the mate

@@ -107,6 +107,16 @@ def test_fold_merges_a_folded_count_with_pending_keys(ctx, monkeypatch):
     assert ref.same(ref.from_runs(keys, counts, 1), _edge_want(args))
 
 
+def test_a_second_session_holds_no_more_device_memory(ctx):
+    """_end frees every block of the stage: what the context holds behind one begin / add / get / end (its scan and sort scratch stays, by
+    design) is what it holds behind the next"""
+    args = _edge([[(2 << 1) | 1]])
+    ctx.sitepile(*args)
+    held = ctx.mem_bytes()
+    ctx.sitepile(*args)
+    assert ctx.mem_bytes() == held
+
+
 # ---- 2. argument errors --------------------------------------------------------------------------------------------------------------
 def test_argument_errors_emit_nothing(built):
     c = t1k_amd.Context()
@@ -122,7 +132,7 @@ def test_argument_errors_emit_nothing(built):
         def table():
             return ref.from_runs(*c.sitepile_get(), len(sa))
         one = (np.array([0, 1], np.uint64), np.array([(2 << 1) | 1], np.uint32))
-        assert c.sitepile_add(rec(), one[0], one[1], text, ops, raw=True) == ERR_STATE          # add / get / end before begin
+        assert c.sitepile_add(rec(), one[0], one[1], text, ops, raw=True) == ERR_STATE and c.last_error().startswith("t1k_sitepile_add: ")   # add / get / end before begin
         assert c.sitepile_get(raw=True) == ERR_STATE and c.sitepile_end(raw=True) == ERR_STATE
         # sites: unsorted, duplicate, behind their allele, on an unknown allele; a key space that is too large
         for bad_a, bad_p in (([0, 0], [7, 1]), ([1, 0], [0, 1]), ([0, 0], [3, 3]), ([0], [8]), ([2], [0])):
@@ -143,6 +153,7 @@ def test_argument_errors_emit_nothing(built):
             p = np.concatenate([gp, np.array(ptr[1:], np.uint64)])
             b = np.concatenate([gb, np.array(book, np.uint32)])
             assert c.sitepile_add(np.concatenate([good, bad]), p, b, text, ops, raw=True) == code    # the sound records of the call emit nothing either
+            assert c.last_error().startswith("t1k_sitepile_add: ")                                    # whoever refused it, host or device
             assert ref.same(table(), before)
         refused(rec(ops_at=3, n_ops=5))                   # op value 4
         refused(rec(allele=1, seq_start=1, n_ops=5))      # a walk one base past the allele (5 bases from position 1 of 5)

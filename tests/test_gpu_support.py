@@ -120,6 +120,16 @@ def test_fold_merges_a_folded_count_with_pending_keys(ctx, monkeypatch):
     assert ref.same(ref.from_runs(keys, counts, 1), _edge_want(args))
 
 
+def test_a_second_session_holds_no_more_device_memory(ctx):
+    """_end frees every block of the stage: what the context holds behind one begin / add / get / end (its scan and sort scratch stays, by
+    design) is what it holds behind the next"""
+    args = _edge([[(1, 0, 4)]])
+    ctx.support(*args)
+    held = ctx.mem_bytes()
+    ctx.support(*args)
+    assert ctx.mem_bytes() == held
+
+
 # ---- 2. argument errors --------------------------------------------------------------------------------------------------------------
 def test_argument_errors_emit_nothing(built):
     c = t1k_amd.Context()
@@ -141,7 +151,7 @@ def test_argument_errors_emit_nothing(built):
         def table():
             return ref.from_runs(*c.support_get(), len(sa))
         one = (np.array([0, 1], np.uint64), books((1, 0, 4)))
-        assert c.support_add(rec(), end(), one[0], one[1], text, ops, raw=True) == ERR_STATE        # add / get / end before begin
+        assert c.support_add(rec(), end(), one[0], one[1], text, ops, raw=True) == ERR_STATE and c.last_error().startswith("t1k_support_add: ")   # add / get / end before begin
         assert c.support_get(raw=True) == ERR_STATE and c.support_end(raw=True) == ERR_STATE
         # sites: unsorted, duplicate, behind their allele, on an unknown allele; more than 2^28 of them
         for bad_a, bad_p in (([0, 0], [7, 1]), ([1, 0], [0, 1]), ([0, 0], [3, 3]), ([0], [8]), ([2], [0])):
@@ -165,6 +175,7 @@ def test_argument_errors_emit_nothing(built):
             b = np.concatenate([gb, books(*book)])
             e = np.concatenate([ge, end() if bad_end is None else bad_end])
             assert c.support_add(np.concatenate([good, bad]), e, p, b, text, ops, raw=True) == code    # the sound records of the call emit nothing either
+            assert c.last_error().startswith("t1k_support_add: ")                                        # whoever refused it, host or device
             assert ref.same(table(), before)
         # what t1k_sitepile_add refuses
         refused(rec(ops_at=3, n_ops=5))                   # op value 4
