@@ -562,6 +562,24 @@ int t1k_alt_batch(t1k_ctx *ctx, uint64_t nGroups, const uint64_t *groupPtr /* [n
                   const uint32_t *alleleGene /* [nAlleles] */, uint32_t nGenes, const uint32_t *slotOf /* [nAlleles] */, uint64_t *tables /* [4 * nAlleles] */, double *kernelMs /* may be NULL */);
 uint64_t t1k_alt_pieces(uint64_t nGroups, const uint64_t *groupPtr);
 
+/* ---- co-occurrence of allele-pair candidates (genotyper --diplotypes) ------------------------------------------------------------
+ * Stateless; all pointers are host pointers.  The read groups as a CSR over candidate ids: group g holds entryCand[groupPtr[g] ..
+ * groupPtr[g + 1]), strictly ascending, and weighs q[g] (as t1k_alt_batch).  Ids are gene-major: gene x owns the ids candPtr[x] ..
+ * candPtr[x + 1), n_x of them.  matrix = sum of n_x^2 64-bit cells; the block of gene x begins at the sum of n_y^2 over y < x; cell (i, j)
+ * of local ids at i * n_x + j holds, for i <= j, the sum of q over the groups that hold both candidates (the diagonal: the candidate's
+ * total); the cells i > j are 0.  The sums are 64-bit integers (global atomic adds): the same bits for every launch shape, piece size and
+ * run.  The entries are uploaded in pieces cut at group boundaries, 2^24 entries each (env T1K_DIPLO_PIECE, in entries, read by every
+ * call); a group longer than a piece is a piece of its own; the matrix stays on the device across the pieces and is copied out once.
+ * t1k_diplo_pieces: how many pieces a call with this groupPtr makes.
+ * Every check is made before the first launch and nothing is written unless all of them pass.  T1K_ERR_ARG: groupPtr[0] != 0 or a groupPtr
+ * that decreases; candPtr[0] != 0 or a candPtr that decreases; an entry >= candPtr[nGenes]; the entries of a group not strictly ascending;
+ * a NULL array that would be read.  T1K_ERR_CAPACITY: a gene with more than 2048 candidates; more than 2^29 cells; the sum of q over all
+ * groups -- the bound of every cell -- could reach 2^63; 2^32 groups or more.  nGroups == 0: T1K_OK, the matrix is zeroed.  kernelMs (may
+ * be NULL): device time of the pieces' kernels. */
+int t1k_diplo_batch(t1k_ctx *ctx, uint64_t nGroups, const uint64_t *groupPtr /* [nGroups + 1] */, const uint32_t *entryCand, const uint64_t *q /* [nGroups] */, uint32_t nGenes,
+                    const uint32_t *candPtr /* [nGenes + 1] */, uint64_t *matrix, double *kernelMs /* may be NULL */);
+uint64_t t1k_diplo_pieces(uint64_t nGroups, const uint64_t *groupPtr);
+
 /* ---- profiling counters of the last t1k_assign_batch (algorithmic-traffic terms of SURVEY.md 8d) --------------- */
 typedef struct {
   uint64_t read_ends, lookups, postings, hits, groups, candidates, extended, near_best, dp_calls, rows, batches;
@@ -636,6 +654,8 @@ typedef struct {
   int32_t output_read_assignment;                                     /* --outputReadAssignment */
   int32_t batch_fragments;                                            /* fragments per device batch (0 = default) */
   int32_t alternatives;                                               /* --alternatives: alternatives listed per called allele, 1 .. 1000; 0 = no table */
+  int32_t diplotypes;                                                 /* --diplotypes: allele pairs listed per gene, 1 .. 1000; 0 = no table */
+  int32_t diplo_candidates;                                           /* --diploCandidates: candidates per gene, 2 .. 2048 (default 512) */
 } t1k_job_params;
 void t1k_job_params_default(t1k_job_params *p);
 
@@ -675,12 +695,14 @@ int t1k_job_run(t1k_job *job);
 /* optional, before t1k_job_run: the *_aligned*.fa files (which only need the fragmentAssigned flags) are then written by background
  * threads while the classes are built and the EM runs; t1k_job_write_outputs with the same prefix waits for them */
 int t1k_job_set_output_prefix(t1k_job *job, const char *prefix);
-/* <prefix>_genotype.tsv, _allele.tsv, _aligned*.fa, (_assign.tsv) (Genotyper.cpp:653-718), (_alternatives.tsv: prm.alternatives > 0) */
+/* <prefix>_genotype.tsv, _allele.tsv, _aligned*.fa, (_assign.tsv) (Genotyper.cpp:653-718), (_alternatives.tsv: prm.alternatives > 0), (_diplotypes.tsv: prm.diplotypes > 0) */
 int t1k_job_write_outputs(t1k_job *job, const char *prefix);
 /* results in memory: one line per gene, same text as _genotype.tsv */
 int t1k_job_genotype_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
 /* after t1k_job_run of a job with prm.alternatives > 0 (the rank that writes the tables): the text of <prefix>_alternatives.tsv */
 int t1k_job_alternatives_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
+/* after t1k_job_run of a job with prm.diplotypes > 0 (the rank that writes the tables): the text of <prefix>_diplotypes.tsv */
+int t1k_job_diplotypes_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
 /* per allele of the job's reference, in its order: the gene (index into the lines of _genotype.tsv) and, after t1k_job_run, the abundance; either may be NULL */
 int t1k_job_allele_table(t1k_job *job, int32_t *gene, double *abundance, uint32_t *nAlleles);
 int t1k_job_counts(t1k_job *job, uint64_t *fragments, uint64_t *assignedFragments, uint64_t *groups, uint64_t *ecs, int32_t *emIterations);

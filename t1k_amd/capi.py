@@ -31,7 +31,8 @@ class JobParams(C.Structure):
     _fields_ = [("dev", Params), ("filter_frac", C.c_double), ("filter_cov", C.c_double),
                 ("cross_gene_rate", C.c_double), ("squarem_min_alpha", C.c_double), ("allele_digit_units", C.c_int32),
                 ("allele_delimiter", C.c_char), ("threads", C.c_int32), ("device", C.c_int32),
-                ("output_read_assignment", C.c_int32), ("batch_fragments", C.c_int32), ("alternatives", C.c_int32)]
+                ("output_read_assignment", C.c_int32), ("batch_fragments", C.c_int32), ("alternatives", C.c_int32),
+                ("diplotypes", C.c_int32), ("diplo_candidates", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -86,6 +87,7 @@ assert ROUTE_REC_DTYPE.itemsize == 20
 CIGAR_FILL = 0xAB  # what Context.cigar_batch fills its output arrays with before the call
 ALT_FILL = 0xCD    # what Context.alt_batch fills its tables with before the call
 ALT_EMPTY = 0xFFFFFFFF  # slotOf of an allele that is not called
+DIPLO_FILL = 0xD1  # what Context.diplo_batch fills its matrix with before the call
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_void_p)
 
@@ -161,6 +163,10 @@ def lib():
     L.t1k_alt_pieces.argtypes = [C.c_uint64, vp]
     L.t1k_alt_pieces.restype = C.c_uint64
     L.t1k_job_alternatives_text.argtypes = [vp, C.c_char_p, C.c_uint64, u64p]
+    L.t1k_diplo_batch.argtypes = [vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(C.c_double)]
+    L.t1k_diplo_pieces.argtypes = [C.c_uint64, vp]
+    L.t1k_diplo_pieces.restype = C.c_uint64
+    L.t1k_job_diplotypes_text.argtypes = [vp, C.c_char_p, C.c_uint64, u64p]
     L.t1k_job_allele_table.argtypes = [vp, vp, vp, u32p]
     L.t1k_extract_batch.argtypes = [vp, C.c_uint32, vp, vp]
     L.t1k_extractor_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
@@ -644,6 +650,27 @@ class Context:
         self._check(rc, "t1k_alt_batch")
         return tables, ms.value
 
+    # co-occurrence of the allele-pair candidates of every gene (t1k_diplo_batch)
+    def diplo_batch(self, group_ptr, entry_cand, q, cand_ptr, raw=False):
+        """the read groups as a CSR over candidate ids (uint64 group_ptr [G + 1], uint32 entry_cand), uint64 q [G], uint32 cand_ptr [genes + 1]
+        -> (matrix uint64 [sum of n_x^2]: per gene its n_x * n_x block, cell (i, j) at i * n_x + j, i <= j; the kernels' device time in ms).
+        raw=True: (status code, matrix, ms) without raising; the matrix is filled with DIPLO_FILL bytes before the call.  (More than 2^29
+        cells are refused by the call before it writes: the array then holds 1024 cells only.)"""
+        gp = np.ascontiguousarray(group_ptr, np.uint64)
+        ent = np.ascontiguousarray(entry_cand, np.uint32)
+        qq = np.ascontiguousarray(q, np.uint64)
+        cp = np.ascontiguousarray(cand_ptr, np.uint32)
+        assert len(gp) == len(qq) + 1 and len(cp) >= 1
+        cells = sum((int(cp[x + 1]) - int(cp[x])) ** 2 for x in range(len(cp) - 1))
+        matrix = np.empty(cells if cells <= 1 << 29 else 1024, np.uint64)
+        matrix.view(np.uint8)[:] = DIPLO_FILL
+        ms = C.c_double()
+        rc = lib().t1k_diplo_batch(self.h, len(qq), _ptr(gp), _ptr(ent), _ptr(qq), len(cp) - 1, _ptr(cp), _ptr(matrix), C.byref(ms))
+        if raw:
+            return rc, matrix, ms.value
+        self._check(rc, "t1k_diplo_batch")
+        return matrix, ms.value
+
     # CIGAR / MD / NM of alignments (t1k_cigar_batch; DESIGN §11.6)
     def cigar_batch(self, aln, ops, allele_off, allele_text, clip=None, cigar_cap=None, md_cap=None, raw=False):
         """aln: PILEUP_ALN_DTYPE records (read_at and the weights are ignored); ops: int8 edit columns; allele_text: the alleles' bases back
@@ -880,6 +907,12 @@ def alt_pieces(group_ptr):
     """pieces a t1k_alt_batch call with this group_ptr uploads its entries in (env T1K_ALT_PIECE as the call itself reads it)"""
     gp = np.ascontiguousarray(group_ptr, np.uint64)
     return int(lib().t1k_alt_pieces(max(len(gp) - 1, 0), _ptr(gp)))
+
+
+def diplo_pieces(group_ptr):
+    """pieces a t1k_diplo_batch call with this group_ptr uploads its entries in (env T1K_DIPLO_PIECE as the call itself reads it)"""
+    gp = np.ascontiguousarray(group_ptr, np.uint64)
+    return int(lib().t1k_diplo_pieces(max(len(gp) - 1, 0), _ptr(gp)))
 
 
 def pair_limits():
@@ -1145,6 +1178,14 @@ class Job:
         self._check(lib().t1k_job_alternatives_text(self.h, None, 0, C.byref(need)), "t1k_job_alternatives_text")
         buf = C.create_string_buffer(need.value + 1)
         self._check(lib().t1k_job_alternatives_text(self.h, buf, need.value + 1, C.byref(need)), "t1k_job_alternatives_text")
+        return buf.value.decode()
+
+    def diplotypes_text(self):
+        """the text of <prefix>_diplotypes.tsv (a job created with diplotypes=N, after run())"""
+        need = C.c_uint64()
+        self._check(lib().t1k_job_diplotypes_text(self.h, None, 0, C.byref(need)), "t1k_job_diplotypes_text")
+        buf = C.create_string_buffer(need.value + 1)
+        self._check(lib().t1k_job_diplotypes_text(self.h, buf, need.value + 1, C.byref(need)), "t1k_job_diplotypes_text")
         return buf.value.decode()
 
     def allele_table(self):

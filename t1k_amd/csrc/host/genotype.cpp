@@ -807,4 +807,189 @@ std::string Genotyper::alternativesText(const uint64_t *tab, const std::vector<i
   return text;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// --diplotypes: allele pairs per gene ranked by the weight of the read groups they explain (t1k_diplo.hip)
+// ------------------------------------------------------------------------------------------------------------------
+void Genotyper::diplotypeInput(int maxCand, DiploInput &in) const {
+  const RefSet &R = *ref;
+  const size_t A = R.al.size(), G = nGroups(), nGenes = R.geneName.size();
+  // q[g] as alternativesInput forms it
+  std::vector<uint64_t> q(G);
+  parallelFor(G, [&](size_t g) {
+    float c = groupEnt[groupPtr[g]].weight;
+    for (uint64_t p = groupPtr[g]; p < groupPtr[g + 1]; ++p)
+      if (groupEnt[p].weight > c) c = groupEnt[p].weight;
+    q[g] = (uint64_t)llrint((double)c * 1048576.0);
+  }, 8192);
+  // the groups transposed: per allele the groups of weight > 0 that hold it, ascending; T and W on the way
+  std::vector<uint64_t> listPtr(A + 1, 0), total(A, 0);
+  in.geneWeight.assign(nGenes, 0);
+  {
+    std::vector<uint64_t> seenIn(nGenes, ~0ull);  // the last group that added to the gene's W
+    for (size_t g = 0; g < G; ++g) {
+      if (!q[g]) continue;
+      for (uint64_t p = groupPtr[g]; p < groupPtr[g + 1]; ++p) {
+        const int a = groupEnt[p].allele, x = R.al[a].gene;
+        ++listPtr[a + 1];
+        total[a] += q[g];
+        if (seenIn[x] != g) { seenIn[x] = g; in.geneWeight[x] += q[g]; }
+      }
+    }
+  }
+  for (size_t a = 0; a < A; ++a) listPtr[a + 1] += listPtr[a];
+  std::vector<uint32_t, NoInitAlloc<uint32_t>> list(listPtr[A]);
+  {
+    std::vector<uint64_t> at(listPtr.begin(), listPtr.end() - 1);
+    for (size_t g = 0; g < G; ++g) {
+      if (!q[g]) continue;
+      for (uint64_t p = groupPtr[g]; p < groupPtr[g + 1]; ++p) list[at[groupEnt[p].allele]++] = (uint32_t)g;
+    }
+  }
+  // a hash of every list only orders the comparison: two alleles are one class when their lists are equal, entry by entry
+  std::vector<uint64_t> hash(A);
+  parallelForDynamic(A, 64, [&](size_t a) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (uint64_t p = listPtr[a]; p < listPtr[a + 1]; ++p) h = (h ^ list[p]) * 0x100000001b3ull;
+    hash[a] = h;
+  });
+  auto sameList = [&](int a, int b) {
+    const uint64_t n = listPtr[a + 1] - listPtr[a];
+    return n == listPtr[b + 1] - listPtr[b] && std::equal(list.begin() + listPtr[a], list.begin() + listPtr[a + 1], list.begin() + listPtr[b]);
+  };
+  std::vector<int> called(2 * nGenes, -1);
+  std::vector<std::vector<int>> ofGene(nGenes);
+  for (size_t a = 0; a < A; ++a)
+    if (total[a]) ofGene[R.al[a].gene].push_back((int)a);
+  struct Class { uint64_t total; int rep; uint32_t size; bool isCalled; };
+  std::vector<std::vector<Class>> cand(nGenes);
+  in.nClass.assign(nGenes, 0);
+  parallelForDynamic(nGenes, 1, [&](size_t x) {
+    calledAlleles((int)x, &called[2 * x]);
+    std::vector<int> &mine = ofGene[x];
+    // equal lists next to each other, the smallest index first
+    std::sort(mine.begin(), mine.end(), [&](int a, int b) {
+      if (hash[a] != hash[b]) return hash[a] < hash[b];
+      const auto a0 = list.begin() + listPtr[a], a1 = list.begin() + listPtr[a + 1], b0 = list.begin() + listPtr[b], b1 = list.begin() + listPtr[b + 1];
+      if (std::lexicographical_compare(a0, a1, b0, b1)) return true;
+      if (std::lexicographical_compare(b0, b1, a0, a1)) return false;
+      return a < b;
+    });
+    std::vector<Class> cls;
+    for (size_t i = 0; i < mine.size();) {
+      size_t j = i + 1;
+      while (j < mine.size() && sameList(mine[i], mine[j])) ++j;
+      Class c{total[mine[i]], mine[i], (uint32_t)(j - i), false};
+      for (int k = 1; k >= 0; --k)  // named by the called allele it holds, slot 0 before slot 1
+        if (called[2 * x + k] >= 0 && std::find(mine.begin() + i, mine.begin() + j, called[2 * x + k]) != mine.begin() + j) { c.rep = called[2 * x + k]; c.isCalled = true; }
+      cls.push_back(c);
+      i = j;
+    }
+    in.nClass[x] = (uint32_t)cls.size();
+    auto byWeight = [](const Class &a, const Class &b) { return a.total != b.total ? a.total > b.total : a.rep < b.rep; };
+    std::sort(cls.begin(), cls.end(), byWeight);
+    if (cls.size() > (size_t)maxCand) {
+      std::vector<Class> keep(cls.begin(), cls.begin() + maxCand);
+      for (size_t i = maxCand; i < cls.size(); ++i) {
+        if (!cls[i].isCalled) continue;
+        for (size_t k = keep.size(); k-- > 0;)  // it displaces the last class that is not called (maxCand >= 2 and at most two are called: there is one)
+          if (!keep[k].isCalled) { keep.erase(keep.begin() + k); break; }
+        keep.push_back(cls[i]);
+      }
+      std::sort(keep.begin(), keep.end(), byWeight);
+      cls.swap(keep);
+    }
+    cand[x].swap(cls);
+  });
+  in.candPtr.assign(nGenes + 1, 0);
+  in.candAllele.clear(); in.candEquiv.clear();
+  in.calledCand.assign(2 * nGenes, -1);
+  std::vector<int32_t> candOf(A, -1);  // only the allele that names a class maps to an id
+  std::vector<int> classOf(A, -1);
+  for (size_t x = 0; x < nGenes; ++x) {
+    for (const Class &c : cand[x]) {
+      candOf[c.rep] = (int32_t)in.candAllele.size();
+      in.candAllele.push_back(c.rep);
+      in.candEquiv.push_back(c.size - 1);
+    }
+    in.candPtr[x + 1] = (uint32_t)in.candAllele.size();
+    for (int k = 0; k < 2; ++k) {
+      const int s = called[2 * x + k];
+      if (s < 0 || !total[s]) continue;  // (a called allele that no weighted group holds: as an empty slot)
+      if (candOf[s] >= 0) in.calledCand[2 * x + k] = candOf[s];
+      else  // both called alleles in one class: it is named by slot 0
+        for (uint32_t c = in.candPtr[x]; c < in.candPtr[x + 1]; ++c)
+          if (sameList(in.candAllele[c], s)) in.calledCand[2 * x + k] = (int)c;
+    }
+  }
+  // the groups over candidate ids
+  in.groupPtr.assign(1, 0); in.q.clear(); in.ent.clear();
+  std::vector<uint32_t> ids;
+  for (size_t g = 0; g < G; ++g) {
+    if (!q[g]) continue;
+    ids.clear();
+    for (uint64_t p = groupPtr[g]; p < groupPtr[g + 1]; ++p)
+      if (candOf[groupEnt[p].allele] >= 0) ids.push_back((uint32_t)candOf[groupEnt[p].allele]);
+    if (ids.empty()) continue;
+    std::sort(ids.begin(), ids.end());
+    in.ent.insert(in.ent.end(), ids.begin(), ids.end());
+    in.groupPtr.push_back(in.ent.size());
+    in.q.push_back(q[g]);
+  }
+}
+
+std::string Genotyper::diplotypeText(const DiploInput &in, const uint64_t *matrix, int top) const {
+  const RefSet &R = *ref;
+  const size_t nGenes = R.geneName.size();
+  std::string text = "#gene\trank\tallele1\tallele2\texplained\tonly1\tonly2\tshared\tunexplained\tequiv1\tequiv2\tcalled\tn_cand\tn_class\n";
+  auto w = [](uint64_t v) { char b[64]; snprintf(b, sizeof b, "%.3f", (double)v / 1048576.0); return std::string(b); };
+  struct Pair { uint64_t explained, least; uint32_t i, j; };
+  auto before = [](const Pair &a, const Pair &b) {
+    if (a.explained != b.explained) return a.explained > b.explained;
+    if (a.least != b.least) return a.least > b.least;
+    return a.i != b.i ? a.i < b.i : a.j < b.j;
+  };
+  std::vector<std::string> part(nGenes);
+  uint64_t base = 0;
+  std::vector<uint64_t> blockAt(nGenes);
+  for (size_t x = 0; x < nGenes; ++x) { blockAt[x] = base; const uint64_t n = in.candPtr[x + 1] - in.candPtr[x]; base += n * n; }
+  parallelForDynamic(nGenes, 1, [&](size_t x) {
+    const uint32_t lo = in.candPtr[x], n = in.candPtr[x + 1] - lo;
+    if (!n) return;
+    const uint64_t *M = matrix + blockAt[x];
+    auto make = [&](uint32_t i, uint32_t j) {
+      const uint64_t shared = M[(uint64_t)i * n + j], ti = M[(uint64_t)i * n + i], tj = M[(uint64_t)j * n + j];
+      return Pair{ti + tj - shared, std::min(ti, tj) - shared, i, j};
+    };
+    std::vector<Pair> pairs;
+    pairs.reserve((size_t)n * (n + 1) / 2);
+    for (uint32_t i = 0; i < n; ++i)
+      for (uint32_t j = i; j < n; ++j) pairs.push_back(make(i, j));
+    const size_t shown = std::min(pairs.size(), (size_t)top);
+    // the called pair: the classes of slot 0 and slot 1; one of them alone, or both in one class, is the homozygous pair
+    int ci = in.calledCand[2 * x], cj = in.calledCand[2 * x + 1];
+    if (ci < 0) ci = cj;
+    if (cj < 0) cj = ci;
+    if (ci > cj) std::swap(ci, cj);
+    size_t calledRank = 0;
+    Pair calledPair{};
+    if (ci >= 0) {
+      calledPair = make((uint32_t)ci - lo, (uint32_t)cj - lo);
+      calledRank = 1;
+      for (const Pair &p : pairs) calledRank += before(p, calledPair);
+    }
+    std::partial_sort(pairs.begin(), pairs.begin() + shown, pairs.end(), before);
+    std::string &out = part[x];
+    auto line = [&](const Pair &p, size_t rank, bool isCalled) {
+      const uint64_t shared = M[(uint64_t)p.i * n + p.j], ti = M[(uint64_t)p.i * n + p.i], tj = M[(uint64_t)p.j * n + p.j];
+      out += R.geneName[x] + "\t" + std::to_string(rank) + "\t" + R.al[in.candAllele[lo + p.i]].name + "\t" + R.al[in.candAllele[lo + p.j]].name + "\t" + w(p.explained) + "\t" + w(ti - shared) + "\t" +
+             w(tj - shared) + "\t" + w(shared) + "\t" + w(in.geneWeight[x] - p.explained) + "\t" + std::to_string(in.candEquiv[lo + p.i]) + "\t" + std::to_string(in.candEquiv[lo + p.j]) + "\t" +
+             (isCalled ? "1" : "0") + "\t" + std::to_string(n) + "\t" + std::to_string(in.nClass[x]) + "\n";
+    };
+    for (size_t r = 0; r < shown; ++r) line(pairs[r], r + 1, calledRank == r + 1);
+    if (calledRank > shown) line(calledPair, calledRank, true);
+  });
+  for (size_t x = 0; x < nGenes; ++x) text += part[x];
+  return text;
+}
+
 }  // namespace t1k

@@ -45,6 +45,8 @@ static const char *kUsage =
     "\t--alleleDelimiter CHR: delimiter of the name units (default: automatic)\n"
     "\t--outputReadAssignment: write prefix_assign.tsv\n"
     "\t--alternatives [INT]: write prefix_alternatives.tsv, the INT closest other alleles of every called allele (default: 5; 1 to 1000)\n"
+    "\t--diplotypes [INT]: write prefix_diplotypes.tsv, the INT allele pairs of every gene that explain most reads (default: 10; 1 to 1000)\n"
+    "\t--diploCandidates INT: allele classes per gene that --diplotypes pairs up (default: 512; 2 to 2048)\n"
     "\t--squaremMinAlpha FLOAT: lower bound (negative) of the SQUAREM step length\n"
     "\t--device INT: GPU ordinal (default: $T1K_DEVICE or 0)\n"
     "\t--gpus INT: shard the fragments over the first INT GPUs ($T1K_GPUS=0,1,.. names them; a GPU may be named twice)\n";
@@ -57,7 +59,8 @@ int t1k_genotyper_main(int argc, char **argv) {
                                      {"alleleDigitUnits", required_argument, 0, 1005}, {"alleleDelimiter", required_argument, 0, 1006},
                                      {"alleleWhitelist", required_argument, 0, 1007}, {"outputReadAssignment", no_argument, 0, 1008},
                                      {"squaremMinAlpha", required_argument, 0, 1009}, {"device", required_argument, 0, 1010}, {"gpus", required_argument, 0, 1011},
-                                     {"alternatives", optional_argument, 0, 1012}, {0, 0, 0, 0}};
+                                     {"alternatives", optional_argument, 0, 1012}, {"diplotypes", optional_argument, 0, 1013}, {"diploCandidates", required_argument, 0, 1014},
+                                     {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
   if (const char *d = getenv("T1K_DEVICE")) p.device = atoi(d);
@@ -97,6 +100,22 @@ int t1k_genotyper_main(int argc, char **argv) {
         const long n = v ? strtol(v, &end, 10) : 5;
         if (v && (end == v || *end || n < 1 || n > 1000)) { fprintf(stderr, "genotyper: --alternatives takes an integer from 1 to 1000\n%s", kUsage); return EXIT_FAILURE; }
         p.alternatives = (int32_t)n;
+        break;
+      }
+      case 1013: {  // "--diplotypes", "--diplotypes=INT" or "--diplotypes INT", as --alternatives
+        const char *v = optarg;
+        if (!v && optind < argc && argv[optind][0] != '-') v = argv[optind++];
+        char *end = nullptr;
+        const long n = v ? strtol(v, &end, 10) : 10;
+        if (v && (end == v || *end || n < 1 || n > 1000)) { fprintf(stderr, "genotyper: --diplotypes takes an integer from 1 to 1000\n%s", kUsage); return EXIT_FAILURE; }
+        p.diplotypes = (int32_t)n;
+        break;
+      }
+      case 1014: {
+        char *end = nullptr;
+        const long n = strtol(optarg, &end, 10);
+        if (end == optarg || *end || n < 2 || n > 2048) { fprintf(stderr, "genotyper: --diploCandidates takes an integer from 2 to 2048\n%s", kUsage); return EXIT_FAILURE; }
+        p.diplo_candidates = (int32_t)n;
         break;
       }
       default: fprintf(stderr, "%s", kUsage); return EXIT_FAILURE;

@@ -20,6 +20,8 @@ void t1k_job_params_default(t1k_job_params *p) {
   p->output_read_assignment = 0;
   p->batch_fragments = 0;
   p->alternatives = 0;
+  p->diplotypes = 0;
+  p->diplo_candidates = 512;
 }
 
 int t1k_job_create(const t1k_job_params *p, const char *refFasta, t1k_job **out) { return jobCreate(p, refFasta, nullptr, out); }

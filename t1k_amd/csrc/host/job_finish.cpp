@@ -25,6 +25,31 @@ static int jobAlternatives(t1k_job *job) {
   return T1K_OK;
 }
 
+// --diplotypes: the co-occurrence matrix of t1k_diplo_batch over the job's read groups, restated over the candidates of every
+// gene; ranked and formatted by the genotyper
+static int jobDiplotypes(t1k_job *job) {
+  const double t0 = nowMs();
+  const Genotyper &gt = job->gt;
+  Genotyper::DiploInput in;
+  gt.diplotypeInput(job->prm.diplo_candidates, in);
+  const double t1 = nowMs();
+  const uint32_t nGenes = (uint32_t)job->ref.geneName.size();
+  uint64_t cells = 0;
+  for (uint32_t x = 0; x < nGenes; ++x) { const uint64_t n = in.candPtr[x + 1] - in.candPtr[x]; cells += n * n; }
+  std::vector<uint64_t, NoInitAlloc<uint64_t>> matrix(cells);
+  const uint64_t G = in.q.size();
+  double kernelMs = 0;
+  const int rc = t1k_diplo_batch(job->ctx, G, in.groupPtr.data(), in.ent.data(), in.q.data(), nGenes, in.candPtr.data(), matrix.data(), &kernelMs);
+  if (rc != T1K_OK) return jobFail(job, rc, t1k_last_error(job->ctx));
+  const double t2 = nowMs();
+  job->diploText = gt.diplotypeText(in, matrix.data(), job->prm.diplotypes);
+  if (getenv("T1K_DEBUG_PHASES"))
+    fprintf(stderr, "[t1k job] diplotypes: %llu groups, %llu entries, %llu candidates, %llu cells, %llu pieces, kernel %.3f ms, total %.1f ms (classes and candidates %.1f ms, matrix %.1f ms, ranking %.1f ms)\n",
+            (unsigned long long)G, (unsigned long long)in.ent.size(), (unsigned long long)in.candAllele.size(), (unsigned long long)cells,
+            (unsigned long long)t1k_diplo_pieces(G, in.groupPtr.data()), kernelMs, nowMs() - t0, t1 - t0, t2 - t1, nowMs() - t2);
+  return T1K_OK;
+}
+
 extern "C" {
 
 int t1k_job_finish(t1k_job *job) {
@@ -102,6 +127,12 @@ int t1k_job_finish(t1k_job *job) {
   if (job->prm.alternatives > 0 && job->rank == 0) {  // the rank that writes _genotype.tsv, from the merged groups it holds: no exchange
     if (job->prm.alternatives > 1000) return jobFail(job, T1K_ERR_ARG, "alternatives: 1 .. 1000 per called allele");
     if ((rc = jobAlternatives(job)) != T1K_OK) return rc;
+  }
+  job->diploText.clear();
+  if (job->prm.diplotypes > 0 && job->rank == 0) {  // as above: the merged groups of the writing rank, no exchange
+    if (job->prm.diplotypes > 1000) return jobFail(job, T1K_ERR_ARG, "diplotypes: 1 .. 1000 pairs per gene");
+    if (job->prm.diplo_candidates < 2 || job->prm.diplo_candidates > 2048) return jobFail(job, T1K_ERR_ARG, "diplo_candidates: 2 .. 2048 per gene");
+    if ((rc = jobDiplotypes(job)) != T1K_OK) return rc;
   }
   job->msHost += (t3 - t2) + (t5 - t4); job->msEm = t4 - t3;
   job->stats.ms_total = job->msLoad + job->msDevice + job->msCoalesce + job->msHost + job->msEm;
@@ -304,6 +335,16 @@ int t1k_job_alternatives_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *n
   if (!job || !job->ran) return jobFail(job, T1K_ERR_STATE, "the job has not run");
   if (job->prm.alternatives <= 0 || job->rank != 0) return jobFail(job, T1K_ERR_STATE, "the job keeps no alternatives table");
   const std::string &s = job->altText;
+  if (needed) *needed = s.size();
+  if (buf && cap > s.size()) { memcpy(buf, s.data(), s.size()); buf[s.size()] = 0; }
+  else if (buf) return T1K_ERR_ARG;
+  return T1K_OK;
+}
+
+int t1k_job_diplotypes_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed) {
+  if (!job || !job->ran) return jobFail(job, T1K_ERR_STATE, "the job has not run");
+  if (job->prm.diplotypes <= 0 || job->rank != 0) return jobFail(job, T1K_ERR_STATE, "the job keeps no diplotypes table");
+  const std::string &s = job->diploText;
   if (needed) *needed = s.size();
   if (buf && cap > s.size()) { memcpy(buf, s.data(), s.size()); buf[s.size()] = 0; }
   else if (buf) return T1K_ERR_ARG;

@@ -59,6 +59,7 @@ struct t1k_job {
   std::string abundanceFile;
   std::string assignText;           // --outputReadAssignment rows
   std::string altText;              // --alternatives: the table (on the rank that writes _genotype.tsv)
+  std::string diploText;            // --diplotypes: the table (on the same rank)
   t1k_stats stats{};
   uint64_t distinctReadEnds = 0, readEnds = 0;
   double msLoad = 0, msDevice = 0, msHost = 0, msEm = 0, msCoalesce = 0, msWrite = 0;

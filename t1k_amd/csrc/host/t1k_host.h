@@ -210,6 +210,22 @@ struct Genotyper {
   void alternativesInput(std::vector<uint32_t, NoInitAlloc<uint32_t>> &ent, std::vector<uint64_t> &q, std::vector<uint32_t> &alleleGene, std::vector<uint32_t> &slotOf,
                          std::vector<int> &called) const;
   std::string alternativesText(const uint64_t *tables, const std::vector<int> &called, int top) const;
+  // --diplotypes (no counterpart in the reference).  What t1k_diplo_batch takes, from this job's read groups and calls: the
+  // alleles of a gene that lie in exactly the same groups of weight > 0 are one class, the first `maxCand` classes of a gene by weight
+  // (the called alleles' classes always among them) are its candidates, and the groups are restated over candidate ids (a class is one
+  // id: booked once per group).  diplotypeText: the text of <prefix>_diplotypes.tsv from the matrix, `top` pairs per gene.
+  struct DiploInput {
+    std::vector<uint64_t> groupPtr{0}, q;         // the groups of weight > 0 that hold a candidate
+    std::vector<uint32_t> ent;                    // candidate ids, ascending inside a group
+    std::vector<uint32_t> candPtr;                // [genes + 1]
+    std::vector<int> candAllele;                  // per candidate: the allele that names its class
+    std::vector<uint32_t> candEquiv;              // per candidate: the other alleles of its class
+    std::vector<uint32_t> nClass;                 // per gene: classes of weight > 0
+    std::vector<uint64_t> geneWeight;             // per gene: W, the weight of the groups that hold any of its alleles
+    std::vector<int> calledCand;                  // [2 * genes]: the candidate of slot k's class, -1 for an empty slot
+  };
+  void diplotypeInput(int maxCand, DiploInput &in) const;
+  std::string diplotypeText(const DiploInput &in, const uint64_t *matrix, int top) const;
 };
 
 // host/variants.cpp: novel-variant calling of the analyzer stage (VariantCaller.hpp), host code over the fragments' assignment lists and

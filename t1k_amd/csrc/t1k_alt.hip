@@ -98,33 +98,6 @@ __global__ __launch_bounds__(64 * kAltWaves) void k_alt_groups(AltArgs P) {
   }
 }
 
-// fn(begin, end) over contiguous pieces of [0, n) on the host cores; the first non-empty message wins
-template <class F>
-std::string altParallelCheck(uint64_t n, F fn) {
-  unsigned T = std::thread::hardware_concurrency();
-  if (T > 16) T = 16;
-  if (T < 2 || n < (1ull << 16)) return fn((uint64_t)0, n);
-  std::vector<std::string> msg(T);
-  std::vector<std::thread> th;
-  const uint64_t per = (n + T - 1) / T;
-  for (unsigned t = 0; t < T; ++t) th.emplace_back([&, t] { msg[t] = fn(std::min(n, t * per), std::min(n, (t + 1) * per)); });
-  for (auto &x : th) x.join();
-  for (auto &m : msg) if (!m.empty()) return m;
-  return std::string();
-}
-// pieces: cut at group boundaries; a group longer than a piece is a piece of its own.  -> the group index where each piece begins, then nGroups
-std::vector<uint64_t> altCut(uint64_t nGroups, const uint64_t *groupPtr) {
-  uint64_t pieceEntries = kAltPieceEntries;
-  if (const char *e = getenv("T1K_ALT_PIECE")) { const long long v = atoll(e); if (v > 0) pieceEntries = (uint64_t)v; }
-  std::vector<uint64_t> cut{0};
-  for (uint64_t g = 0; g < nGroups;) {
-    uint64_t h = g + 1;
-    while (h < nGroups && groupPtr[h + 1] - groupPtr[g] <= pieceEntries) ++h;
-    cut.push_back(h);
-    g = h;
-  }
-  return cut;
-}
 }  // namespace
 
 extern "C" {
@@ -151,14 +124,14 @@ int t1k_alt_batch(t1k_ctx *ctx, uint64_t nGroups, const uint64_t *groupPtr, cons
   if (nGroups >= (1ull << 32)) return t1k_fail(ctx, T1K_ERR_CAPACITY, "t1k_alt_batch: 2^32 read groups or more");
   if (nGroups) {
     if (groupPtr[0] != 0) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_alt_batch: groupPtr does not start at 0");
-    std::string bad = altParallelCheck(nGroups, [&](uint64_t g0, uint64_t g1) {
+    std::string bad = t1k_parallel_check(nGroups, [&](uint64_t g0, uint64_t g1) {
       for (uint64_t g = g0; g < g1; ++g)
         if (groupPtr[g + 1] < groupPtr[g]) return "groupPtr decreases at group " + std::to_string(g);
       return std::string();
     });
     if (!bad.empty()) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_alt_batch: " + bad);
     if (groupPtr[nGroups] && !entryAllele) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_alt_batch: bad arguments (NULL entryAllele)");
-    bad = altParallelCheck(nGroups, [&](uint64_t g0, uint64_t g1) {
+    bad = t1k_parallel_check(nGroups, [&](uint64_t g0, uint64_t g1) {
       for (uint64_t g = g0; g < g1; ++g)
         for (uint64_t p = groupPtr[g]; p < groupPtr[g + 1]; ++p) {
           if (entryAllele[p] >= nAlleles) return "entry " + std::to_string(p) + " names allele " + std::to_string(entryAllele[p]) + " of " + std::to_string(nAlleles);
@@ -178,7 +151,7 @@ int t1k_alt_batch(t1k_ctx *ctx, uint64_t nGroups, const uint64_t *groupPtr, cons
     if (nAlleles) memset(tables, 0, 32ull * nAlleles);
     return T1K_OK;
   }
-  const std::vector<uint64_t> cut = altCut(nGroups, groupPtr);
+  const std::vector<uint64_t> cut = t1k_group_pieces(nGroups, groupPtr, kAltPieceEntries, "T1K_ALT_PIECE");
   uint64_t maxEnt = 0, maxGroups = 0;
   for (size_t i = 0; i + 1 < cut.size(); ++i) {
     maxEnt = std::max(maxEnt, groupPtr[cut[i + 1]] - groupPtr[cut[i]]);
@@ -227,7 +200,7 @@ int t1k_alt_batch(t1k_ctx *ctx, uint64_t nGroups, const uint64_t *groupPtr, cons
 
 uint64_t t1k_alt_pieces(uint64_t nGroups, const uint64_t *groupPtr) {
   if (nGroups == 0 || !groupPtr) return 0;
-  return (uint64_t)altCut(nGroups, groupPtr).size() - 1;
+  return (uint64_t)t1k_group_pieces(nGroups, groupPtr, kAltPieceEntries, "T1K_ALT_PIECE").size() - 1;
 }
 
 }  // extern "C"

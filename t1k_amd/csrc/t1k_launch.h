@@ -1,7 +1,11 @@
 // t1k_amd/csrc/t1k_launch.h -- internal: kernel argument blocks and host launchers shared by the .hip files
 #pragma once
 #include <algorithm>
+#include <cstdlib>
 #include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
 #include "t1k_dev.h"
 
 #define T1K_USED_MASK_WORDS 10
@@ -171,6 +175,35 @@ inline unsigned t1k_grid(t1k_ctx *ctx, uint64_t items, uint32_t perBlock, uint32
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
   return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * blocksPerCu, (items + perBlock - 1) / perBlock));
 }
+// read groups as a CSR handed to a stateless call (t1k_alt_batch, t1k_diplo_batch).
+// t1k_parallel_check: fn(begin, end) over contiguous pieces of [0, n) on up to 16 host threads; the first non-empty message wins.
+template <class F>
+std::string t1k_parallel_check(uint64_t n, F fn) {
+  unsigned T = std::thread::hardware_concurrency();
+  if (T > 16) T = 16;
+  if (T < 2 || n < (1ull << 16)) return fn((uint64_t)0, n);
+  std::vector<std::string> msg(T);
+  std::vector<std::thread> th;
+  const uint64_t per = (n + T - 1) / T;
+  for (unsigned t = 0; t < T; ++t) th.emplace_back([&, t] { msg[t] = fn(std::min(n, t * per), std::min(n, (t + 1) * per)); });
+  for (auto &x : th) x.join();
+  for (auto &m : msg) if (!m.empty()) return m;
+  return std::string();
+}
+// t1k_group_pieces: the entries go up in pieces of pieceEntries (the environment variable `env`, in entries, overrides it) cut at group
+// boundaries; a group longer than a piece is a piece of its own.  -> the group index where each piece begins, then nGroups
+inline std::vector<uint64_t> t1k_group_pieces(uint64_t nGroups, const uint64_t *groupPtr, uint64_t pieceEntries, const char *env) {
+  if (const char *e = getenv(env)) { const long long v = atoll(e); if (v > 0) pieceEntries = (uint64_t)v; }
+  std::vector<uint64_t> cut{0};
+  for (uint64_t g = 0; g < nGroups;) {
+    uint64_t h = g + 1;
+    while (h < nGroups && groupPtr[h + 1] - groupPtr[g] <= pieceEntries) ++h;
+    cut.push_back(h);
+    g = h;
+  }
+  return cut;
+}
+
 inline int t1k_bits(unsigned long long v) {  // bits that hold every value <= v (at least 1)
   int b = 1;
   while (b < 64 && (v >> b)) ++b;
