@@ -262,6 +262,14 @@ def lib():
     L.t1k_rowset_groups_download_all.argtypes = [vp, vp, vp, vp]
     L.t1k_comm_abort.argtypes = [vp]
     L.t1k_ref_share.argtypes = [vp, vp]
+    L.t1k_reads_share.argtypes = [vp, vp]
+    L.t1k_xwin_create.argtypes = [vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]
+    L.t1k_xwin_destroy.argtypes = [vp]
+    L.t1k_xwin_destroy.restype = None
+    L.t1k_xwin_last_error.argtypes = [vp]
+    L.t1k_xwin_last_error.restype = C.c_char_p
+    L.t1k_xwin_link.argtypes = [vp, vp, C.c_uint32, u32p]
+    L.t1k_xwin_resolve.argtypes = [vp, vp, C.c_uint32]
     _lib = L
     return L
 
@@ -334,6 +342,11 @@ class Context:
         """this context reads the reference another context of the same GPU uploaded (t1k_ref_share); src must outlive it"""
         self.allele_len = src.allele_len
         self._check(lib().t1k_ref_share(self.h, src.h), "t1k_ref_share")
+
+    def reads_share(self, src):
+        """this context reads the read set (and the list table) another context of the same GPU uploaded (t1k_reads_share); src must outlive it"""
+        self.n_read_ends = src.n_read_ends
+        self._check(lib().t1k_reads_share(self.h, src.h), "t1k_reads_share")
 
     def reads_upload(self, seqs, weights=None):
         blob, offs = _concat(seqs)
@@ -1058,6 +1071,52 @@ class Readset:
             self.close()
         except Exception:
             pass
+
+
+class Xwin:
+    """The table of read-ends across the windows of a job (t1k_xwin; test use: a job makes its own).  A window is a context whose read set
+    t1k_reads_dedupe has collapsed; the contexts, or the read sets detached from them, must outlive the table's use."""
+
+    def __init__(self, owner, max_read_ends, max_windows):
+        h = C.c_void_p()
+        owner._check(lib().t1k_xwin_create(owner.h, max_read_ends, max_windows, C.byref(h)), "t1k_xwin_create")
+        self.h = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise T1kError("%s failed (%d): %s" % (what, rc, self.last_error()))
+
+    def last_error(self):
+        return lib().t1k_xwin_last_error(self.h).decode()
+
+    def close(self):
+        if self.h:
+            lib().t1k_xwin_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def link(self, reader, window, raw=False):
+        """the distinct read-ends of `reader` (window `window`) whose sequence an earlier window holds are marked, the others become known to
+        later windows (t1k_xwin_link): how many were marked.  raw=True: (status code, that count) without raising"""
+        n = C.c_uint32()
+        rc = lib().t1k_xwin_link(self.h, reader.h, window, C.byref(n))
+        if raw:
+            return rc, n.value
+        self._check(rc, "t1k_xwin_link")
+        return n.value
+
+    def resolve(self, ctx, window, raw=False):
+        """the marked read-ends of window `window` take the list-table entries of the windows that assigned their sequences (t1k_xwin_resolve);
+        raw=True returns the status code instead of raising"""
+        rc = lib().t1k_xwin_resolve(self.h, ctx.h, window)
+        if raw:
+            return rc
+        self._check(rc, "t1k_xwin_resolve")
 
 
 class Reads:

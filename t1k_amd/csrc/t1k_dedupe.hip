@@ -22,14 +22,24 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long h, unsign
   return h;
 }
 
-__global__ void k_dedupe_hash(T1kReadsDev R, unsigned long long *keys, uint32_t *idx) {
+// TEST-ONLY: T1K_TEST_DEDUPE_HASH_BITS / T1K_TEST_XWIN_HASH_BITS (read once per process) keep that many low bits of the stages' hashes (0: every
+// read-end has the same hash), so that read-ends collide and the word-by-word compares behind the hashes decide (tests/test_gpu_dedupe.py).
+// A collision costs t1k_reads_dedupe a merge wherever another read-end of the same hash lies between two copies in upload order -- with 0 bits it
+// merges neighbours only -- and costs the table across windows probes, nothing else.  Unset: all 64 bits.
+static unsigned long long testHashMask(const char *name) {
+  const char *e = getenv(name);
+  const int bits = e ? atoi(e) : 64;
+  return bits >= 0 && bits < 64 ? (1ull << bits) - 1 : ~0ull;
+}
+
+__global__ void k_dedupe_hash(T1kReadsDev R, unsigned long long *keys, uint32_t *idx, unsigned long long hashMask) {
   const uint32_t re = blockIdx.x * blockDim.x + threadIdx.x;
   if (re >= R.nReadEnds) return;
   const int S = R.S;
   const uint64_t *b = R.bases + (uint64_t)re * 2 * S, *m = R.nmask + (uint64_t)re * 2 * S;
   unsigned long long h = mix64(0x243F6A8885A308D3ull, R.len[re]);
   for (int w = 0; w < S; ++w) { h = mix64(h, b[w]); h = mix64(h, m[w] + 0x9E3779B97F4A7C15ull * (unsigned)(w + 1)); }
-  keys[re] = h;
+  keys[re] = h & hashMask;
   idx[re] = re;
 }
 
@@ -100,8 +110,9 @@ extern "C" int t1k_reads_dedupe(t1k_ctx *ctx, uint32_t *distinctOf, uint32_t *nD
   uint32_t *idx = (uint32_t *)(sp + 2 * n8), *idxSorted = idx + n4 / 4, *flag = idxSorted + n4 / 4, *runOf = flag + n4 / 4, *repr = runOf + n4 / 4,
            *dDistinctOf = repr + n4 / 4, *isRep = dDistinctOf + n4 / 4, *repPos = isRep + n4 / 4, *runRep = repPos + n4 / 4;
   static const bool hashOrder = [] { const char *e = getenv("T1K_DISTINCT_ORDER"); return e && !strcmp(e, "hash"); }();
+  static const unsigned long long hashMask = testHashMask("T1K_TEST_DEDUPE_HASH_BITS");
   const unsigned nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_dedupe_hash, dim3(nb), dim3(256), 0, ctx->stream, ctx->reads, keys, idx);
+  hipLaunchKernelGGL(k_dedupe_hash, dim3(nb), dim3(256), 0, ctx->stream, ctx->reads, keys, idx, hashMask);
   if ((rc = t1k_sort_pairs(ctx, keys, keysSorted, idx, idxSorted, n))) return rc;
   hipLaunchKernelGGL(k_dedupe_mark, dim3(nb), dim3(256), 0, ctx->stream, ctx->reads, keysSorted, idxSorted, flag);
   if ((rc = t1k_inclusive_sum(ctx, flag, runOf, n))) return rc;
@@ -167,12 +178,12 @@ struct t1k_xwin {
   std::string err;
 };
 
-__device__ __forceinline__ unsigned long long xwinHash(const T1kReadsDev &R, uint32_t re) {
+__device__ __forceinline__ unsigned long long xwinHash(const T1kReadsDev &R, uint32_t re, unsigned long long hashMask) {
   const int S = R.S, len = R.len[re], nw = (len + 31) >> 5;
   const uint64_t *b = R.bases + (uint64_t)re * 2 * S, *m = R.nmask + (uint64_t)re * 2 * S;
   unsigned long long h = mix64(0x13198A2E03707344ull, (unsigned long long)len);
   for (int w = 0; w < nw; ++w) { h = mix64(h, b[w]); h = mix64(h, m[w] + 0x9E3779B97F4A7C15ull * (unsigned)(w + 1)); }  // (words of the forward strand: S does not enter)
-  return h | 1ull;  // 0 = empty slot
+  return (h & hashMask) | 1ull;  // 0 = empty slot
 }
 __device__ __forceinline__ bool xwinSame(const T1kReadsDev &R, uint32_t re, const XSrc &s, uint32_t idx) {
   const int len = R.len[re];
@@ -186,10 +197,10 @@ __device__ __forceinline__ bool xwinSame(const T1kReadsDev &R, uint32_t re, cons
 }
 // ext[d] = 0, or 1 + (window << 32 | index) of the kept read-end with the same sequence; skip[d] = ext[d] != 0
 __global__ void k_xwin_lookup(T1kReadsDev R, const unsigned long long *keys, const unsigned long long *vals, uint64_t mask, const XSrc *src, unsigned long long *ext,
-                              uint8_t *skip, uint32_t *found) {
+                              uint8_t *skip, uint32_t *found, unsigned long long hashMask) {
   const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= R.nReadEnds) return;
-  const unsigned long long h = xwinHash(R, d);
+  const unsigned long long h = xwinHash(R, d, hashMask);
   unsigned long long hit = 0;
   uint64_t slot = (h >> 1) & mask;
   for (uint64_t probe = 0; probe <= mask; ++probe, slot = (slot + 1) & mask) {
@@ -203,10 +214,11 @@ __global__ void k_xwin_lookup(T1kReadsDev R, const unsigned long long *keys, con
   skip[d] = hit ? 1 : 0;
   if (hit) atomicAdd(found, 1u);
 }
-__global__ void k_xwin_insert(T1kReadsDev R, unsigned long long *keys, unsigned long long *vals, uint64_t mask, uint32_t window, const uint8_t *skip) {
+__global__ void k_xwin_insert(T1kReadsDev R, unsigned long long *keys, unsigned long long *vals, uint64_t mask, uint32_t window, const uint8_t *skip,
+                              unsigned long long hashMask) {
   const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= R.nReadEnds || skip[d]) return;
-  const unsigned long long h = xwinHash(R, d);
+  const unsigned long long h = xwinHash(R, d, hashMask);
   uint64_t slot = (h >> 1) & mask;
   for (uint64_t probe = 0; probe < 4096; ++probe, slot = (slot + 1) & mask) {  // (a table this full is not worth more probes: the read-end just stays unknown)
     if (atomicCAS(&keys[slot], 0ull, h) == 0ull) { vals[slot] = ((unsigned long long)window << 32) | d; return; }
@@ -269,10 +281,11 @@ extern "C" int t1k_xwin_link(t1k_xwin *x, t1k_ctx *reader, uint32_t window, uint
   X_HIP(hipMemcpyAsync((XSrc *)x->bSrc.p + window, &s, sizeof(XSrc), hipMemcpyHostToDevice, reader->stream));
   X_HIP(hipMemsetAsync(x->bCount.p, 0, 4, reader->stream));
   const unsigned nb = (n + 255) / 256;
+  static const unsigned long long hashMask = testHashMask("T1K_TEST_XWIN_HASH_BITS");
   hipLaunchKernelGGL(k_xwin_lookup, dim3(nb), dim3(256), 0, reader->stream, reader->reads, (const unsigned long long *)x->bKeys.p, (const unsigned long long *)x->bVals.p, x->cap - 1,
-                     (const XSrc *)x->bSrc.p, (unsigned long long *)P.ext.p, (uint8_t *)P.skip.p, (uint32_t *)x->bCount.p);
+                     (const XSrc *)x->bSrc.p, (unsigned long long *)P.ext.p, (uint8_t *)P.skip.p, (uint32_t *)x->bCount.p, hashMask);
   hipLaunchKernelGGL(k_xwin_insert, dim3(nb), dim3(256), 0, reader->stream, reader->reads, (unsigned long long *)x->bKeys.p, (unsigned long long *)x->bVals.p, x->cap - 1, window,
-                     (const uint8_t *)P.skip.p);
+                     (const uint8_t *)P.skip.p, hashMask);
   uint32_t found = 0;
   X_HIP(hipMemcpyAsync(&found, x->bCount.p, 4, hipMemcpyDeviceToHost, reader->stream));
   X_HIP(hipStreamSynchronize(reader->stream));
