@@ -23,7 +23,6 @@
 #define GA_BIG_MAX 2048
 #define GA_SCRATCH_INTS (6 * (GA_BIG_MAX + 4))  // row arrays of t1k_ga_general for sequences up to 2048 bases
 
-enum { ERR_HITCAP = 1, ERR_STAGECAP = 2, ERR_CANDCAP = 4, ERR_BIGGROUP = 8, ERR_OVLCAP = 16, ERR_SORTCAP = 32, ERR_SLOWCAP = 64, ERR_ROWCAP = 128, ERR_GROUPCAP = 256 };
 
 // ------------------------------------------------------------------------------------------------------------------
 // pack
@@ -505,7 +504,7 @@ __global__ __launch_bounds__(1024) void k_select_classes(SelectArgs P, int packe
     if (tid == 0) P.counters[T1K_CTR_SELECT_LEN + k] = tot;
   }
 #ifdef T1K_SELECT_ROUTES
-  if (tid == 0) P.counters[40] = n - listed;  // route 0: read-ends without a candidate
+  if (tid == 0) P.counters[T1K_WIN_SELECT_ROUTES] = n - listed;  // route 0: read-ends without a candidate
 #else
   (void)listed;
 #endif
@@ -522,10 +521,10 @@ __global__ __launch_bounds__(1024) void k_select_classes(SelectArgs P, int packe
 }
 
 // -DT1K_SELECT_ROUTES: read-ends and candidates per route of the selection (no candidate; 1 .. SELECT_CUT_LEN; .. SELECT_SMALL not cut / cut;
-// beyond not cut / cut), counted in counters[40 .. 52) and summed per process (a measurement build: thread 0 pays two atomics per read-end)
+// beyond not cut / cut), counted in the T1K_WIN_SELECT_ROUTES window and summed per process (a measurement build: thread 0 pays two atomics per read-end)
 #ifdef T1K_SELECT_ROUTES
 #define T1K_SELECT_ROUTE_COUNT() do { if (tid == 0) { const int r_ = n <= SELECT_CUT_LEN ? 1 : (n <= SELECT_SMALL ? 2 : 4) + (cutList ? 1 : 0); \
-  atomicAdd(&P.counters[40 + 2 * r_], 1ull); atomicAdd(&P.counters[41 + 2 * r_], (unsigned long long)n); } } while (0)
+  atomicAdd(&P.counters[T1K_WIN_SELECT_ROUTES + 2 * r_], 1ull); atomicAdd(&P.counters[T1K_WIN_SELECT_ROUTES + 1 + 2 * r_], (unsigned long long)n); } } while (0)
 #else
 #define T1K_SELECT_ROUTE_COUNT() do { } while (0)
 #endif
@@ -542,7 +541,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
   __shared__ __attribute__((aligned(8))) uint16_t sCnt[256 * (NT / 64)];  // (the cut's emit words live here too)
   const int tid = threadIdx.x;
   unsigned int nbTotal = 0;
-  unsigned long long emitTotal = 0;  // (thread 0, PK) emitted overlaps before the cut: counters[1] counts the kept ones
+  unsigned long long emitTotal = 0;  // (thread 0, PK) emitted overlaps before the cut (T1K_CTR_EMITTED): T1K_CTR_OVL counts the kept ones
   // a read-end's list in the tables: where it starts in the range's records, its length; PK: also in the read set's list table
   auto publish = [&](uint32_t re, uint32_t start, uint32_t count) {
     P.ovlStart[re] = start; P.ovlCount[re] = count;
@@ -588,7 +587,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
     if (np2 <= SELECT_LDS_CAP) key = sKey;
     else if (SELECT_LDS_CAP == SELECT_LARGE && np2 <= P.sortCap && np2 <= (1u << 15)) key = P.sortScratch + (uint64_t)blockIdx.x * P.sortCap * 6;
     else {
-      if (tid == 0) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); publishEmpty(re); }
+      if (tid == 0) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_SORTCAP); publishEmpty(re); }
       continue;
     }
     // key: matchCnt desc, similarity desc (== readSpan+seqSpan asc at equal matchCnt), readSpan desc, allele asc; payload: candidate
@@ -612,7 +611,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
                           (((fl & T1K_F_NEEDCLIP) && !(sim < 0.95)) ? SEL_F_KEEPCLIP : 0u);  // SeqSet.hpp:2170-2172
       const uint32_t slot = i;
       uint64_t kk;
-      if (!packSelectKey(W, m, d, rspan, c.allele & 0x7FFFFFFFu, i, kf, P.alleleBits, iBits, &kk)) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); kk = (uint64_t)i << 3; }
+      if (!packSelectKey(W, m, d, rspan, c.allele & 0x7FFFFFFFu, i, kf, P.alleleBits, iBits, &kk)) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_SORTCAP); kk = (uint64_t)i << 3; }
       key[slot] = kk;
     }
     __syncthreads();
@@ -768,7 +767,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
     };
     auto storePacked = [&](uint64_t at, const T1kOvl &o) {
       T1kOvlP p;
-      if (!t1k_ovl_pack(o, p)) atomicOr(&P.counters[2], 1024ull);
+      if (!t1k_ovl_pack(o, p)) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_PACK);
       P.store[at] = p;
     };
     uint32_t keep = tot;  // records of the list that are written
@@ -806,7 +805,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
         const int rspan = x.readEnd - x.readStart;
         const int d = rspan + 1 + x.seqEnd - x.seqStart + 1 + 2 * x.leftClip + 2 * x.rightClip;  // similarity desc == d asc at equal matchCnt
         uint64_t kk;
-        if (!packSortKey(TW, (int)x.matchCnt, d, rspan, P.cand[c0 + i].allele & 0x7FFFFFFFu, i, P.alleleBits, iBits, &kk)) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); kk = i; }
+        if (!packSortKey(TW, (int)x.matchCnt, d, rspan, P.cand[c0 + i].allele & 0x7FFFFFFFu, i, P.alleleBits, iBits, &kk)) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_SORTCAP); kk = i; }
         if ((int)x.matchCnt >= bestMatch - 10) ++nbLocal;  // (the near-best statistic counts the emitted overlaps, before the cut)
         key[selBitPos(emitBits, wordBase, i)] = kk;
       }
@@ -867,9 +866,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
       keep = (uint32_t)sLatch;
     }
     if (tid == 0) {
-      unsigned long long b = atomicAdd(&P.counters[1], (unsigned long long)keep);
+      unsigned long long b = atomicAdd(&P.counters[T1K_CTR_OVL], (unsigned long long)keep);
       emitTotal += tot;
-      if (b + keep > P.ovlCap) { atomicOr(&P.counters[2], (unsigned long long)ERR_OVLCAP); sBase = 0xFFFFFFFFu; publishEmpty(re); }
+      if (b + keep > P.ovlCap) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_OVLCAP); sBase = 0xFFFFFFFFu; publishEmpty(re); }
       else { sBase = (uint32_t)b; publish(re, (uint32_t)b, keep); }
     }
     __syncthreads();
@@ -896,7 +895,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELECT_LDS_C
     nbTotal += nbLocal;
     __syncthreads();
   }
-  if (PK && tid == 0 && emitTotal) atomicAdd(&P.counters[21], emitTotal);
+  if (PK && tid == 0 && emitTotal) atomicAdd(&P.counters[T1K_CTR_EMITTED], emitTotal);
   t1k_stat_add(P.counters, T1K_STAT_NEARBEST, nbTotal);
 }
 
@@ -1054,7 +1053,7 @@ __global__ __launch_bounds__(64) void k_fullalign_slow(SlowArgs P) {
     const int64_t goff = (int64_t)P.ref.alleleOff[o.allele];
     const int lp = o.readEnd - o.readStart + 1, lt = o.seqEnd - o.seqStart + 1;
     const int w = P.noCov ? 0 : (int)P.reads.weight[o.re];
-    if ((lp + 1) * (lt + 1) > P.maxCells || lt > GA_BIG_MAX) { atomicOr(&P.counters[2], (unsigned long long)ERR_SLOWCAP); continue; }
+    if ((lp + 1) * (lt + 1) > P.maxCells || lt > GA_BIG_MAX) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_SLOWCAP); continue; }
     T1kSeqView T{P.ref.bases, P.ref.nmask, goff + o.seqStart}, Pv{rb, rn, (int64_t)o.readStart};
     t1k_ga_general(T, lt, Pv, lp, rows, trace, nullptr);
     int n = t1k_ga_traceback(trace, lt, lp, ops);
@@ -1150,7 +1149,7 @@ __global__ __launch_bounds__(WG) void k_align_fill(SlowArgs P) {
   // statistics: DP cells filled, one atomic per wavefront
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) cells += __shfl_xor(cells, o, 64);
-  if ((threadIdx.x & 63) == 0 && cells) atomicAdd(&P.counters[24], cells);
+  if ((threadIdx.x & 63) == 0 && cells) atomicAdd(&P.counters[T1K_CTR_DP_CELLS], cells);
 }
 
 __global__ __launch_bounds__(WG) void k_align_apply_eq(SlowArgs P) {
@@ -1314,7 +1313,7 @@ __global__ __launch_bounds__(NT) T1K_TRUNC_ATTR void k_truncate(TruncArgs P) {
     __syncthreads();
     if (tid == 0) {  // (T1K_RE_HANDOUT read-ends per atomic on the hand-out word: round 6)
       constexpr uint32_t HO = SELECT_LDS_CAP == SELECT_SMALL ? T1K_TRUNC_SMALL_HANDOUT : T1K_TRUNC_LARGE_HANDOUT;
-      if (hoLeft == 0) { hoNext = (uint32_t)atomicAdd(&P.counters[SELECT_LDS_CAP == SELECT_SMALL ? 30 : 31], (unsigned long long)HO); hoLeft = HO; }
+      if (hoLeft == 0) { hoNext = (uint32_t)atomicAdd(&P.counters[SELECT_LDS_CAP == SELECT_SMALL ? T1K_CTR_TRUNC_HANDOUT : T1K_CTR_TRUNC_HANDOUT + 1], (unsigned long long)HO); hoLeft = HO; }
       sNextRe = hoNext++; --hoLeft;
     }
     __syncthreads();
@@ -1329,9 +1328,9 @@ __global__ __launch_bounds__(NT) T1K_TRUNC_ATTR void k_truncate(TruncArgs P) {
     uint64_t *wgScratch = P.sortScratch + (uint64_t)blockIdx.x * ((uint64_t)P.sortCap * 6);
     if (np2 <= SELECT_LDS_CAP) key = sKey;
     else if (np2 <= P.sortCap) key = wgScratch;
-    else { if (tid == 0) atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); continue; }
+    else { if (tid == 0) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_SORTCAP); continue; }
     T1kOvl *stage = (T1kOvl *)(wgScratch + P.sortCap * 2);
-    if (n > P.sortCap) { if (tid == 0) atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); continue; }
+    if (n > P.sortCap) { if (tid == 0) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_SORTCAP); continue; }
     int iBits = 1;
     while ((1u << iBits) < n) ++iBits;
     const uint64_t iMask = (1ull << iBits) - 1;
@@ -1342,7 +1341,7 @@ __global__ __launch_bounds__(NT) T1K_TRUNC_ATTR void k_truncate(TruncArgs P) {
         const T1kOvl o = P.ovl[o0 + i];
         int rspan = o.readEnd - o.readStart;
         int d = rspan + 1 + o.seqEnd - o.seqStart + 1 + 2 * o.leftClip + 2 * o.rightClip;  // similarity desc == d asc at equal matchCnt
-        if (!packSortKey(W, (int)o.matchCnt, d, rspan, o.allele, i, P.alleleBits, iBits, &kk)) { atomicOr(&P.counters[2], (unsigned long long)ERR_SORTCAP); kk = i; }
+        if (!packSortKey(W, (int)o.matchCnt, d, rspan, o.allele, i, P.alleleBits, iBits, &kk)) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_SORTCAP); kk = i; }
         stage[i] = o;
       }
       key[i] = kk;

@@ -231,7 +231,7 @@ __global__ void k_pack_overlaps(const T1kOvl *work, T1kOvlP *store, uint64_t nOv
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= nOvl) return;
   T1kOvlP p;
-  if (!t1k_ovl_pack(work[g], p)) atomicOr(&counters[2], 1024ull);
+  if (!t1k_ovl_pack(work[g], p)) atomicOr(&counters[T1K_CTR_ERR], (unsigned long long)ERR_PACK);
   store[g] = p;
 }
 static void t1k_launch_publish_lists(t1k_ctx *ctx, unsigned long long *listPtr, uint32_t *listCount, const T1kOvl *work, T1kOvlP *store, uint64_t nOvl,
@@ -642,7 +642,7 @@ int t1k_extract_batch(t1k_ctx *ctx, uint32_t endsPerFragment, uint8_t *good, uin
 // ------------------------------------------------------------------------------------------------------------------
 // AssignRead over the batch
 // ------------------------------------------------------------------------------------------------------------------
-// control counters + the striped statistics folded into their historical slots (7 dp, 11 fast, 12 general, 14 extend dp, 10 near-best)
+// h[T1K_CTR_WORDS]: the control words, with the striped statistics folded into theirs (t1k_stat_slot) and the group total
 extern "C++" int t1k_fetch_counters(t1k_ctx *ctx, unsigned long long *h) {
   std::vector<unsigned long long> &raw = ctx->hRaw;
   raw.resize(T1K_COUNTER_WORDS);
@@ -652,63 +652,70 @@ extern "C++" int t1k_fetch_counters(t1k_ctx *ctx, unsigned long long *h) {
   T1K_HIP(ctx, hipMemcpyAsync(ctx->countersPinned, ctx->bCounters.p, (size_t)T1K_COUNTER_WORDS * 8, hipMemcpyDeviceToHost, ctx->stream));
   T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));
   memcpy(raw.data(), ctx->countersPinned, (size_t)T1K_COUNTER_WORDS * 8);
-  memcpy(h, raw.data(), 64 * 8);
-  h[6] = 0;  // group records: sum of the arena's segment cursors
-  for (int s = 0; s < T1K_NSTRIPE; ++s) h[6] += raw[T1K_ARENA_BASE + ((size_t)T1K_AR_GROUPS * T1K_NSTRIPE + s) * T1K_STRIPE_WORDS];
-  static const int slot[8] = {7, 11, 12, 14, 10, 3, 4, 5};
+  memcpy(h, raw.data(), T1K_CTR_WORDS * 8);
+  h[T1K_CTR_GROUPS] = t1k_cursor_sum(raw, T1K_AR_GROUPS);
   for (int s = 0; s < T1K_STAT_STRIPES; ++s)
-    for (int k = 0; k < 8; ++k) h[slot[k]] += raw[64 + s * 8 + k];
-  if (getenv("T1K_SEED_PROFILE") && raw[48]) fprintf(stderr, "[t1k] seed phases (ticks, thread 0 of every workgroup): lookup %llu rule %llu setup+chunk-selection %llu [chunks visited %llu] slice %llu scan %llu walk %llu emit-scan %llu (record writes + reset are charged to slice)\n", raw[48], raw[49], raw[50], raw[51], raw[52], raw[53], raw[54], raw[55]);
+    for (int k = 0; k < T1K_STAT_KINDS; ++k) h[t1k_stat_slot(k)] += raw[T1K_STAT_BASE + s * T1K_STAT_KINDS + k];
+  const unsigned long long *sp = &raw[T1K_WIN_SEED_PROFILE];
+  if (getenv("T1K_SEED_PROFILE") && sp[0]) fprintf(stderr, "[t1k] seed phases (ticks, thread 0 of every workgroup): lookup %llu rule %llu setup+chunk-selection %llu [chunks visited %llu] slice %llu scan %llu walk %llu emit-scan %llu (record writes + reset are charged to slice)\n", sp[0], sp[1], sp[2], sp[3], sp[4], sp[5], sp[6], sp[7]);
   return 0;
 }
-static int fetchCounters(t1k_ctx *ctx, unsigned long long *h) { return t1k_fetch_counters(ctx, h); }
+
+// The working capacities of the batch arenas (t1k_ctx::cap, indexed by T1K_CAP_*), one rule each: where its demand stands after an
+// overflow (the fullest stripe of its arenas x T1K_NSTRIPE, or a control word), the error bit under which it grows, where it starts for a
+// range (read-ends x perRe x num / den, perRe = the reference's groups per read-end; perRe false: read-ends x num), its floor and the
+// floor under T1K_TEST_SMALL_ARENAS, its limit, its label in the T1K_DEBUG_PHASES line (nullptr: not shown).
+//   job lists (memo slots waiting for k_dp_dense): a read-end's memo has 2048 slots, so count * 2048 is the most there can be.  A list that
+//   overflows must not be survived by releasing the claim (another lane may already wait on that memo slot): the range runs again.
+//   hit lists of the multi-diagonal groups: 64 M entries (256 MB) serve every 2 x 150 bp range; a window with reads beyond the hit masks
+//   sends every group of THOSE read-ends through explicit lists (~1000 hits a group) and grows the arena to what the device counted.
+enum CapLimit { LIM_GROUP_CAP, LIM_CAND_CAP, LIM_OVL_CAP, LIM_JOBS, LIM_GENHITS };
+struct CapRule { int arenas[5]; int word; unsigned long long bit; bool perRe; uint32_t num, den; uint64_t floor, tinyFloor; CapLimit limit; const char *label; };
+static const CapRule kCapRules[T1K_NCAP] = {
+  /* T1K_CAP_GROUP  */ {{T1K_AR_GROUPS, -1}, -1, ERR_GROUPCAP, true, 1, 1, 4u << 20, 1024, LIM_GROUP_CAP, "groups"},
+  /* T1K_CAP_LIST   */ {{T1K_AR_SLOW, T1K_AR_RETRY, T1K_AR_FINISH, T1K_AR_EXTRETRY, -1}, -1, ERR_GROUPCAP, true, 7, 12, 1u << 20, 1024, LIM_GROUP_CAP, " lists"},
+  /* T1K_CAP_RARE   */ {{T1K_AR_GENERAL, T1K_AR_WAVE, T1K_AR_BIG, -1}, -1, ERR_GROUPCAP, true, 1, 24, 1u << 18, 1024, LIM_GROUP_CAP, " /"},
+  /* T1K_CAP_JOB    */ {{T1K_AR_JOBS, T1K_AR_EXTJOBS, -1}, -1, ERR_GROUPCAP, false, 512, 1, 1u << 20, 1u << 20, LIM_JOBS, " jobs"},
+  /* T1K_CAP_GENJOB */ {{T1K_AR_GENJOBS, -1}, -1, ERR_GROUPCAP, false, 128, 1, 1u << 20, 1u << 20, LIM_JOBS, " /"},
+  /* T1K_CAP_CAND   */ {{-1}, T1K_CTR_CAND, ERR_CANDCAP, true, 5, 12, 2u << 20, 128, LIM_CAND_CAP, " candidates"},
+  /* T1K_CAP_OVL    */ {{-1}, T1K_CTR_OVL, ERR_OVLCAP, true, 1, 3, 2u << 20, 128, LIM_OVL_CAP, " overlaps"},
+  /* T1K_CAP_GENHIT */ {{T1K_AR_GENHITS, -1}, -1, ERR_STAGECAP, false, 0, 1, 64u << 20, 64u << 20, LIM_GENHITS, nullptr},  // (candidate staging: only the hit arena grows)
+};
+// EXCEPTION, kept as code: the job lists are sized against max(jobLimit, what they already are) but grow against jobLimit * 2
+static uint64_t capLimit(const t1k_ctx *ctx, int i, uint32_t count, bool growing) {
+  const int64_t jobLimit = (int64_t)count * 2048 + (1 << 20);
+  switch (kCapRules[i].limit) {
+    case LIM_GROUP_CAP: return (uint64_t)ctx->prm.group_cap;  // (the group-id lists share the group arena's limit)
+    case LIM_CAND_CAP: return (uint64_t)ctx->prm.cand_cap;
+    case LIM_OVL_CAP: return (uint64_t)ctx->prm.ovl_cap;
+    case LIM_JOBS: return (uint64_t)(growing ? jobLimit * 2 : std::max<int64_t>(jobLimit, (int64_t)ctx->cap[i].w));
+    case LIM_GENHITS: break;
+  }
+  return 1024ull << 20;
+}
 
 // An arena overflowed.  The cursors keep counting past their capacity, so the last fetched counter block holds the demand of the
 // stages that ran: remember it, t1k_assign_range sizes its working capacities from it and runs the range again.
 static int capacityError(t1k_ctx *ctx, unsigned long long flags) {
   // (a full job list releases memo claims other lanes may already wait on; with the launches behind it no longer held back by a counter
   // fetch, one of them can meet a slot left pending: a consequence of the overflow, cured by the rerun with lists that fit)
-  if (flags & 256) flags &= ~512ull;
+  if (flags & ERR_GROUPCAP) flags &= ~(unsigned long long)ERR_MEMO;
   ctx->lastCapFlags = flags;
-  if (flags & 512) return t1k_fail(ctx, T1K_ERR_INTERNAL, "alignment memo entry left pending");
-  if (flags & 1024) return t1k_fail(ctx, T1K_ERR_INTERNAL, "an overlap record does not fit the packed form of the overlap store");
+  if (flags & ERR_MEMO) return t1k_fail(ctx, T1K_ERR_INTERNAL, "alignment memo entry left pending");
+  if (flags & ERR_PACK) return t1k_fail(ctx, T1K_ERR_INTERNAL, "an overlap record does not fit the packed form of the overlap store");
   if (ctx->covCommitted) {
     // k_fullalign has already added this range's ungapped alignments to the coverage arrays: running the range again (larger arenas,
     // or split in two) would count them twice.  The context's coverage is void; the caller must not retry on it.
     return t1k_fail(ctx, T1K_ERR_COMMITTED, "an alignment queue or sort buffer overflowed after part of the range's coverage was added (flags " + std::to_string(flags) +
                                                "): rerun with smaller ranges (T1K_BATCH) -- this context's coverage is no longer valid");
   }
-  if (ctx->hRaw.size() >= T1K_COUNTER_WORDS) {
-    auto maxSeg = [&](int arena) {
-      unsigned long long m = 0;
-      for (int st = 0; st < T1K_NSTRIPE; ++st) m = std::max(m, ctx->hRaw[T1K_ARENA_BASE + ((size_t)arena * T1K_NSTRIPE + st) * T1K_STRIPE_WORDS]);
-      return m;
-    };
-    unsigned long long lists = 0, rare = 0;
-    for (int ar : {T1K_AR_SLOW, T1K_AR_RETRY, T1K_AR_FINISH, T1K_AR_EXTRETRY}) lists = std::max(lists, maxSeg(ar));
-    for (int ar : {T1K_AR_GENERAL, T1K_AR_WAVE, T1K_AR_BIG}) rare = std::max(rare, maxSeg(ar));
-    ctx->needGroup = maxSeg(T1K_AR_GROUPS) * T1K_NSTRIPE;
-    ctx->needList = lists * T1K_NSTRIPE;
-    ctx->needRare = rare * T1K_NSTRIPE;
-    ctx->needJob = std::max(maxSeg(T1K_AR_JOBS), maxSeg(T1K_AR_EXTJOBS)) * T1K_NSTRIPE;
-    ctx->needGenJob = maxSeg(T1K_AR_GENJOBS) * T1K_NSTRIPE;
-    ctx->needGenHit = maxSeg(T1K_AR_GENHITS) * T1K_NSTRIPE;
-    ctx->needCand = ctx->hRaw[0];
-    ctx->needOvl = ctx->hRaw[1];
+  for (int i = 0; i < T1K_NCAP && ctx->hRaw.size() >= T1K_COUNTER_WORDS; ++i) {
+    const CapRule &r = kCapRules[i];
+    unsigned long long need = r.word >= 0 ? ctx->hRaw[r.word] : 0;
+    for (int k = 0; r.word < 0 && r.arenas[k] >= 0; ++k) need = std::max(need, t1k_cursor_max(ctx->hRaw, r.arenas[k]) * T1K_NSTRIPE);
+    ctx->cap[i].need = need;
   }
-  std::string m = "device arena overflow:";
-  if (flags & 1) m += " hit_cap";
-  if (flags & 2) m += " candidate staging";
-  if (flags & 4) m += " cand_cap";
-  if (flags & 8) m += " group too large";
-  if (flags & 16) m += " ovl_cap";
-  if (flags & 32) m += " sort capacity";
-  if (flags & 64) m += " slow-alignment queue";
-  if (flags & 128) m += " row_cap";
-  if (flags & 256) m += " group_cap";
-  if (flags & 512) return t1k_fail(ctx, T1K_ERR_INTERNAL, "alignment memo entry left pending");
-  if (flags & 1024) return t1k_fail(ctx, T1K_ERR_INTERNAL, "an overlap record does not fit the packed form of the overlap store");
-  return t1k_fail(ctx, T1K_ERR_CAPACITY, m);
+  return t1k_fail(ctx, T1K_ERR_CAPACITY, t1k_capacity_message(flags));
 }
 
 
@@ -752,8 +759,8 @@ extern "C++" int t1k_fullalign_phase(t1k_ctx *ctx, const T1kReadsDev &rd, T1kOvl
   f.fullLen = noCov ? -1 : ctx->covFullLen;
   t1k_launch_fullalign(ctx, f);
   T1K_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
-  if ((rc = fetchCounters(ctx, hc))) return rc;
-  if (hc[2]) return capacityError(ctx, hc[2]);
+  if ((rc = t1k_fetch_counters(ctx, hc))) return rc;
+  if (hc[T1K_CTR_ERR]) return capacityError(ctx, hc[T1K_CTR_ERR]);
   {
     const T1kArenaCounts ce = t1k_arena_counts(ctx, T1K_AR_EQ, qSegCap), cb = t1k_arena_counts(ctx, T1K_AR_BAND, qSegCap), cw = t1k_arena_counts(ctx, T1K_AR_WIDE, qSegCap);
     if (ce.overflow || cb.overflow || cw.overflow) {
@@ -770,7 +777,7 @@ extern "C++" int t1k_fullalign_phase(t1k_ctx *ctx, const T1kReadsDev &rd, T1kOvl
       ctx->queueBoost = std::min<uint32_t>(ctx->queueBoost * 4, 1u << 20);
       if (getenv("T1K_DEBUG_PHASES")) fprintf(stderr, "[t1k] a stripe of an alignment queue is full (%llu records in stripes of %u): %s, the range runs again with stripes x%u\n",
                                               (unsigned long long)nOvl, qSegCap, noCov ? "nothing was committed" : "the range's coverage was taken back", ctx->queueBoost);
-      return capacityError(ctx, 64);
+      return capacityError(ctx, ERR_SLOWCAP);
     }
     // equal / band queues: dense, then ordered by (read-end, strand, read window, allele-window hash)
     t1k_arena_compact(ctx, T1K_AR_EQ, f.eqStr, qSegCap, vDense, ce.maxSeg);
@@ -780,11 +787,11 @@ extern "C++" int t1k_fullalign_phase(t1k_ctx *ctx, const T1kReadsDev &rd, T1kOvl
     t1k_arena_compact64(ctx, T1K_AR_BAND, f.bandKeyStr, qSegCap, kDense, cb.maxSeg);
     if ((rc = t1k_sort_pairs(ctx, kDense, kSorted, vDense, qBand, (uint32_t)cb.total))) return rc;
     t1k_arena_compact(ctx, T1K_AR_WIDE, f.wideStr, qSegCap, qWide, cw.maxSeg);
-    hc[8] = ce.total; hc[15] = cb.total; hc[20] = cw.total;
+    hc[T1K_CTR_EQ_JOBS] = ce.total; hc[T1K_CTR_BAND_JOBS] = cb.total; hc[T1K_CTR_WIDE_JOBS] = cw.total;
   }
   // equal spans (register-band traced DP) and spans differing by 1..4 (wider register band): flags -> runs -> fill -> apply
   for (int kind = 0; kind < 2; ++kind) {
-    const uint32_t nJobs = (uint32_t)(kind == 0 ? hc[8] : hc[15]);
+    const uint32_t nJobs = (uint32_t)(kind == 0 ? hc[T1K_CTR_EQ_JOBS] : hc[T1K_CTR_BAND_JOBS]);
     if (!nJobs) continue;
     SlowArgs sl{};
     sl.ref = ctx->ref; sl.reads = rd; sl.relax = relaxFlag; sl.noCov = noCov; sl.ovl = ovl; sl.slowQueue = kind == 0 ? qEq : qBand; sl.nSlow = nJobs;
@@ -805,10 +812,10 @@ extern "C++" int t1k_fullalign_phase(t1k_ctx *ctx, const T1kReadsDev &rd, T1kOvl
     t1k_launch_align_fill_apply(ctx, sl, kind == 0);
     if (getenv("T1K_DEBUG_PHASES")) fprintf(stderr, "[t1k] %s alignments: %u jobs in %u runs of identical windows\n", kind == 0 ? "equal-span" : "band", nJobs, nRuns);
   }
-  if (hc[20]) {  // wide length difference: general DP with row arrays in HBM
+  if (hc[T1K_CTR_WIDE_JOBS]) {  // wide length difference: general DP with row arrays in HBM
     if ((rc = t1k_ensure(ctx, ctx->bSlowScratch, (size_t)slowBlocks * 64 * t1k_slow_per_thread(maxCells)))) return rc;
     SlowArgs sl{};
-    sl.ref = ctx->ref; sl.reads = rd; sl.relax = relaxFlag; sl.noCov = noCov; sl.ovl = ovl; sl.slowQueue = qWide; sl.nSlow = (uint32_t)hc[20];
+    sl.ref = ctx->ref; sl.reads = rd; sl.relax = relaxFlag; sl.noCov = noCov; sl.ovl = ovl; sl.slowQueue = qWide; sl.nSlow = (uint32_t)hc[T1K_CTR_WIDE_JOBS];
     sl.scratch = (uint8_t *)ctx->bSlowScratch.p; sl.perThread = t1k_slow_per_thread(maxCells); sl.maxCells = maxCells; sl.counters = counters;
     t1k_launch_fullalign_slow(ctx, sl, slowBlocks);
   }
@@ -829,17 +836,13 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count);
 static void routeCommit(t1k_ctx *ctx) {
   auto &rr = ctx->route;
   if (ctx->hRaw.size() < T1K_COUNTER_WORDS) return;
-  auto total = [&](int arena) {
-    uint64_t t = 0;
-    for (int s = 0; s < T1K_NSTRIPE; ++s) t += ctx->hRaw[T1K_ARENA_BASE + ((size_t)arena * T1K_NSTRIPE + s) * T1K_STRIPE_WORDS];
-    return t;
-  };
+  auto total = [&](int arena) { return (uint64_t)t1k_cursor_sum(ctx->hRaw, arena); };
   t1k_route_totals &k = rr.kept;
   ++k.ranges; ++(rr.passLong ? k.ranges_nw10 : k.ranges_nw5); k.ranges_xlong += rr.passXlong ? 1 : 0;
   k.groups += total(T1K_AR_GROUPS); k.slow += total(T1K_AR_SLOW); k.jobs += total(T1K_AR_JOBS); k.retry += total(T1K_AR_RETRY); k.finish += total(T1K_AR_FINISH);
   k.general += total(T1K_AR_GENERAL); k.wave += total(T1K_AR_WAVE); k.genjobs += total(T1K_AR_GENJOBS); k.big += total(T1K_AR_BIG);
   k.eq += total(T1K_AR_EQ); k.band += total(T1K_AR_BAND); k.wide += total(T1K_AR_WIDE); k.extjobs += total(T1K_AR_EXTJOBS); k.extretry += total(T1K_AR_EXTRETRY);
-  for (int s = 0; s < T1K_STAT_STRIPES; ++s) k.fast += ctx->hRaw[64 + s * 8 + T1K_STAT_FAST];
+  for (int s = 0; s < T1K_STAT_STRIPES; ++s) k.fast += ctx->hRaw[T1K_STAT_BASE + s * T1K_STAT_KINDS + T1K_STAT_FAST];
   rr.keptRecs.insert(rr.keptRecs.end(), rr.passRecs.begin(), rr.passRecs.end());
   rr.passRecs.clear();
 }
@@ -853,72 +856,55 @@ int t1k_assign_range(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   if (!ctx || !ctx->ref.bases) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_assign_range: no reference uploaded");
   if (first + count > ctx->reads.nReadEnds) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_assign_range: range outside the uploaded reads");
   T1K_HIP(ctx, hipSetDevice(ctx->device));
-  auto clampCap = [](uint64_t want, uint64_t floor, int64_t limit) { return std::min<uint64_t>((uint64_t)limit, std::max<uint64_t>(want, floor)); };
   // floors per read-end: what a 2x150 bp read-end needs against an HLA-sized reference (about 30 000 alleles: 1 900 groups, 1 000 of
   // them on the gap-walk list, 800 candidates, 610 overlaps), with room to spare; smaller references just leave part of it unused
   // (the group arena is striped: its fullest stripe decides, and it runs about 1.3 - 1.45 times the average -- 3 350 per read-end
   // keeps the first ranges of a job from running twice)
-  const uint64_t perRe = std::min<uint64_t>(3400, std::max<uint64_t>(256, (uint64_t)ctx->ref.nAlleles * 23 / 200));
-  ctx->wGroup = clampCap(std::max<uint64_t>(ctx->wGroup, (uint64_t)count * perRe), 4u << 20, ctx->prm.group_cap);
-  ctx->wCand = clampCap(std::max<uint64_t>(ctx->wCand, (uint64_t)count * perRe * 5 / 12), 2u << 20, ctx->prm.cand_cap);
-  ctx->wOvl = clampCap(std::max<uint64_t>(ctx->wOvl, (uint64_t)count * perRe / 3), 2u << 20, ctx->prm.ovl_cap);
-  ctx->wList = clampCap(std::max<uint64_t>(ctx->wList, (uint64_t)count * perRe * 7 / 12), 1u << 20, ctx->prm.group_cap);
-  ctx->wRare = clampCap(std::max<uint64_t>(ctx->wRare, (uint64_t)count * perRe / 24), 1u << 18, ctx->prm.group_cap);
-  // alignment job lists (memo slots waiting for k_dp_dense): a read-end's memo has 2048 slots, so count * 2048 is the most there can be.
-  // A list that overflows must not be survived by releasing the claim (another lane may already wait on that memo slot): the range
-  // runs again with a list that fits.
-  const int64_t jobLimit = (int64_t)count * 2048 + (1 << 20);
-  ctx->wJob = clampCap(std::max<uint64_t>(ctx->wJob, (uint64_t)count * 512), 1u << 20, std::max<int64_t>(jobLimit, (int64_t)ctx->wJob));
-  ctx->wGenJob = clampCap(std::max<uint64_t>(ctx->wGenJob, (uint64_t)count * 128), 1u << 20, std::max<int64_t>(jobLimit, (int64_t)ctx->wGenJob));
-  // hit lists of the multi-diagonal groups: 64 M entries (256 MB) serve every 2 x 150 bp range; a window with reads beyond the hit masks sends
-  // every group of THOSE read-ends through explicit lists (~1000 hits a group) and grows the arena to what the device counted -- round 3
-  // reserved 1 G entries (4 GB per pipeline) as soon as one such read was in the window
-  const int64_t genHitLimit = 1024ll << 20;
-  ctx->wGenHit = clampCap(ctx->wGenHit, 64u << 20, genHitLimit);
+  // (T1K_TEST_SMALL_ARENAS: the tests' way of making the first working capacities of a few hundred read-ends overflow, so that the
+  // driver has to grow them: 2 per read-end and the table's small floors.  The limits stay.)
+  static const bool tinyArenas = getenv("T1K_TEST_SMALL_ARENAS") != nullptr;
+  const uint64_t perRe = tinyArenas ? 2 : std::min<uint64_t>(3400, std::max<uint64_t>(256, (uint64_t)ctx->ref.nAlleles * 23 / 200));
+  for (int i = 0; i < T1K_NCAP; ++i) {
+    const CapRule &r = kCapRules[i];
+    const uint64_t start = (uint64_t)count * (r.perRe ? perRe : 1) * r.num / r.den;
+    ctx->cap[i].w = std::min(capLimit(ctx, i, count, false), std::max({ctx->cap[i].w, start, tinyArenas ? r.tinyFloor : r.floor}));
+  }
   for (int attempt = 0;; ++attempt) {
-    ctx->lastCapFlags = 0; ctx->needGroup = ctx->needCand = ctx->needOvl = ctx->needList = ctx->needRare = ctx->needJob = ctx->needGenJob = ctx->needGenHit = 0;
+    ctx->lastCapFlags = 0;
+    for (auto &c : ctx->cap) c.need = 0;
     const int rc = assignOnce(ctx, first, count);
     if (ctx->route.on && rc == T1K_OK && count) routeCommit(ctx);  // (opt-in: the pass that was kept, once)
     if (rc != T1K_ERR_CAPACITY || attempt >= 10) return rc;
+    const unsigned long long flags = ctx->lastCapFlags;
     bool grew = false;
-    auto grow = [&](uint64_t &w, uint64_t need, int64_t limit) {  // to the demand the device counted, with a quarter to spare
-      if (w >= (uint64_t)limit || need <= w) return;
-      w = std::min<uint64_t>((uint64_t)limit, need + need / 4);
-      grew = true;
-    };
-    if (ctx->lastCapFlags & 256) {
-      const uint64_t before = ctx->wGroup;
-      grow(ctx->wGroup, ctx->needGroup, ctx->prm.group_cap);
-      if (ctx->wGroup > before && !ctx->scaledOnce) {
-        // the seeding kernel is the first to overflow and the later arenas' demand goes with the number of groups: scale them once
-        // by the same factor instead of discovering each of them with a failed pass of its own
-        const double f = std::min(4.0, (double)ctx->wGroup / (double)before);
-        ctx->wList = std::min<uint64_t>((uint64_t)ctx->prm.group_cap, (uint64_t)(ctx->wList * f));
-        ctx->wCand = std::min<uint64_t>((uint64_t)ctx->prm.cand_cap, (uint64_t)(ctx->wCand * f));
-        ctx->wOvl = std::min<uint64_t>((uint64_t)ctx->prm.ovl_cap, (uint64_t)(ctx->wOvl * f));
+    for (int i = 0; i < T1K_NCAP; ++i) {
+      if (!(flags & kCapRules[i].bit)) continue;
+      auto &c = ctx->cap[i];
+      const uint64_t before = c.w, limit = capLimit(ctx, i, count, true);
+      if (c.w < limit && c.need > c.w) { c.w = std::min(limit, c.need + c.need / 4); grew = true; }  // to the demand the device counted, with a quarter to spare
+      if (i == T1K_CAP_GROUP && c.w > before && !ctx->scaledOnce) {
+        // EXCEPTION: the seeding kernel is the first to overflow and the later arenas' demand goes with the number of groups: scale them
+        // once (the first growth of the group arena, by at most 4) instead of discovering each of them with a failed pass of its own
+        const double f = std::min(4.0, (double)c.w / (double)before);
+        for (int j : {T1K_CAP_LIST, T1K_CAP_CAND, T1K_CAP_OVL}) ctx->cap[j].w = std::min(capLimit(ctx, j, count, true), (uint64_t)(ctx->cap[j].w * f));
         ctx->scaledOnce = true;
       }
-      grow(ctx->wList, ctx->needList, ctx->prm.group_cap);
-      grow(ctx->wRare, ctx->needRare, ctx->prm.group_cap);
-      grow(ctx->wJob, ctx->needJob, jobLimit * 2);
-      grow(ctx->wGenJob, ctx->needGenJob, jobLimit * 2);
     }
-    if (ctx->lastCapFlags & 2) grow(ctx->wGenHit, ctx->needGenHit, genHitLimit);  // (candidate staging of the multi-diagonal groups: only the hit arena grows)
-    if (ctx->lastCapFlags & 4) grow(ctx->wCand, ctx->needCand, ctx->prm.cand_cap);
-    if (ctx->lastCapFlags & 16) grow(ctx->wOvl, ctx->needOvl, ctx->prm.ovl_cap);
-    if (ctx->lastCapFlags & 64) grew = true;  // an alignment queue's stripe: t1k_fullalign_phase has raised queueBoost (and taken the range's coverage back)
-    if (!grew || (ctx->lastCapFlags & ~(256ull | 4ull | 16ull | 64ull | 2ull))) return rc;  // at the limits (or another arena): the caller splits the range
-    if (getenv("T1K_DEBUG_PHASES")) fprintf(stderr, "[t1k] range of %u read-ends again with capacities: groups %llu lists %llu / %llu jobs %llu / %llu candidates %llu overlaps %llu\n", count,
-                                            (unsigned long long)ctx->wGroup, (unsigned long long)ctx->wList, (unsigned long long)ctx->wRare, (unsigned long long)ctx->wJob, (unsigned long long)ctx->wGenJob,
-                                            (unsigned long long)ctx->wCand, (unsigned long long)ctx->wOvl);
+    if (flags & ERR_SLOWCAP) grew = true;  // an alignment queue's stripe: t1k_fullalign_phase has raised queueBoost (and taken the range's coverage back)
+    if (!grew || (flags & ~ERR_RETRYABLE)) return rc;  // at the limits (or another arena): the caller splits the range
+    if (getenv("T1K_DEBUG_PHASES")) {
+      std::string caps;
+      for (int i = 0; i < T1K_NCAP; ++i) if (kCapRules[i].label) caps += std::string(kCapRules[i].label) + " " + std::to_string(ctx->cap[i].w);
+      fprintf(stderr, "[t1k] range of %u read-ends again with capacities: %s\n", count, caps.c_str());
+    }
   }
 }
 
 // the statistics of a finished range from its last counter fetch; `emitted`: the overlaps the selection emitted (before lists are cut)
 static int finishRangeStats(t1k_ctx *ctx, uint32_t n, const unsigned long long *hc, unsigned long long emitted, double t0) {
   t1k_stats &st = ctx->stats;
-  st.read_ends = n; st.lookups = hc[3]; st.postings = hc[4]; st.hits = hc[5]; st.groups = hc[6]; st.candidates = hc[0]; st.extended = emitted;
-  st.dp_calls = hc[7] + hc[14]; st.near_best = hc[10]; st.dp_cells = hc[24];
+  st.read_ends = n; st.lookups = hc[T1K_CTR_LOOKUPS]; st.postings = hc[T1K_CTR_POSTINGS]; st.hits = hc[T1K_CTR_HITS]; st.groups = hc[T1K_CTR_GROUPS]; st.candidates = hc[T1K_CTR_CAND]; st.extended = emitted;
+  st.dp_calls = hc[T1K_CTR_DP] + hc[T1K_CTR_EXTEND_DP]; st.near_best = hc[T1K_CTR_NEARBEST]; st.dp_cells = hc[T1K_CTR_DP_CELLS];
   float ms[4] = {0, 0, 0, 0}, msSeed = 0;  // kernel durations from HIP events on the launch stream
   for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ms[i], ctx->ev[i], ctx->ev[i + 1]);
   (void)hipEventElapsedTime(&msSeed, ctx->ev[0], ctx->ev[8]);
@@ -941,9 +927,12 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   const int maxChunks = t1k_chain_max_chunks(ctx->ref.nAlleles), memoN = t1k_chain_memo_entries();
   const bool longReads = ctx->batchFastMaxLen > 160;  // (read-ends beyond T1K_MAX_READ_LEN are k_seed_long's: they do not widen the masks)
   const int recStride = t1k_chain_rec_stride(ctx->batchFastMaxLen);
-  const uint64_t groupCap = ctx->wGroup;
+  const auto &cap = ctx->cap;  // this pass's working capacities (t1k_assign_range)
+  const uint64_t wGroup = cap[T1K_CAP_GROUP].w, wList = cap[T1K_CAP_LIST].w, wRare = cap[T1K_CAP_RARE].w, wJob = cap[T1K_CAP_JOB].w, wGenJob = cap[T1K_CAP_GENJOB].w,
+                 wCand = cap[T1K_CAP_CAND].w, wOvl = cap[T1K_CAP_OVL].w, wGenHit = cap[T1K_CAP_GENHIT].w;
+  const uint64_t groupCap = wGroup;
   // (a window with reads beyond T1K_MAX_READ_LEN sends every group of those read-ends through the explicit hit lists: up to ~1000 hits a group)
-  const uint32_t jobCap = (uint32_t)ctx->wJob, genCandCap = 16u << 20, genHitCap = (uint32_t)std::min<uint64_t>(ctx->wGenHit ? ctx->wGenHit : (64u << 20), 1024u << 20), genJobCap = (uint32_t)ctx->wGenJob;
+  const uint32_t jobCap = (uint32_t)wJob, genCandCap = 16u << 20, genHitCap = (uint32_t)std::min<uint64_t>(wGenHit ? wGenHit : (64u << 20), 1024u << 20), genJobCap = (uint32_t)wGenJob;
   const int bigBlocks = 32;
   if ((rc = t1k_ensure(ctx, ctx->bCounters, (size_t)T1K_COUNTER_WORDS * 8))) return rc;
   if ((rc = t1k_ensure(ctx, ctx->bWgGroups, groupCap * recStride * 4))) return rc;                        // batch group records
@@ -955,21 +944,21 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   // work lists: every list exists twice, as a striped arena the kernels append to and as the dense list its consumer reads
   const uint32_t groupSegCap = (uint32_t)std::min<uint64_t>(groupCap / T1K_NSTRIPE, 0xFFFFFFFFull / T1K_NSTRIPE);
   // group-id lists: the frequent kinds (gap walk, retry, finish; extension retry) and the rare ones (several diagonals, wave, big scratch)
-  const uint32_t listSegCap = (uint32_t)std::max<uint64_t>(ctx->wList / T1K_NSTRIPE, 1024u), rareSegCap = (uint32_t)std::max<uint64_t>(ctx->wRare / T1K_NSTRIPE, 1024u);
+  const uint32_t listSegCap = (uint32_t)std::max<uint64_t>(wList / T1K_NSTRIPE, 1024u), rareSegCap = (uint32_t)std::max<uint64_t>(wRare / T1K_NSTRIPE, 1024u);
   const uint32_t jobSegCap = jobCap / T1K_NSTRIPE, genCandSegCap = genCandCap / T1K_NSTRIPE;
   const size_t listWords = (size_t)listSegCap * T1K_NSTRIPE, rareWords = (size_t)rareSegCap * T1K_NSTRIPE;
   if ((rc = t1k_ensure(ctx, ctx->bLists, ((size_t)jobCap * 2 + listWords * 5 + rareWords * 6 + (size_t)genCandCap * 6 + genHitCap + (size_t)genJobCap * 2) * 4 + 64))) return rc;
-  if ((rc = t1k_ensure(ctx, ctx->bCand, (size_t)ctx->wCand * sizeof(T1kCand)))) return rc;
-  if ((rc = t1k_ensure(ctx, ctx->bExt, (size_t)ctx->wCand * sizeof(T1kExt)))) return rc;
+  if ((rc = t1k_ensure(ctx, ctx->bCand, (size_t)wCand * sizeof(T1kCand)))) return rc;
+  if ((rc = t1k_ensure(ctx, ctx->bExt, (size_t)wCand * sizeof(T1kExt)))) return rc;
   // this range's lists go to the end of the overlap store: the current chunk if the working overlap capacity still fits, else the next one
-  const uint64_t chunkEntries = std::max<uint64_t>(ctx->wOvl, (uint64_t)std::max(1, ctx->prm.store_chunk_mb) * ((1ull << 20) / sizeof(T1kOvlP)));
+  const uint64_t chunkEntries = std::max<uint64_t>(wOvl, (uint64_t)std::max(1, ctx->prm.store_chunk_mb) * ((1ull << 20) / sizeof(T1kOvlP)));
   {
     const int sl = ctx->storeSlot;
     std::vector<T1kDevBuf> &chunks = ctx->storeChunks[sl];
     for (;;) {
       if (ctx->storeChunk[sl] >= chunks.size()) chunks.resize(ctx->storeChunk[sl] + 1);
       T1kDevBuf &ch = chunks[ctx->storeChunk[sl]];
-      if (ch.p && ctx->storeUsed[sl] + ctx->wOvl <= ch.bytes / sizeof(T1kOvlP)) break;   // fits behind what the chunk already holds
+      if (ch.p && ctx->storeUsed[sl] + wOvl <= ch.bytes / sizeof(T1kOvlP)) break;   // fits behind what the chunk already holds
       if (ch.p && ctx->storeUsed[sl] > 0) { ++ctx->storeChunk[sl]; ctx->storeUsed[sl] = 0; continue; }
       if (ch.p) { (void)t1k_dev_free(ch.p); ch.p = nullptr; ch.bytes = 0; }  // an empty chunk that is too small for this range
       const auto t0 = std::chrono::steady_clock::now();
@@ -983,7 +972,7 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   // Without --relaxIntronAlign and with the coverage deferred nothing reads the records between the selection and the cut: k_select
   // finishes the lists itself and writes them to the store in the packed form (no working records, no k_truncate, no k_pack_overlaps)
   const bool packedSelect = !ctx->prm.relax_intron_align && ctx->covMode == 1;
-  if (!packedSelect && (rc = t1k_ensure(ctx, ctx->bOvlWork, (size_t)ctx->wOvl * sizeof(T1kOvl)))) return rc;
+  if (!packedSelect && (rc = t1k_ensure(ctx, ctx->bOvlWork, (size_t)wOvl * sizeof(T1kOvl)))) return rc;
   ctx->ovlBase = packedSelect ? nullptr : (T1kOvl *)ctx->bOvlWork.p;
   ctx->ovlPacked = packedSelect;
   // (n + 1 entries each: the two counts are cleared one entry past the range.  Since round 1 the blocks were asked for n entries and cleared for n + 1 --
@@ -1004,7 +993,7 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   if (getenv("T1K_DEBUG_TRACE")) fprintf(stderr, "[t1k trace] assign_range first %llu count %u\n", (unsigned long long)first, n);
   memset(&ctx->stats, 0, sizeof(ctx->stats));
   if (n == 0) return T1K_OK;
-  unsigned long long hc[64];
+  unsigned long long hc[T1K_CTR_WORDS];
   double t0 = nowMs();
   ChainArgs a{};
   a.ref = ctx->ref; a.reads = rd;
@@ -1029,13 +1018,12 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   a.bigScratch = (uint32_t *)ctx->bWgBig.p;
   { static const int ns = getenv("T1K_NO_SIMPLE_CHAIN") ? 0 : 1; a.nearSimple = ns; }
   { static const int ep = getenv("T1K_NO_EARLY_PRUNE") ? 0 : getenv("T1K_WALK_IN_CLOSED") ? atoi(getenv("T1K_WALK_IN_CLOSED")) + 1 : 2; a.earlyPrune = ep; }  // 0: none, 1: the closed-form pass prunes with the gap-count bound, 2: ... and runs the gap walk's first pass
-  a.cand = (T1kCand *)ctx->bCand.p; a.candCap = ctx->wCand;
+  a.cand = (T1kCand *)ctx->bCand.p; a.candCap = wCand;
   a.candStart = (uint32_t *)ctx->bCandStart.p; a.candCount = (uint32_t *)ctx->bCandCount.p;
   a.counters = (unsigned long long *)ctx->bCounters.p;
   if ((rc = t1k_run_chain(ctx, a, nWg, bigBlocks, longReads, hc))) return rc;
-  double t1 = nowMs();
-  if (hc[2]) return capacityError(ctx, hc[2]);
-  ctx->nCand = hc[0];
+  if (hc[T1K_CTR_ERR]) return capacityError(ctx, hc[T1K_CTR_ERR]);
+  ctx->nCand = hc[T1K_CTR_CAND];
   ExtendArgs e{};
   e.ref = ctx->ref; e.reads = rd; e.k = a.k; e.sim = a.sim;
   e.cand = a.cand; e.ext = (T1kExt *)ctx->bExt.p; e.nCand = ctx->nCand; e.counters = a.counters;
@@ -1053,10 +1041,9 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
     t1k_launch_extend_retry_dev(ctx, e, a.retryList, T1K_AR_EXTRETRY, eR);
   }
   T1K_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-  double t2 = nowMs();
   SelectArgs s{};
   s.reads = rd; s.cand = a.cand; s.ext = e.ext; s.candStart = a.candStart; s.candCount = a.candCount;
-  s.ovl = ctx->ovlBase; s.ovlCap = ctx->wOvl;
+  s.ovl = ctx->ovlBase; s.ovlCap = wOvl;
   s.ovlStart = (uint32_t *)ctx->bOvlStart.p; s.ovlCount = (uint32_t *)ctx->bOvlCount.p;
   s.sortScratch = (uint64_t *)ctx->bSortScratch.p; s.sortCap = sortCap; s.counters = a.counters;
   s.alleleBits = 1; s.relax = relaxFlag; s.xl = ctx->batchMaxLen > T1K_MAX_READ_LEN ? 1 : 0;
@@ -1069,13 +1056,13 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
     // the lists are final, in the store and in the read set's table: one fetch ends the range (error word, kept and emitted records,
     // the extension's arena counts, the statistics)
     T1K_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    if ((rc = fetchCounters(ctx, hc))) return rc;
-    if (hc[2]) return capacityError(ctx, hc[2]);
+    if ((rc = t1k_fetch_counters(ctx, hc))) return rc;
+    if (hc[T1K_CTR_ERR]) return capacityError(ctx, hc[T1K_CTR_ERR]);
     t1k_arena_estimate_set(ctx, T1K_AR_EXTJOBS, t1k_arena_counts(ctx, T1K_AR_EXTJOBS, e.jobSegCap).total, n);
     t1k_arena_estimate_set(ctx, T1K_AR_EXTRETRY, t1k_arena_counts(ctx, T1K_AR_EXTRETRY, e.retrySegCap).total, n);
-    ctx->nOvl = hc[1];  // the records kept: the store advances by them
+    ctx->nOvl = hc[T1K_CTR_OVL];  // the records kept: the store advances by them
     ctx->storeUsed[ctx->storeSlot] += ctx->nOvl;
-    if (getenv("T1K_DEBUG_PHASES")) fprintf(stderr, "[t1k] packed selection: cand %llu emitted %llu kept %llu\n", hc[0], hc[21], hc[1]);
+    if (getenv("T1K_DEBUG_PHASES")) fprintf(stderr, "[t1k] packed selection: cand %llu emitted %llu kept %llu\n", hc[T1K_CTR_CAND], hc[T1K_CTR_EMITTED], hc[T1K_CTR_OVL]);
 #ifdef T1K_SELECT_ROUTES
     {
       static unsigned long long sum[12];
@@ -1084,17 +1071,16 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
         for (int r = 0; r < 6; ++r) fprintf(stderr, "[t1k] select routes: %-22s %12llu read-ends %14llu candidates\n", name[r], sum[2 * r], sum[2 * r + 1]);
       });
       (void)once;
-      for (int r = 0; r < 12; ++r) __atomic_fetch_add(&sum[r], hc[40 + r], __ATOMIC_RELAXED);
+      for (int r = 0; r < T1K_WIN_SELECT_ROUTES_LEN; ++r) __atomic_fetch_add(&sum[r], hc[T1K_WIN_SELECT_ROUTES + r], __ATOMIC_RELAXED);
     }
 #endif
-    return finishRangeStats(ctx, n, hc, hc[21], t0);
+    return finishRangeStats(ctx, n, hc, hc[T1K_CTR_EMITTED], t0);
   }
-  if ((rc = fetchCounters(ctx, hc))) return rc;
-  double t3 = nowMs();
-  if (hc[2]) return capacityError(ctx, hc[2]);
+  if ((rc = t1k_fetch_counters(ctx, hc))) return rc;
+  if (hc[T1K_CTR_ERR]) return capacityError(ctx, hc[T1K_CTR_ERR]);
   t1k_arena_estimate_set(ctx, T1K_AR_EXTJOBS, t1k_arena_counts(ctx, T1K_AR_EXTJOBS, e.jobSegCap).total, n);
   t1k_arena_estimate_set(ctx, T1K_AR_EXTRETRY, t1k_arena_counts(ctx, T1K_AR_EXTRETRY, e.retrySegCap).total, n);
-  ctx->nOvl = hc[1];
+  ctx->nOvl = hc[T1K_CTR_OVL];
   // Near-best full alignments (SeqSet.hpp:2188-2285).  Without --relaxIntronAlign they only feed the per-base coverage, so a context
   // whose coverage is deferred (t1k_ctx_set_coverage_mode) skips them here altogether: k_select has written the relaxed counts, and
   // t1k_coverage_selected later aligns the records of the alleles whose coverage is actually read.  With it they run for the relaxed
@@ -1105,7 +1091,7 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
     if ((rc = t1k_fullalign_phase(ctx, rd, s.ovl, ctx->nOvl, relaxFlag, deferCov ? 1 : 0, ctx->batchMaxLen, false, hc))) return rc;
   } else {
     T1K_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
-    hc[8] = hc[15] = hc[20] = 0;
+    hc[T1K_CTR_EQ_JOBS] = hc[T1K_CTR_BAND_JOBS] = hc[T1K_CTR_WIDE_JOBS] = 0;
   }
   hipEvent_t evSlow = ctx->ev[9];
   T1K_HIP(ctx, hipEventRecord(evSlow, ctx->stream));
@@ -1116,24 +1102,23 @@ static int assignOnce(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   T1K_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
   // the lists are final: publish them in the read set's table (absolute read-end index) and keep their records in the store
   t1k_launch_publish_lists(ctx, rd.listPtr + first, rd.listCount + first, ctx->ovlBase, ctx->storeBase, ctx->nOvl, s.ovlStart, s.ovlCount, n, a.counters, rd.skip);
-  if ((rc = fetchCounters(ctx, hc))) return rc;
-  double t4 = nowMs();
-  if (hc[2]) return capacityError(ctx, hc[2]);
+  if ((rc = t1k_fetch_counters(ctx, hc))) return rc;
+  if (hc[T1K_CTR_ERR]) return capacityError(ctx, hc[T1K_CTR_ERR]);
   ctx->storeUsed[ctx->storeSlot] += ctx->nOvl;
   if (getenv("T1K_DEBUG_PHASES")) {
     float a1 = 0, a2 = 0, a3 = 0;
     (void)hipEventElapsedTime(&a1, ctx->ev[3], ctx->ev[7]); (void)hipEventElapsedTime(&a2, ctx->ev[7], evSlow); (void)hipEventElapsedTime(&a3, evSlow, ctx->ev[4]);
     fprintf(stderr, "[t1k] fullalign %.2f ms, eq-DP (%llu jobs) + general-DP (%llu jobs) %.2f ms, truncate %.2f ms; cand %llu ovl %llu dp %llu; groups %llu (gap walk %llu) fast %llu general %llu big %llu; memo jobs %llu parked %llu wide-queue %llu\n",
-            a1, hc[8], hc[15], a2, a3, hc[0], hc[1], hc[7], hc[6], (unsigned long long)ctx->lastSlowGroups, hc[11], hc[12], hc[13], hc[16], hc[17], hc[20]);
+            a1, hc[T1K_CTR_EQ_JOBS], hc[T1K_CTR_BAND_JOBS], a2, a3, hc[T1K_CTR_CAND], hc[T1K_CTR_OVL], hc[T1K_CTR_DP], hc[T1K_CTR_GROUPS], (unsigned long long)ctx->lastSlowGroups, hc[T1K_CTR_FAST], hc[T1K_CTR_GENERAL], hc[T1K_CTR_BIG_GROUPS], hc[T1K_CTR_JOB_TOTAL], hc[T1K_CTR_RETRY_TOTAL], hc[T1K_CTR_WIDE_JOBS]);
 #ifdef T1K_NEAR_STATS
-    fprintf(stderr, "[t1k] multi-diagonal groups: far strays %llu, near count saturated %llu, other fallback %llu, masks ok but not a chain (<= 32 hits) %llu, (> 32 hits) %llu, chain (<= 96) %llu, chain (> 96) %llu\n", hc[40], hc[41], hc[42], hc[43], hc[47], hc[45], hc[46]);
+    const unsigned long long *nw = hc + T1K_WIN_NEAR_STATS;
+    fprintf(stderr, "[t1k] multi-diagonal groups: far strays %llu, near count saturated %llu, other fallback %llu, masks ok but not a chain (<= 32 hits) %llu, (> 32 hits) %llu, chain (<= 96) %llu, chain (> 96) %llu\n", nw[T1K_NEAR_FAR], nw[T1K_NEAR_SATURATED], nw[T1K_NEAR_FALLBACK], nw[T1K_NEAR_NOCHAIN_SMALL], nw[T1K_NEAR_NOCHAIN_LARGE], nw[T1K_NEAR_CHAIN_SMALL], nw[T1K_NEAR_CHAIN_LARGE]);
 #endif
 #ifdef T1K_WALK_STATS
-    fprintf(stderr, "[t1k] gap walk classes: exact without a DP %llu, pruned by the per-gap bound %llu, memo / DP %llu\n", hc[40], hc[41], hc[42]);
+    fprintf(stderr, "[t1k] gap walk classes: exact without a DP %llu, pruned by the per-gap bound %llu, memo / DP %llu\n", hc[T1K_WIN_WALK_STATS], hc[T1K_WIN_WALK_STATS + 1], hc[T1K_WIN_WALK_STATS + 2]);
 #endif
   }
-  (void)t1; (void)t2; (void)t3; (void)t4;
-  return finishRangeStats(ctx, n, hc, hc[1], t0);
+  return finishRangeStats(ctx, n, hc, hc[T1K_CTR_OVL], t0);
 }
 
 int t1k_overlaps_download(t1k_ctx *ctx, uint32_t *counts, t1k_overlap *out, uint64_t cap, uint64_t *total) {

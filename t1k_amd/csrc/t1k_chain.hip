@@ -300,7 +300,7 @@ __device__ inline int groupFastPath(const uint32_t *Mw, int diag, const ReadCtx 
     const int upper = 2 * (span - sumSmall - nBig);
 #ifdef T1K_WALK_STATS
     { const int cls = nBig == 0 ? 0 : ((double)upper / (double)(2 * span) < simThreshold) ? 1 : 2;
-      for (int c = 0; c < 3; ++c) { const unsigned long long mk = __ballot(cls == c); if (mk && (int)(threadIdx.x & 63) == __ffsll((long long)mk) - 1) atomicAdd(&sink.counters[40 + c], (unsigned long long)__popcll(mk)); } }
+      for (int c = 0; c < 3; ++c) { const unsigned long long mk = __ballot(cls == c); if (mk && (int)(threadIdx.x & 63) == __ffsll((long long)mk) - 1) atomicAdd(&sink.counters[T1K_WIN_WALK_STATS + c], (unsigned long long)__popcll(mk)); } }
 #endif
     if (nBig == 0) matchCnt = upper;  // exact
     else if ((double)upper / (double)(2 * span) < simThreshold) matchCnt = upper;  // certain to be dropped; no DP needed
@@ -482,7 +482,7 @@ __global__ __launch_bounds__(WG) void k_chain_fast(ChainArgs P, const uint32_t *
   constexpr bool DEFER = MODE != 2;
   constexpr bool LOOP = MODE != 0;
   unsigned int dpLocal = 0, fastLocal = 0;
-  if (nDev && P.counters[2]) return;  // an arena overflowed earlier in this submission: the range runs again, nothing of this pass is kept
+  if (nDev && P.counters[T1K_CTR_ERR]) return;  // an arena overflowed earlier in this submission: the range runs again, nothing of this pass is kept
   // list mode: 1-D grid over a dense list of record indices; all records: blockIdx.y = arena segment, blockIdx.x strides over the segment
   const uint32_t limit = list ? (nDev ? (uint32_t)*nDev : nItems)
                               : (uint32_t)min(*t1k_arena_cursor(P.counters, T1K_AR_GROUPS, blockIdx.y), (unsigned long long)P.groupSegCap);
@@ -549,7 +549,7 @@ __global__ __launch_bounds__(WG) void k_chain_fast(ChainArgs P, const uint32_t *
 
 // K3: one lane per registered alignment
 __global__ __launch_bounds__(WG) void k_dp_dense(ChainArgs P, const uint32_t *jobs, uint32_t nJobs, const unsigned long long *nDev) {
-  if (nDev) { if (P.counters[2]) return; nJobs = (uint32_t)*nDev; }
+  if (nDev) { if (P.counters[T1K_CTR_ERR]) return; nJobs = (uint32_t)*nDev; }
   unsigned int dpLocal = 0;
   for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nJobs; q += gridDim.x * blockDim.x) {
     const uint32_t tag = jobs[q];
@@ -615,7 +615,7 @@ __device__ __forceinline__ uint32_t evenBits32(uint64_t x) {  // bit 2j of x -> 
 template <int NW>
 __global__ __launch_bounds__(WG) void k_near_hits(ChainArgs P, uint32_t nItems, const unsigned long long *nDev) {
   constexpr int NQ = NW + 1;  // 64-bit words (32 positions each) of the per-position masks: one spare word for the k-mer's reach
-  if (nDev) { if (P.counters[2]) return; nItems = (uint32_t)*nDev; }
+  if (nDev) { if (P.counters[T1K_CTR_ERR]) return; nItems = (uint32_t)*nDev; }
   for (uint32_t qb = blockIdx.x * WG; qb < nItems; qb += gridDim.x * WG) {
   const uint32_t q = qb + threadIdx.x;
   bool toWave = false;
@@ -760,9 +760,9 @@ __global__ __launch_bounds__(WG) void k_near_hits(ChainArgs P, uint32_t nItems, 
     if (!ok) rec[6] = 0u;
 #ifdef T1K_NEAR_STATS
     {  // what the multi-diagonal groups are (profiles/r04_multidiag_classes.txt)
-      int cls = 42;
-      if (recFar(rv[2]) != 0) cls = 40; else if (nearCnt == 31) cls = 41; else if (ok) cls = rec[6] == 1u ? (n > 96 ? 46 : 45) : (n > 32 ? 47 : 43);
-      atomicAdd(&P.counters[cls], 1ull);
+      int cls = T1K_NEAR_FALLBACK;
+      if (recFar(rv[2]) != 0) cls = T1K_NEAR_FAR; else if (nearCnt == 31) cls = T1K_NEAR_SATURATED; else if (ok) cls = rec[6] == 1u ? (n > 96 ? T1K_NEAR_CHAIN_LARGE : T1K_NEAR_CHAIN_SMALL) : (n > 32 ? T1K_NEAR_NOCHAIN_LARGE : T1K_NEAR_NOCHAIN_SMALL);
+      atomicAdd(&P.counters[T1K_WIN_NEAR_STATS + cls], 1ull);
     }
 #endif
   }
@@ -772,7 +772,7 @@ __global__ __launch_bounds__(WG) void k_near_hits(ChainArgs P, uint32_t nItems, 
 
 template <int ROUNDS>
 __global__ __launch_bounds__(WG) void k_gather_general(ChainArgs P, uint32_t nItems, int skipDone, const unsigned long long *nDev) {
-  if (nDev) { if (P.counters[2]) return; nItems = (uint32_t)*nDev; }
+  if (nDev) { if (P.counters[T1K_CTR_ERR]) return; nItems = (uint32_t)*nDev; }
   const int lane = threadIdx.x & 63;
   const uint32_t wave = (blockIdx.x * WG + threadIdx.x) >> 6, nWaves = gridDim.x * (WG / 64);
   const int maxK = (int)P.maxK;
@@ -846,7 +846,7 @@ __global__ __launch_bounds__(WG) void k_gather_general(ChainArgs P, uint32_t nIt
 // to 3 * GENERAL_SMALL hits in the same LDS)
 __global__ __launch_bounds__(64) void k_chain_general(ChainArgs P, uint32_t nItems, int useSimple, const unsigned long long *nDev) {
   __shared__ uint32_t sArr[3 * GENERAL_SMALL * 64];
-  if (nDev) { if (P.counters[2]) return; nItems = (uint32_t)*nDev; }
+  if (nDev) { if (P.counters[T1K_CTR_ERR]) return; nItems = (uint32_t)*nDev; }
   unsigned int dpLocal = 0, genLocal = 0;
   for (uint32_t qb = blockIdx.x * 64; qb < nItems; qb += gridDim.x * 64) {  // (a lane's work arrays are its own: no barrier between the rounds)
   const uint32_t q = qb + threadIdx.x;
@@ -864,22 +864,22 @@ __global__ __launch_bounds__(64) void k_chain_general(ChainArgs P, uint32_t nIte
     const int pass = (rec[0] >> 31) ? 0 : 1;
     ReadCtx c = makeCtx(P, re, pass, allele);
     const int n = (int)nHits;
-    if (rec[3] == T1K_ARENA_FULL) atomicOr(&P.counters[2], (unsigned long long)ERR_STAGECAP);
+    if (rec[3] == T1K_ARENA_FULL) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_STAGECAP);
     const uint32_t *hh = P.genHits + (rec[3] == T1K_ARENA_FULL ? 0u : rec[3]);
     bool needScratch = false;
     uint32_t cbuf[2 * GENERAL_SMALL + 6];  // a candidate needs >= 3 hits
     CandOut out{cbuf, 0, 6, GENERAL_SMALL / 3 + 1};
     const GapSink sink{P.memo + (uint64_t)re * GAP_CACHE, P.genJobStr, P.counters, re * GAP_CACHE, P.genJobSegCap, T1K_AR_GENJOBS};
     LaneArr A{sArr + threadIdx.x}, B{sArr + GENERAL_SMALL * 64 + threadIdx.x}, C{sArr + 2 * GENERAL_SMALL * 64 + threadIdx.x};
-    if (simple) groupSimple(hh, n, c, P.k, P.hitLenRequired, A, out, &dpLocal, &P.counters[2], &needScratch, &sink, pass);
-    else groupGeneral(hh, n, c, P.k, P.radius, P.hitLenRequired, A, B, C, nullptr, 0, out, &dpLocal, &P.counters[2], &needScratch, &sink, pass);
+    if (simple) groupSimple(hh, n, c, P.k, P.hitLenRequired, A, out, &dpLocal, &P.counters[T1K_CTR_ERR], &needScratch, &sink, pass);
+    else groupGeneral(hh, n, c, P.k, P.radius, P.hitLenRequired, A, B, C, nullptr, 0, out, &dpLocal, &P.counters[T1K_CTR_ERR], &needScratch, &sink, pass);
     if (needScratch) { const uint32_t b = t1k_arena_append(P.counters, T1K_AR_BIG, P.rareSegCap); if (b != T1K_ARENA_FULL) P.bigStr[b] = gi; }
     else {
       ++genLocal;
       uint32_t base = 0;
       if (out.n) {
         base = t1k_arena_alloc(P.counters, T1K_AR_GENCAND, (uint32_t)out.n, P.genCandSegCap);
-        if (base == T1K_ARENA_FULL) { atomicOr(&P.counters[2], (unsigned long long)ERR_STAGECAP); out.n = 0; base = 0; }
+        if (base == T1K_ARENA_FULL) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_STAGECAP); out.n = 0; base = 0; }
         for (int i = 0; i < 6 * out.n; ++i) P.genCand[(uint64_t)base * 6 + i] = cbuf[i];
       }
       rec[3] = base;
@@ -898,7 +898,7 @@ __global__ __launch_bounds__(64) void k_chain_general(ChainArgs P, uint32_t nIte
 // these groups hold a few dozen hits, and with room for WAVE_CAP of them a workgroup's 48 KB left three wavefronts on a compute unit)
 __global__ __launch_bounds__(64) void k_chain_wave(ChainArgs P, uint32_t nItems, const unsigned long long *nDev, uint32_t cap, uint32_t above) {
   extern __shared__ uint32_t sW[];  // A | B | C, cap words each
-  if (nDev) { if (P.counters[2]) return; nItems = (uint32_t)*nDev; }
+  if (nDev) { if (P.counters[T1K_CTR_ERR]) return; nItems = (uint32_t)*nDev; }
   uint32_t *A = sW, *B = sW + cap, *C = sW + 2 * cap;
   const int lane = threadIdx.x;
   unsigned int dpLocal = 0, genLocal = 0;
@@ -911,7 +911,7 @@ __global__ __launch_bounds__(64) void k_chain_wave(ChainArgs P, uint32_t nItems,
     const int n = (int)rec[4];
     if ((uint32_t)n <= above || (uint32_t)n > cap) continue;  // (the other launch's; uniform over the wavefront)
     const bool lost = rec[3] == T1K_ARENA_FULL;
-    if (lost && lane == 0) atomicOr(&P.counters[2], (unsigned long long)ERR_STAGECAP);
+    if (lost && lane == 0) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_STAGECAP);
     const uint32_t *hh = P.genHits + (lost ? 0u : rec[3]);
     ReadCtx c = makeCtx(P, re, pass, allele);
     const int k = P.k;
@@ -969,19 +969,19 @@ __global__ __launch_bounds__(64) void k_chain_wave(ChainArgs P, uint32_t nItems,
         B[r] = x;
       }
       __syncthreads();
-      if (lane == 0) chainRun(c, k, P.hitLenRequired, A, B, C, s, m, nullptr, 0, out, &dpLocal, &P.counters[2], &needScratch, &sink, pass);
+      if (lane == 0) chainRun(c, k, P.hitLenRequired, A, B, C, s, m, nullptr, 0, out, &dpLocal, &P.counters[T1K_CTR_ERR], &needScratch, &sink, pass);
       __syncthreads();
       s = e;
     }
     if (lane == 0) {
-      if (out.overflow) atomicOr(&P.counters[2], (unsigned long long)ERR_BIGGROUP);
+      if (out.overflow) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_BIGGROUP);
       if (needScratch) { const uint32_t b = t1k_arena_append(P.counters, T1K_AR_BIG, P.rareSegCap); if (b != T1K_ARENA_FULL) P.bigStr[b] = gi; }
       else {
         ++genLocal;
         uint32_t base = 0;
         if (out.n) {
           base = t1k_arena_alloc(P.counters, T1K_AR_GENCAND, (uint32_t)out.n, P.genCandSegCap);
-          if (base == T1K_ARENA_FULL) { atomicOr(&P.counters[2], (unsigned long long)ERR_STAGECAP); out.n = 0; base = 0; }
+          if (base == T1K_ARENA_FULL) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_STAGECAP); out.n = 0; base = 0; }
           for (int i = 0; i < 6 * out.n; ++i) P.genCand[(uint64_t)base * 6 + i] = cbuf[i];
         }
         rec[3] = base;
@@ -995,7 +995,7 @@ __global__ __launch_bounds__(64) void k_chain_wave(ChainArgs P, uint32_t nItems,
 
 // K5c: add the memo's match counts to the candidates of the multi-diagonal groups
 __global__ __launch_bounds__(WG) void k_general_finish(ChainArgs P, uint32_t nItems, const unsigned long long *nDev) {
-  if (nDev) { if (P.counters[2]) return; nItems = (uint32_t)*nDev; }
+  if (nDev) { if (P.counters[T1K_CTR_ERR]) return; nItems = (uint32_t)*nDev; }
   for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nItems; q += gridDim.x * blockDim.x) {
   const uint32_t *rec = P.recs + (uint64_t)P.generalList[q] * P.recStride;
   if ((rec[2] & (REC_DONE | 0x40000000u)) != (REC_DONE | 0x40000000u)) continue;  // not chained yet (waits for k_chain_big)
@@ -1010,7 +1010,7 @@ __global__ __launch_bounds__(WG) void k_general_finish(ChainArgs P, uint32_t nIt
       const uint32_t slot = (g[3 + (i >> 1)] >> (16 * (i & 1))) & 0xFFFFu;
       const unsigned long long e = __hip_atomic_load(&memo[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const uint32_t v = GAP_VAL(e);
-      if (v == GAP_PENDING) atomicOr(&P.counters[2], (unsigned long long)ERR_MEMO);
+      if (v == GAP_PENDING) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_MEMO);
       sum += v;
     }
     g[2] += (2u * sum) << 20;
@@ -1024,7 +1024,7 @@ __global__ __launch_bounds__(WG) void k_general_finish(ChainArgs P, uint32_t nIt
 __global__ __launch_bounds__(64) void k_chain_big(ChainArgs P, uint32_t nItems, const unsigned long long *nDev) {
   __shared__ int sGa[GA_SCRATCH_INTS];
   if (threadIdx.x != 0) return;
-  if (nDev) { if (P.counters[2]) return; nItems = (uint32_t)*nDev; }
+  if (nDev) { if (P.counters[T1K_CTR_ERR]) return; nItems = (uint32_t)*nDev; }
   const uint32_t t = blockIdx.x, nT = gridDim.x;
   uint32_t *mine = P.bigScratch + (uint64_t)t * (4 * BIG_CAP);
   unsigned int dpLocal = 0;
@@ -1036,24 +1036,24 @@ __global__ __launch_bounds__(64) void k_chain_big(ChainArgs P, uint32_t nItems, 
     ReadCtx c = makeCtx(P, re, pass, allele);
     uint32_t *hh = mine + 3 * BIG_CAP;
     const int n = gatherHits(P, re, pass, allele, hh, BIG_CAP);
-    if (n > BIG_CAP) { atomicOr(&P.counters[2], (unsigned long long)ERR_BIGGROUP); rec[2] = REC_DONE; continue; }
+    if (n > BIG_CAP) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_BIGGROUP); rec[2] = REC_DONE; continue; }
     bool dummy = false;
     uint32_t cbuf[192];  // at most 32 candidates are kept per group
     CandOut o2{cbuf, 0, 6, 32};
     groupGeneral(hh, n, c, P.k, P.radius, P.hitLenRequired, mine, mine + BIG_CAP, mine + 2 * BIG_CAP, sGa, GA_BIG_MAX, o2, &dpLocal,
-                 &P.counters[2], &dummy);
-    if (o2.overflow) atomicOr(&P.counters[2], (unsigned long long)ERR_BIGGROUP);
+                 &P.counters[T1K_CTR_ERR], &dummy);
+    if (o2.overflow) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_BIGGROUP);
     uint32_t base = 0;
     if (o2.n) {
       base = t1k_arena_alloc(P.counters, T1K_AR_GENCAND, (uint32_t)o2.n, P.genCandSegCap);
-      if (base == T1K_ARENA_FULL) { atomicOr(&P.counters[2], (unsigned long long)ERR_STAGECAP); o2.n = 0; base = 0; }
+      if (base == T1K_ARENA_FULL) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_STAGECAP); o2.n = 0; base = 0; }
       for (int i = 0; i < 6 * o2.n; ++i) P.genCand[(uint64_t)base * 6 + i] = cbuf[i];
     }
     rec[3] = base;
     rec[2] = REC_DONE | 0x40000000u | (uint32_t)o2.n;
-    atomicAdd(&P.counters[13], 1ull);
+    atomicAdd(&P.counters[T1K_CTR_BIG_GROUPS], 1ull);
   }
-  if (dpLocal) atomicAdd(&P.counters[7], (unsigned long long)dpLocal);
+  if (dpLocal) atomicAdd(&P.counters[T1K_CTR_DP], (unsigned long long)dpLocal);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1096,7 +1096,7 @@ __device__ __forceinline__ uint32_t pendingMatchWord(const ChainArgs &P, uint32_
     const uint32_t slot = ((i >> 1 ? s1 : s0) >> (16 * (i & 1))) & 0xFFFFu;
     const unsigned long long e = __hip_atomic_load(&memo[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t v = GAP_VAL(e);
-    if (v == GAP_PENDING) atomicOr(&P.counters[2], (unsigned long long)ERR_MEMO);  // cannot happen: every registered job is run by k_dp_dense
+    if (v == GAP_PENDING) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_MEMO);  // cannot happen: every registered job is run by k_dp_dense
     sum += v;
   }
   return w2 + ((2u * sum) << 20);
@@ -1130,13 +1130,13 @@ __global__ __launch_bounds__(WG) T1K_COLLECT_ATTR void k_collect(ChainArgs P) {
   __shared__ uint32_t sKeepBits[KEEP_BITS / 32];
   const int tid = threadIdx.x;
   const uint32_t stride = P.recStride;
-  if (P.devDriven && P.counters[2]) return;  // an arena overflowed earlier in this submission: the range runs again
+  if (P.devDriven && P.counters[T1K_CTR_ERR]) return;  // an arena overflowed earlier in this submission: the range runs again
   __shared__ uint32_t sNextRe;  // read-ends handed out one at a time (device counter): their group counts differ by orders of magnitude
   uint32_t hoNext = 0, hoLeft = 0;
   for (;;) {
     __syncthreads();
     if (tid == 0) {  // (T1K_RE_HANDOUT read-ends per atomic on the hand-out word: round 6)
-      if (hoLeft == 0) { hoNext = (uint32_t)atomicAdd(&P.counters[27], (unsigned long long)T1K_COLLECT_HANDOUT); hoLeft = T1K_COLLECT_HANDOUT; }
+      if (hoLeft == 0) { hoNext = (uint32_t)atomicAdd(&P.counters[T1K_CTR_COLLECT_HANDOUT], (unsigned long long)T1K_COLLECT_HANDOUT); hoLeft = T1K_COLLECT_HANDOUT; }
       sNextRe = hoNext++; --hoLeft;
     }
     __syncthreads();
@@ -1246,8 +1246,8 @@ __global__ __launch_bounds__(WG) T1K_COLLECT_ATTR void k_collect(ChainArgs P) {
     uint32_t totWin;
     t1k_block_scan_exclusive(nCand[winPlus], warpSums, &totWin);
     if (tid == 0) {
-      unsigned long long b = totWin ? atomicAdd(&P.counters[0], (unsigned long long)totWin) : 0ull;
-      if (b + totWin > P.candCap) { atomicOr(&P.counters[2], (unsigned long long)ERR_CANDCAP); sBase = 0xFFFFFFFFu; P.candStart[re] = 0; P.candCount[re] = 0; }
+      unsigned long long b = totWin ? atomicAdd(&P.counters[T1K_CTR_CAND], (unsigned long long)totWin) : 0ull;
+      if (b + totWin > P.candCap) { atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_CANDCAP); sBase = 0xFFFFFFFFu; P.candStart[re] = 0; P.candCount[re] = 0; }
       else { sBase = (uint32_t)b; P.candStart[re] = (uint32_t)b; P.candCount[re] = totWin; }
     }
     __syncthreads();
@@ -1336,7 +1336,7 @@ __global__ __launch_bounds__(WG) void k_arena_compact(const V *src, uint32_t seg
     counters[T1K_TOTAL_BASE + arena] = (unsigned long long)prefix + cnt;
     bool over = false;
     for (uint32_t s = 0; s < T1K_NSTRIPE; ++s) over = over || cursors[s * T1K_STRIPE_WORDS] > (unsigned long long)segCap;
-    if (over && overflowFlag) atomicOr(&counters[2], overflowFlag);
+    if (over && overflowFlag) atomicOr(&counters[T1K_CTR_ERR], overflowFlag);
   }
   for (uint32_t i = blockIdx.x * WG + threadIdx.x; i < cnt; i += gridDim.x * WG) dst[prefix + i] = src[(uint64_t)seg * segCap + i];
 }
@@ -1344,7 +1344,7 @@ __global__ __launch_bounds__(WG) void k_arena_compact(const V *src, uint32_t seg
 T1kArenaCounts t1k_arena_counts(const t1k_ctx *ctx, int arena, uint32_t segCap) {
   T1kArenaCounts r{0, 0, false};
   for (int s = 0; s < T1K_NSTRIPE; ++s) {
-    unsigned long long c = ctx->hRaw[T1K_ARENA_BASE + ((size_t)arena * T1K_NSTRIPE + s) * T1K_STRIPE_WORDS];
+    unsigned long long c = t1k_cursor(ctx->hRaw, arena, s);
     if (c > segCap) { r.overflow = true; c = segCap; }
     r.total += c;
     r.maxSeg = std::max<uint32_t>(r.maxSeg, (uint32_t)c);
@@ -1539,7 +1539,7 @@ static int routeCollect(t1k_ctx *ctx, const ChainArgs &a, bool longReads, bool x
 // stripe raises ERR_GROUPCAP on the device; the kernels behind it work on the clamped lists (their results are thrown away: the caller
 // runs the range again with the capacities the cursors ask for, as before).  One counter fetch is left, at the end.
 // ------------------------------------------------------------------------------------------------------------------
-// runs K1..K6; on return counters[0] = number of candidates, counters[2] = error flags
+// runs K1..K6; on return hc[T1K_CTR_CAND] = number of candidates, hc[T1K_CTR_ERR] = error flags, hc[T1K_CTR_JOB_TOTAL ..] the lists' totals
 int t1k_run_chain(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBlocks, bool longReads, unsigned long long *hc) {
   ChainArgs a = aIn;
   a.devDriven = 1;
@@ -1612,14 +1612,14 @@ int t1k_run_chain(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBlocks, bo
   const T1kArenaCounts groups = t1k_arena_counts(ctx, T1K_AR_GROUPS, a.groupSegCap), slow = t1k_arena_counts(ctx, T1K_AR_SLOW, a.listSegCap), jobs = t1k_arena_counts(ctx, T1K_AR_JOBS, a.jobSegCap),
                        retry = t1k_arena_counts(ctx, T1K_AR_RETRY, a.listSegCap), fin = t1k_arena_counts(ctx, T1K_AR_FINISH, a.listSegCap), gen = t1k_arena_counts(ctx, T1K_AR_GENERAL, a.rareSegCap),
                        wv = t1k_arena_counts(ctx, T1K_AR_WAVE, a.rareSegCap), gj = t1k_arena_counts(ctx, T1K_AR_GENJOBS, a.genJobSegCap), big = t1k_arena_counts(ctx, T1K_AR_BIG, a.rareSegCap);
-  if (groups.overflow || slow.overflow || jobs.overflow || retry.overflow || gen.overflow || wv.overflow || gj.overflow || big.overflow) hc[2] |= ERR_GROUPCAP;
-  // (the finish list: word 22 is a statistic; the list itself is not read -- see above -- so its overflow is not an error)
+  if (groups.overflow || slow.overflow || jobs.overflow || retry.overflow || gen.overflow || wv.overflow || gj.overflow || big.overflow) hc[T1K_CTR_ERR] |= ERR_GROUPCAP;
+  // (the finish list: T1K_CTR_FINISH_TOTAL is a statistic; the list itself is not read -- see above -- so its overflow is not an error)
   // A full job list means memo claims were released while other lanes already waited on them: what ran behind it may have met a slot still
   // pending (ERR_MEMO).  That is a consequence of the overflow, not an internal error: the range runs again with lists that fit.
-  if (hc[2] & ERR_GROUPCAP) hc[2] &= ~(unsigned long long)ERR_MEMO;
+  if (hc[T1K_CTR_ERR] & ERR_GROUPCAP) hc[T1K_CTR_ERR] &= ~(unsigned long long)ERR_MEMO;
   ctx->lastSlowGroups = slow.total;
-  hc[16] = jobs.total; hc[17] = retry.total; hc[18] = gen.total; hc[19] = big.total; hc[22] = fin.total;
-  if (!hc[2]) {
+  hc[T1K_CTR_JOB_TOTAL] = jobs.total; hc[T1K_CTR_RETRY_TOTAL] = retry.total; hc[T1K_CTR_GENERAL_TOTAL] = gen.total; hc[T1K_CTR_BIG_TOTAL] = big.total; hc[T1K_CTR_FINISH_TOTAL] = fin.total;
+  if (!hc[T1K_CTR_ERR]) {
     const T1kArenaCounts *cs[] = {&groups, &slow, &jobs, &retry, &gen, &wv, &gj, &big};
     const int ar[] = {T1K_AR_GROUPS, T1K_AR_SLOW, T1K_AR_JOBS, T1K_AR_RETRY, T1K_AR_GENERAL, T1K_AR_WAVE, T1K_AR_GENJOBS, T1K_AR_BIG};
     for (int i = 0; i < 8; ++i) t1k_arena_estimate_set(ctx, ar[i], cs[i]->total, nRe);
@@ -1627,7 +1627,7 @@ int t1k_run_chain(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBlocks, bo
   }
   if (ctx->route.on) {  // (opt-in: nothing above depends on it)
     ctx->route.passRecs.clear();
-    if (!hc[2])
+    if (!hc[T1K_CTR_ERR])
       if (const int rc = routeCollect(ctx, a, longReads, xlong, gen.total, big.total)) return rc;
   }
   return 0;

@@ -13,8 +13,6 @@
 #define DIAG_EMPTY 0x7FFFFFFF    // diagonal of an accumulator no hit has reached
 #define GROUP_MAX_REFS 4         // two 32-bit words of 16-bit memo slots in a group record
 
-enum { ERR_HITCAP = 1, ERR_STAGECAP = 2, ERR_CANDCAP = 4, ERR_BIGGROUP = 8, ERR_OVLCAP = 16, ERR_SORTCAP = 32, ERR_SLOWCAP = 64, ERR_ROWCAP = 128, ERR_GROUPCAP = 256, ERR_MEMO = 512 };
-
 // record word 2 before chaining: reference diagonal (22 bits, biased; alleles are shorter than 2^20 bases) and the counts of hits off
 // it: FAR = beyond `radius` diagonals (bits 22..24, saturating at 7) and NEAR = within `radius` (bits 25..29, saturating at 31) -- the
 // chain asks "near > 0" and "far > 2" (several diagonals: the general path), k_near_hits asks for "far == 0" and the exact near count

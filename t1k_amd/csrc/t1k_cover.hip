@@ -162,7 +162,7 @@ int t1k_coverage_selected(t1k_ctx *ctx, t1k_readset *rs, const uint8_t *selected
   // the batch-relative read-end); every queue stripe can hold the whole batch, so nothing here can overflow and nothing is added twice
   uint64_t cap = 1u << 20;
   if (const char *ev = getenv("T1K_COVER_BATCH")) cap = (uint64_t)std::max(64, atoi(ev));
-  unsigned long long hc[64];
+  unsigned long long hc[T1K_CTR_WORDS];
   for (uint32_t i0 = 0; i0 < D;) {
     const uint32_t lim = (uint32_t)std::min<uint64_t>(D, (uint64_t)i0 + (1u << 20));
     uint32_t i1 = (uint32_t)(std::upper_bound(off.begin() + i0 + 1, off.begin() + lim + 1, off[i0] + cap) - off.begin()) - 1;

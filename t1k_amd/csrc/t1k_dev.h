@@ -14,6 +14,7 @@
 #include <type_traits>
 #include <vector>
 #include "../../include/t1k_gpu.h"
+#include "t1k_counters.h"  // the counter block: control words, statistics stripes, arena cursors, the error word
 
 // Longest read of the FAST kernels: the hit-offset masks of the chain kernels span 320 positions (10 words), k_extract_screen gives a
 // lane five consecutive k-mers and k_extract a thread three positions of both strands.  The genotyper / analyzer take reads of up to
@@ -768,9 +769,7 @@ __device__ inline int t1k_ga_traceback(const uint8_t *trace, int lent, int lenp,
 }
 
 // Statistics counters (never read by device code).  Millions of atomics on one address serialise in L2, so every
-// statistic is striped over T1K_STAT_STRIPES cache lines behind the 64 control counters; the host adds the stripes up.
-#define T1K_STAT_STRIPES 256
-enum { T1K_STAT_DP = 0, T1K_STAT_FAST = 1, T1K_STAT_GENERAL = 2, T1K_STAT_EXTEND_DP = 3, T1K_STAT_NEARBEST = 4, T1K_STAT_LOOKUPS = 5, T1K_STAT_POSTINGS = 6, T1K_STAT_HITS = 7 };
+// statistic is striped over T1K_STAT_STRIPES cache lines behind the control words (t1k_counters.h); the host adds the stripes up.
 // Allocation cursors.  A returning atomic on ONE word tops out near 88 M/s on this part, far below what the chain kernels
 // ask for, so every device arena (group records, work lists, queues) is cut into T1K_NSTRIPE independent segments with
 // their own cursor (64 bytes apart); a workgroup allocates from segment blockIdx.x % T1K_NSTRIPE.  Lists are made dense
@@ -809,10 +808,6 @@ enum { T1K_STAT_DP = 0, T1K_STAT_FAST = 1, T1K_STAT_GENERAL = 2, T1K_STAT_EXTEND
 #ifndef T1K_SELECT_MID_HANDOUT
 #define T1K_SELECT_MID_HANDOUT 1
 #endif
-// control counters of the selection: hand-out word and list length per size class (words 28 / 29 were the hand-out words of the two launches that
-// walked the whole range)
-#define T1K_CTR_SELECT_HANDOUT 56
-#define T1K_CTR_SELECT_LEN 59
 #ifndef T1K_TRUNC_SMALL_HANDOUT
 #define T1K_TRUNC_SMALL_HANDOUT 4
 #endif
@@ -831,17 +826,6 @@ enum { T1K_STAT_DP = 0, T1K_STAT_FAST = 1, T1K_STAT_GENERAL = 2, T1K_STAT_EXTEND
 #ifndef T1K_TRUNC_LARGE_WAVES
 #define T1K_TRUNC_LARGE_WAVES 0
 #endif
-#define T1K_NSTRIPE 32
-enum { T1K_AR_GROUPS = 0, T1K_AR_JOBS, T1K_AR_RETRY, T1K_AR_FINISH, T1K_AR_GENERAL, T1K_AR_BIG, T1K_AR_GENCAND, T1K_AR_EQ, T1K_AR_BAND, T1K_AR_WIDE, T1K_AR_GENHITS, T1K_AR_GENJOBS, T1K_AR_WAVE, T1K_AR_EXTJOBS, T1K_AR_EXTRETRY, T1K_AR_SLOW, T1K_NARENA };
-#define T1K_ARENA_BASE (64 + T1K_STAT_STRIPES * 8)
-// behind the cursors: one word per arena = the number of entries of its DENSE list (sum over the stripes of min(cursor, segCap)), written by
-// k_arena_compact where it makes the list dense -- the list's consumers read their item count there instead of from a launch argument, so
-// the host does not have to fetch the cursors between a producer and its consumers (t1k_run_chain: one counter fetch per range)
-#ifndef T1K_STRIPE_WORDS
-#define T1K_STRIPE_WORDS 8   // 64-bit words between the cursors of two stripes of an arena (8: 64 bytes apart; 16: a 128-byte cache line each)
-#endif
-#define T1K_TOTAL_BASE (T1K_ARENA_BASE + T1K_NARENA * T1K_NSTRIPE * T1K_STRIPE_WORDS)
-#define T1K_COUNTER_WORDS (T1K_TOTAL_BASE + ((T1K_NARENA + 7) & ~7))
 #define T1K_ARENA_FULL 0xFFFFFFFFu
 __device__ __forceinline__ unsigned long long *t1k_arena_cursor(unsigned long long *counters, int arena, uint32_t stripe) {
   return counters + T1K_ARENA_BASE + ((uint32_t)arena * T1K_NSTRIPE + stripe) * T1K_STRIPE_WORDS;
@@ -872,7 +856,7 @@ __device__ __forceinline__ void t1k_stat_add(unsigned long long *counters, int k
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   if ((threadIdx.x & 63) == 0 && v) {
     const unsigned int stripe = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (T1K_STAT_STRIPES - 1);
-    atomicAdd(&counters[64 + stripe * 8 + kind], (unsigned long long)v);
+    atomicAdd(&counters[T1K_STAT_BASE + stripe * T1K_STAT_KINDS + kind], (unsigned long long)v);
   }
 }
 
@@ -959,6 +943,9 @@ inline void t1k_stage_blocks(T1kStage &s, F &&f) {
   for (T1kStageBuf &m : s.more) f(std::string(m.name), m.b);
 }
 
+// the working capacities of the batch arenas (their rules: kCapRules, t1k_capi.hip)
+enum { T1K_CAP_GROUP = 0, T1K_CAP_LIST, T1K_CAP_RARE, T1K_CAP_JOB, T1K_CAP_GENJOB, T1K_CAP_CAND, T1K_CAP_OVL, T1K_CAP_GENHIT, T1K_NCAP };
+
 struct t1k_ctx {
   int device = 0;
   std::vector<unsigned long long> hRaw;  // last fetched counter block (control | statistics stripes | arena cursors)
@@ -998,8 +985,7 @@ struct t1k_ctx {
   T1kOvlP *storeBase = nullptr;    // where the running range's packed lists go
   // working capacities of the batch arenas (t1k_assign_range grows them on demand up to the limits in prm) and the demand the last
   // overflow reported
-  uint64_t wGroup = 0, wList = 0, wRare = 0, wCand = 0, wOvl = 0, wJob = 0, wGenJob = 0, wGenHit = 0;
-  uint64_t needGroup = 0, needList = 0, needRare = 0, needCand = 0, needOvl = 0, needJob = 0, needGenJob = 0, needGenHit = 0;
+  struct { uint64_t w = 0, need = 0; } cap[T1K_NCAP];
   unsigned long long lastCapFlags = 0;
   bool scaledOnce = false;
   bool covCommitted = false;     // the running range has started adding to the coverage arrays (no retry after that)

@@ -24,11 +24,11 @@
 #else
 #define PP(i) do { } while (0)
 #endif
-// -DT1K_PAIR_ROUTES: fragments and list records per join route and launch, counted in counters[40 .. 52) and summed per process (a
+// -DT1K_PAIR_ROUTES: fragments and list records per join route and launch, counted in the T1K_WIN_PAIR_ROUTES window and summed per process (a
 // measurement build: thread 0 pays two atomics per fragment)
 #ifdef T1K_PAIR_ROUTES
 #define T1K_ROUTE_COUNT() do { if (tid == 0) { const int r_ = 2 * ((jt.direct() ? 2 : jt.lds() ? 0 : 1) + (P.only ? 3 : 0)); \
-  atomicAdd(&P.counters[40 + r_], 1ull); atomicAdd(&P.counters[41 + r_], (unsigned long long)(n1 + n2)); } } while (0)
+  atomicAdd(&P.counters[T1K_WIN_PAIR_ROUTES + r_], 1ull); atomicAdd(&P.counters[T1K_WIN_PAIR_ROUTES + 1 + r_], (unsigned long long)(n1 + n2)); } } while (0)
 #else
 #define T1K_ROUTE_COUNT() do { } while (0)
 #endif
@@ -164,10 +164,10 @@ struct PairArgs {
   uint32_t epochBase;              // epoch of fragment f = epochBase + f + 1 (never 0, never reused between clears)
   Frag *frags; uint32_t fragCap;   // [wg][fragCap]
   uint32_t *keep;                  // [wg][fragCap]
-  unsigned long long *counters;    // [2] error flags, [9] row total
+  unsigned long long *counters;    // the T1K_PCTR_* words (t1k_counters.h)
   // second pass (same launch sequence, no host step between the two): the fragments whose two lists did not fit the first pass's per-workgroup
-  // scratch.  `only` = {fragment, offset of its scratch in the big arena} pairs written by the first pass, their number in counters[23]
-  // (read by the device: the launch is unconditional and sized to fill the chip), the arena cursor in counters[24] (entries, counted past
+  // scratch.  `only` = {fragment, offset of its scratch in the big arena} pairs written by the first pass, their number in T1K_PCTR_LONG
+  // (read by the device: the launch is unconditional and sized to fill the chip), the arena cursor in T1K_PCTR_BIG_CURSOR (entries, counted past
   // the capacity so that the host knows what to allocate when it has to run the call again)
   const uint32_t *only;
   Frag *bigFrags; uint32_t *bigKeep; uint64_t bigCap;
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
 #ifdef T1K_PAIR_PROFILE
   uint64_t tp_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = __builtin_amdgcn_s_memtime();
 #endif
-  const uint32_t nItems = P.only ? (uint32_t)P.counters[23] : P.nFragments;
+  const uint32_t nItems = P.only ? (uint32_t)P.counters[T1K_PCTR_LONG] : P.nFragments;
   // fragments are handed out one at a time (a device counter per launch): their cost spans two orders of magnitude (0 .. 8192 and more
   // overlaps), and with a fixed stride the kernel lasted as long as its unluckiest workgroup
   // Round 6: a fragment cost FOUR atomics on three hot words of the counter block -- the hand-out and the row cursor (both returning), the
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
   unsigned long long rowNext = 0; uint32_t rowLeft = 0;    // thread 0: what is left of its last reservation in the rowset's chunk
   for (;;) {
     if (tid == 0) {
-      if (hoLeft == 0) { hoNext = (uint32_t)atomicAdd(&P.counters[P.only ? 26 : 25], (unsigned long long)T1K_PAIR_HANDOUT); hoLeft = T1K_PAIR_HANDOUT; }
+      if (hoLeft == 0) { hoNext = (uint32_t)atomicAdd(&P.counters[P.only ? T1K_PCTR_HANDOUT + 1 : T1K_PCTR_HANDOUT], (unsigned long long)T1K_PAIR_HANDOUT); hoLeft = T1K_PAIR_HANDOUT; }
       sItem = hoNext++; --hoLeft;
       sDup = 0; sFail = 0; sBestM = -1; sBestIdx = 0x7FFFFFFF; sAnySep = 0; sNotOne = 0; sN = 0; sLo = 0xFFFFFFFFu; sHi = 0;
     }
@@ -348,15 +348,15 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
     if (n1 + n2 > fragCap) {
       if (P.overflowList) {  // the second launch takes it, with a scratch of its own size
         if (tid == 0) {
-          const unsigned long long q = atomicAdd(&P.counters[23], 1ull);
-          const unsigned long long off = atomicAdd(&P.counters[24], (unsigned long long)(n1 + n2));
+          const unsigned long long q = atomicAdd(&P.counters[T1K_PCTR_LONG], 1ull);
+          const unsigned long long off = atomicAdd(&P.counters[T1K_PCTR_BIG_CURSOR], (unsigned long long)(n1 + n2));
           P.overflowList[2 * q] = f; P.overflowList[2 * q + 1] = (uint32_t)min(off, 0xFFFFFFFFull);
         }
         __syncthreads();
         continue;
       }
       if (tid == 0) {
-        atomicOr(&P.counters[2], P.only ? 1024ull : 128ull);  // 1024: the big arena is too small (the host grows it to counters[24] and runs the call again)
+        atomicOr(&P.counters[T1K_PCTR_ERR], P.only ? (unsigned long long)PAIR_ERR_BIGARENA : (unsigned long long)PAIR_ERR_ROWS);  // (big arena: the host grows it to T1K_PCTR_BIG_CURSOR and runs the call again)
         if (P.rsRowPtr) { P.rsRowCount[P.fragBase + f] = 0; P.rsAssigned[P.fragBase + f] = 0; }
         else { P.rowStart[f] = 0; P.rowCount[f] = 0; P.fragAssigned[f] = 0; }
       }
@@ -788,8 +788,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
     const double adjust = sNotOne ? 1.0 : 0.25;  // 804-817
     if (!P.rsRowPtr) {
       if (tid == 0) {
-        unsigned long long b = nRow ? atomicAdd(&P.counters[9], (unsigned long long)nRow) : 0ull;
-        if (b + nRow > P.rowCap) { atomicOr(&P.counters[2], 128ull); sBase = 0xFFFFFFFFu; P.rowStart[f] = 0; P.rowCount[f] = 0; }
+        unsigned long long b = nRow ? atomicAdd(&P.counters[T1K_PCTR_ROWS], (unsigned long long)nRow) : 0ull;
+        if (b + nRow > P.rowCap) { atomicOr(&P.counters[T1K_PCTR_ERR], (unsigned long long)PAIR_ERR_ROWS); sBase = 0xFFFFFFFFu; P.rowStart[f] = 0; P.rowCount[f] = 0; }
         else { sBase = (uint32_t)b; P.rowStart[f] = (uint32_t)b; P.rowCount[f] = nRow; }
         P.fragAssigned[f] = anyKept ? 1 : 0;
       }
@@ -829,7 +829,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
           if (b + take > P.rsCap) fitsChunk = false; else { rowNext = b + nRow; rowLeft = (uint32_t)(take - nRow); }
         }
       }
-      if (!fitsChunk) { atomicOr(&P.counters[2], 128ull); sRowBase = ~0ull; }
+      if (!fitsChunk) { atomicOr(&P.counters[T1K_PCTR_ERR], (unsigned long long)PAIR_ERR_ROWS); sRowBase = ~0ull; }
       else { sRowBase = b; sStatRows += nRow; }
     }
     // rank of every entry among the row's (distinct) alleles
@@ -884,11 +884,11 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(T1K_PAIR_WAV
     PP(7);
   }
   if (tid == 0) {  // the workgroup's statistics, once
-    if (sStatOvl) atomicAdd(&P.counters[22], sStatOvl);
-    if (sStatRows) atomicAdd(&P.counters[9], sStatRows);
+    if (sStatOvl) atomicAdd(&P.counters[T1K_PCTR_OVERLAPS], sStatOvl);
+    if (sStatRows) atomicAdd(&P.counters[T1K_PCTR_ROWS], sStatRows);
   }
 #ifdef T1K_PAIR_PROFILE
-  if (tid == 0) for (int i = 0; i < 8; ++i) atomicAdd(&P.counters[32 + i], (unsigned long long)tp_[i]);
+  if (tid == 0) for (int i = 0; i < T1K_WIN_PAIR_PROFILE_LEN; ++i) atomicAdd(&P.counters[T1K_WIN_PAIR_PROFILE + i], (unsigned long long)tp_[i]);
 #endif
 }
 
@@ -971,11 +971,11 @@ static int pairLaunch(t1k_ctx *ctx, t1k_rowset *rs, const uint32_t *end1, const 
   p.direct = pairDirectOn();
   if (getenv("T1K_DEBUG_TRACE")) fprintf(stderr, "[t1k trace] pair %u fragments%s\n", n, rs ? " into the rowset" : "");
   for (int attempt = 0;; ++attempt) {
-    T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + 2 * 8, 0, 8, ctx->stream));
-    T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + 9 * 8, 0, 8, ctx->stream));
-    T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + 22 * 8, 0, 40, ctx->stream));  // [22] overlaps read, [23] long fragments, [24] their arena cursor, [25] / [26] next fragment of the two launches
+    T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + T1K_PCTR_ERR * 8, 0, 8, ctx->stream));
+    T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + T1K_PCTR_ROWS * 8, 0, 8, ctx->stream));
+    T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + T1K_PCTR_CLEAR_FIRST * 8, 0, T1K_PCTR_CLEAR_WORDS * 8, ctx->stream));  // overlaps read, long fragments, their arena cursor, next fragment of the two launches
 #ifdef T1K_PAIR_ROUTES
-    T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + 40 * 8, 0, 12 * 8, ctx->stream));
+    T1K_HIP(ctx, hipMemsetAsync((char *)ctx->bCounters.p + T1K_WIN_PAIR_ROUTES * 8, 0, T1K_WIN_PAIR_ROUTES_LEN * 8, ctx->stream));
 #endif
     size_t chunk = 0;
     if (rs) {
@@ -989,7 +989,7 @@ static int pairLaunch(t1k_ctx *ctx, t1k_rowset *rs, const uint32_t *end1, const 
     launch((unsigned)nWg, p);
     {
       // second launch, always: the fragments whose lists exceed the first pass's scratch (with 29 k alleles the large genes put whole classes
-      // of fragments here).  Their number is on the device (counters[23]); the workgroups beyond it leave at once.  Same per-workgroup
+      // of fragments here).  Their number is on the device (T1K_PCTR_LONG); the workgroups beyond it leave at once.  Same per-workgroup
       // allele tables as the first launch (the kernels run one after the other on this stream), fresh epochs.
       PairArgs q = p;
       q.only = (const uint32_t *)ctx->bPairOverflow.p; q.overflowList = nullptr;
@@ -999,27 +999,27 @@ static int pairLaunch(t1k_ctx *ctx, t1k_rowset *rs, const uint32_t *end1, const 
     }
     T1K_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     if (!ctx->countersPinned) T1K_HIP(ctx, hipHostMalloc((void **)&ctx->countersPinned, (size_t)T1K_COUNTER_WORDS * 8, hipHostMallocDefault));
-    T1K_HIP(ctx, hipMemcpyAsync(ctx->countersPinned, ctx->bCounters.p, 64 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    T1K_HIP(ctx, hipMemcpyAsync(ctx->countersPinned, ctx->bCounters.p, T1K_CTR_WORDS * 8, hipMemcpyDeviceToHost, ctx->stream));
     T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));
     unsigned long long *hc = ctx->countersPinned;
     { float ms = 0; (void)hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]); ctx->stats.ms_pair = (attempt ? ctx->stats.ms_pair : 0) + ms; }
-    if ((hc[2] & 1024ull) && attempt < 4) {
-      // the big arena was too small for this call's long fragments: the device counted the demand (counters[24]); fragments are written
+    if ((hc[T1K_PCTR_ERR] & PAIR_ERR_BIGARENA) && attempt < 4) {
+      // the big arena was too small for this call's long fragments: the device counted the demand (T1K_PCTR_BIG_CURSOR); fragments are written
       // by index, so the call simply runs again (the rows of the first attempt are left behind in the rowset's chunk)
-      ctx->pairBigCap = (uint64_t)((double)hc[24] * 1.25) + (getenv("T1K_PAIR_BIGCAP") ? 16 : (1u << 20));
+      ctx->pairBigCap = (uint64_t)((double)hc[T1K_PCTR_BIG_CURSOR] * 1.25) + (getenv("T1K_PAIR_BIGCAP") ? 16 : (1u << 20));
       if ((rc = t1k_ensure(ctx, ctx->bPairBig, (size_t)ctx->pairBigCap * (sizeof(Frag) + 4)))) return rc;
       if (getenv("T1K_DEBUG_TRACE")) fprintf(stderr, "[t1k trace] pair: big arena grows to %llu entries\n", (unsigned long long)ctx->pairBigCap);
-      if (!rs || !(hc[2] & ~1024ull)) continue;
+      if (!rs || !(hc[T1K_PCTR_ERR] & ~(unsigned long long)PAIR_ERR_BIGARENA)) continue;
     }
-    if (hc[2] && rs && attempt < 4) {
+    if (hc[T1K_PCTR_ERR] && rs && attempt < 4) {
       // the rowset's current chunk is full (or a fragment has more overlaps than the scratch holds: that repeats and fails below):
       // close the chunk and run the call again; fragments are written by index, the first attempt's rows are simply left behind
       if ((rc = t1k_rowset_chunk_full(rs, ctx, chunk))) return rc;
       continue;
     }
-    if (hc[2]) return t1k_fail(ctx, T1K_ERR_CAPACITY, "device arena overflow: row_cap / fragment scratch");
-    if (!rs) ctx->nRows = hc[9];
-    ctx->stats.rows = hc[9]; ctx->stats.pair_overlaps = hc[22];
+    if (hc[T1K_PCTR_ERR]) return t1k_fail(ctx, T1K_ERR_CAPACITY, "device arena overflow: row_cap / fragment scratch");
+    if (!rs) ctx->nRows = hc[T1K_PCTR_ROWS];
+    ctx->stats.rows = hc[T1K_PCTR_ROWS]; ctx->stats.pair_overlaps = hc[T1K_PCTR_OVERLAPS];
 #ifdef T1K_PAIR_ROUTES
     {
       static unsigned long long sum[12];
@@ -1028,11 +1028,12 @@ static int pairLaunch(t1k_ctx *ctx, t1k_rowset *rs, const uint32_t *end1, const 
         for (int r = 0; r < 6; ++r) fprintf(stderr, "[t1k] pair routes (direct route %d): %-22s %12llu fragments %14llu records\n", pairDirectOn(), name[r], sum[2 * r], sum[2 * r + 1]);
       });
       (void)once;
-      for (int r = 0; r < 12; ++r) __atomic_fetch_add(&sum[r], hc[40 + r], __ATOMIC_RELAXED);
+      for (int r = 0; r < T1K_WIN_PAIR_ROUTES_LEN; ++r) __atomic_fetch_add(&sum[r], hc[T1K_WIN_PAIR_ROUTES + r], __ATOMIC_RELAXED);
     }
 #endif
 #ifdef T1K_PAIR_PROFILE
-    fprintf(stderr, "[t1k] pair phases (ticks, thread 0 of every workgroup): tables %llu join %llu best %llu keep %llu rules %llu setreads %llu rank %llu rows+hash %llu\n", hc[32], hc[33], hc[34], hc[35], hc[36], hc[37], hc[38], hc[39]);
+    const unsigned long long *pp = hc + T1K_WIN_PAIR_PROFILE;
+    fprintf(stderr, "[t1k] pair phases (ticks, thread 0 of every workgroup): tables %llu join %llu best %llu keep %llu rules %llu setreads %llu rank %llu rows+hash %llu\n", pp[0], pp[1], pp[2], pp[3], pp[4], pp[5], pp[6], pp[7]);
 #endif
     return T1K_OK;
   }

@@ -425,7 +425,7 @@ __device__ __forceinline__ void seedGroupsBody(const ChainArgs &P) {
         if (tid == 0) {
           const uint32_t gb = gTot ? t1k_arena_alloc(P.counters, T1K_AR_GROUPS, gTot, P.groupSegCap) : 0u;
           const bool ok = gb != T1K_ARENA_FULL && chunk < P.maxChunks;
-          if (!ok) atomicOr(&P.counters[2], (unsigned long long)ERR_GROUPCAP);
+          if (!ok) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_GROUPCAP);
           sGroupBase = ok ? gb : 0xFFFFFFFFu;
           if (ok && gTot) { P.chunkStart[(uint64_t)re * P.maxChunks + chunk] = gb; P.chunkCount[(uint64_t)re * P.maxChunks + chunk] = gTot; }
         }
@@ -468,10 +468,10 @@ __device__ __forceinline__ void seedGroupsBody(const ChainArgs &P) {
     }
   }
 #ifdef T1K_SEED_PROFILE
-  if (tid == 0) for (int i = 0; i < 8; ++i) atomicAdd(&P.counters[48 + i], (unsigned long long)tp_[i]);
+  if (tid == 0) for (int i = 0; i < T1K_WIN_SEED_PROFILE_LEN; ++i) atomicAdd(&P.counters[T1K_WIN_SEED_PROFILE + i], (unsigned long long)tp_[i]);
 #endif
   if (tid == 0) {  // statistics: one striped atomic per workgroup and counter
-    unsigned long long *st = P.counters + 64 + (blockIdx.x & (T1K_STAT_STRIPES - 1)) * 8;
+    unsigned long long *st = P.counters + T1K_STAT_BASE + (blockIdx.x & (T1K_STAT_STRIPES - 1)) * T1K_STAT_KINDS;
     atomicAdd(&st[T1K_STAT_LOOKUPS], sStat[0]); atomicAdd(&st[T1K_STAT_POSTINGS], sStat[1]); atomicAdd(&st[T1K_STAT_HITS], sStat[2]);
   }
 }
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(WG) void k_seed_long(ChainArgs P) {
       }
       if (tid == 0) {
         P.usedCount[2 * re] = sUsed[0]; P.usedCount[2 * re + 1] = sUsed[1];
-        unsigned long long *st = P.counters + 64 + (blockIdx.x & (T1K_STAT_STRIPES - 1)) * 8;
+        unsigned long long *st = P.counters + T1K_STAT_BASE + (blockIdx.x & (T1K_STAT_STRIPES - 1)) * T1K_STAT_KINDS;
         atomicAdd(&st[T1K_STAT_LOOKUPS], (unsigned long long)lookups); atomicAdd(&st[T1K_STAT_POSTINGS], (unsigned long long)postings);
       }
     }
@@ -603,7 +603,7 @@ __global__ __launch_bounds__(WG) void k_seed_long(ChainArgs P) {
         if (tid == 0) {
           const uint32_t gb = gTot ? t1k_arena_alloc(P.counters, T1K_AR_GROUPS, gTot, P.groupSegCap) : 0u;
           const bool ok = gb != T1K_ARENA_FULL && chunk < P.maxChunks;
-          if (!ok) atomicOr(&P.counters[2], (unsigned long long)ERR_GROUPCAP);
+          if (!ok) atomicOr(&P.counters[T1K_CTR_ERR], (unsigned long long)ERR_GROUPCAP);
           sGroupBase = ok ? gb : 0xFFFFFFFFu;
           if (ok && gTot) { P.chunkStart[(uint64_t)re * P.maxChunks + chunk] = gb; P.chunkCount[(uint64_t)re * P.maxChunks + chunk] = gTot; }
         }
