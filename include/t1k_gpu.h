@@ -625,6 +625,29 @@ typedef struct {
 int t1k_route_report_enable(t1k_ctx *ctx, int on);
 int t1k_route_report_get(t1k_ctx *ctx, t1k_route_totals *totals /* may be NULL */, t1k_route_rec *recs /* may be NULL */, uint64_t cap, uint64_t *nRecs);
 
+/* ---- seed report: which k-mers of each read-end had their posting lists used (diagnostics and tests) ----------------
+ * The look-up rule of SeqSet::GetHitsFromRead as the seeding kernels decided it, per read-end.  Host side only: no kernel knows of it.
+ * Off by default, and then t1k_assign_range issues exactly the launches and copies it issues without it.  t1k_seed_report_enable(ctx, 1)
+ * clears the report and starts it (start it again after another read set was uploaded: the records are indexed by read-end in the
+ * uploaded set); (ctx, 0) stops it and drops what it held.  While it is on, every range that t1k_assign_range finishes copies, for each of
+ * its read-ends, the used-k-mer counts per strand, the used entries and the two used-offset masks out of the seeding kernels' buffers;
+ * a range that ran again after a capacity error counts once, from the pass that was kept, and a read-end assigned again replaces its record.
+ * t1k_seed_report_get, every array optional (NULL), n = the read-ends of the uploaded set:
+ *   seen[n]                            1: a finished range held the read-end since the report was started
+ *   counts[n][2]                       used k-mers of the read-end as given / of its reverse complement
+ *   masks[n][2][T1K_SEED_MASK_WORDS]   bit r = the list of the k-mer at read offset r of that strand is used; all zero for a read-end the
+ *                                      mask kernel does not seed (shorter than k, beyond 320 bases, or linked to an earlier window)
+ *   used[*nUsed]                       the used entries of all seen read-ends, by read-end, the read-end as given first, in the order the
+ *                                      kernel kept them (ascending offset); cap < *nUsed: T1K_ERR_ARG, *nUsed is still set
+ * T1K_ERR_STATE while the report is off. */
+#define T1K_SEED_MASK_WORDS 10
+typedef struct {
+  uint32_t read_off, list_len;    /* offset of the k-mer in its strand's text; postings of its list */
+  uint8_t strand, reserved[3];    /* 0: the read-end as given, 1: its reverse complement */
+} t1k_seed_used;
+int t1k_seed_report_enable(t1k_ctx *ctx, int on);
+int t1k_seed_report_get(t1k_ctx *ctx, uint8_t *seen, uint32_t *counts, uint32_t *masks, t1k_seed_used *used, uint64_t cap, uint64_t *nUsed);
+
 /* wall time (ms) the context has spent allocating device memory and the bytes it asked for (diagnostics) */
 double t1k_alloc_ms(t1k_ctx *ctx, uint64_t *bytes);
 /* the device blocks the context holds right now, in bytes; print != 0: one line on stderr naming every block of 64 MB and more (diagnostics, T1K_DEBUG_MEM) */

@@ -101,6 +101,28 @@ int orc_kmer_postings(void *h, const char *kmer, int *alleles, int cap) {
   return o->kmerPostings(code, alleles, cap);
 }
 
+// the look-up rule of SeqSet::GetHitsFromRead as Oracle::seedHits restates it: the distinct (strand, read offset) of the hits in the
+// order they were made (the read as given first; strand 0 = as given, 1 = reverse complement), the length of each one's posting list,
+// and what the call added to stats.lookups / stats.postings.  At most cap entries written; returns their number.
+int orc_seed_used(void *h, const char *read, int *strand, int *readOff, int *listLen, int cap, unsigned long long *lookups, unsigned long long *postings) {
+  Oracle *o = (Oracle *)h;
+  const uint64_t l0 = o->stats.lookups, p0 = o->stats.postings;
+  std::vector<int> st, off;
+  std::vector<Posting> post;
+  if ((int)strlen(read) >= o->prm.k) o->seedHits(read, st, off, post);  // GetOverlapsFromRead returns before seeding a shorter read (SeqSet.hpp:1598-1599)
+  if (lookups) *lookups = o->stats.lookups - l0;
+  if (postings) *postings = o->stats.postings - p0;
+  int n = 0;
+  for (size_t i = 0; i < st.size();) {
+    size_t j = i;
+    while (j < st.size() && st[j] == st[i] && off[j] == off[i]) ++j;
+    if (n < cap) { strand[n] = st[i] == 1 ? 0 : 1; readOff[n] = off[i]; listLen[n] = (int)(j - i); }
+    ++n;
+    i = j;
+  }
+  return n;
+}
+
 // per-base coverage of the allele's own base (the only counter GetSeqMissingBaseCoverage reads, SeqSet.hpp:2729)
 int orc_coverage(void *h, int allele, int *out, int cap) {
   Oracle *o = (Oracle *)h;

@@ -360,7 +360,6 @@ void Oracle::buildIndex() {
   const int k = prm.k;
   const uint64_t mask = (1ull << (2 * k)) - 1;
   size_t nKeys = (size_t)1 << (2 * k);
-  std::vector<uint32_t> cnt(nKeys + 1, 0);
   std::vector<std::pair<uint32_t, Posting>> tmp;
   for (int a = 0; a < (int)alleles.size(); ++a) {
     const std::string &s = alleles[a].seq;
@@ -376,16 +375,17 @@ void Oracle::buildIndex() {
       if (i < k - 1) continue;
       if (invalid == -1 && (i == k || code != prev)) {
         tmp.push_back({(uint32_t)code, Posting{(uint32_t)a, (uint32_t)(i - k + 1)}});
-        ++cnt[code + 1];
       }
       prev = code;
     }
   }
+  // (one table of 4^k + 1 words, not three: at k = 15 each of them is 4 GB)
   idxStart.assign(nKeys + 1, 0);
-  for (size_t i = 0; i < nKeys; ++i) idxStart[i + 1] = idxStart[i] + cnt[i + 1];
+  for (auto &e : tmp) ++idxStart[(size_t)e.first + 1];
+  for (size_t i = 0; i < nKeys; ++i) idxStart[i + 1] += idxStart[i];
+  std::stable_sort(tmp.begin(), tmp.end(), [](const std::pair<uint32_t, Posting> &a, const std::pair<uint32_t, Posting> &b) { return a.first < b.first; });  // insertion order inside a list
   idxPost.resize(tmp.size());
-  std::vector<uint32_t> cur(idxStart.begin(), idxStart.end() - 1);
-  for (auto &e : tmp) idxPost[cur[e.first]++] = e.second;
+  for (size_t i = 0; i < tmp.size(); ++i) idxPost[i] = tmp[i].second;
 }
 
 // SeqSet::GetHitsFromRead (SeqSet.hpp:1071-1229) with strand=0, barcode=-1, puse=NULL, allowTotalSkip=false

@@ -84,6 +84,10 @@ ROUTE_REC_DTYPE = np.dtype([("read_end", "<u4"), ("allele", "<u4"), ("n", "<u4")
                             ("nw", "u1"), ("xlong", "u1"), ("reserved", "u1", (2,))])
 ROUTE_NAMES = ("general_lane", "wave_small", "wave_large", "big_by_size", "big_by_scratch")
 assert ROUTE_REC_DTYPE.itemsize == 20
+# t1k_seed_used / T1K_SEED_MASK_WORDS (seed report)
+SEED_USED_DTYPE = np.dtype([("read_off", "<u4"), ("list_len", "<u4"), ("strand", "u1"), ("reserved", "u1", (3,))])
+SEED_MASK_WORDS = 10
+assert SEED_USED_DTYPE.itemsize == 12
 CIGAR_FILL = 0xAB  # what Context.cigar_batch fills its output arrays with before the call
 ALT_FILL = 0xCD    # what Context.alt_batch fills its tables with before the call
 ALT_EMPTY = 0xFFFFFFFF  # slotOf of an allele that is not called
@@ -173,6 +177,8 @@ def lib():
     L.t1k_stats_get.argtypes = [vp, C.POINTER(Stats)]
     L.t1k_route_report_enable.argtypes = [vp, C.c_int]
     L.t1k_route_report_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
+    L.t1k_seed_report_enable.argtypes = [vp, C.c_int]
+    L.t1k_seed_report_get.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
     L.t1k_genotyper_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_job_params_default.argtypes = [C.POINTER(JobParams)]
     L.t1k_job_create.argtypes = [C.POINTER(JobParams), C.c_char_p, C.POINTER(vp)]
@@ -456,6 +462,31 @@ class Context:
         recs = np.zeros(n.value, ROUTE_REC_DTYPE)
         self._check(lib().t1k_route_report_get(self.h, _ptr(tot), _ptr(recs), n.value, C.byref(n)), "t1k_route_report_get")
         return dict(zip(ROUTE_TOTALS, (int(x) for x in tot))), recs
+
+    def assign_range(self, first, count):
+        """t1k_assign_range: the read-ends [first, first + count) of the uploaded set as one range"""
+        self._check(lib().t1k_assign_range(self.h, first, count), "t1k_assign_range")
+
+    def seed_report_enable(self, on=True):
+        """starts (and clears) or stops the seed report (t1k_seed_report_enable)"""
+        self._check(lib().t1k_seed_report_enable(self.h, 1 if on else 0), "t1k_seed_report_enable")
+
+    def seed_report(self):
+        """the used k-mers of the read-ends of the ranges finished since seed_report_enable(): (seen[n] uint8, counts[n, 2], masks[n, 2,
+        SEED_MASK_WORDS], used_ptr[n + 1], used as SEED_USED_DTYPE); read-end i's entries are used[used_ptr[i]:used_ptr[i + 1]], the
+        read-end as given first"""
+        n = self.n_read_ends
+        tot = C.c_uint64()
+        self._check(lib().t1k_seed_report_get(self.h, None, None, None, None, 0, C.byref(tot)), "t1k_seed_report_get")
+        seen = np.zeros(n, np.uint8)
+        counts = np.zeros((n, 2), np.uint32)
+        masks = np.zeros((n, 2, SEED_MASK_WORDS), np.uint32)
+        used = np.zeros(tot.value, SEED_USED_DTYPE)
+        self._check(lib().t1k_seed_report_get(self.h, _ptr(seen), _ptr(counts), _ptr(masks), _ptr(used), tot.value, C.byref(tot)), "t1k_seed_report_get")
+        ptr = np.zeros(n + 1, np.int64)
+        np.cumsum(counts.sum(axis=1, dtype=np.int64), out=ptr[1:])
+        assert int(ptr[-1]) == len(used)
+        return seen, counts, masks, ptr, used
 
     def align_batch(self, texts, pats, want_ops=True):
         n = len(texts)

@@ -847,6 +847,15 @@ static void routeCommit(t1k_ctx *ctx) {
   rr.passRecs.clear();
 }
 
+// Seed report: the kept pass's record joins the report (a read-end assigned again is answered from the later record: t1k_seed_report_get)
+static void seedCommit(t1k_ctx *ctx) {
+  auto &sr = ctx->seedRep;
+  if (!sr.passValid) return;
+  sr.kept.push_back(std::move(sr.pass));
+  sr.pass = t1k_ctx::SeedRange{};
+  sr.passValid = false;
+}
+
 // Working capacities.  t1k_params holds the LIMITS of the batch arenas; what is allocated follows the demand: the first range
 // starts from a floor per read-end, an overflow (always detected before anything of the range is committed) raises the working
 // capacity to the demand the device counted and the range runs again.  Fresh VRAM costs about 35 ms per GB on this platform
@@ -872,8 +881,10 @@ int t1k_assign_range(t1k_ctx *ctx, uint64_t first, uint32_t count) {
   for (int attempt = 0;; ++attempt) {
     ctx->lastCapFlags = 0;
     for (auto &c : ctx->cap) c.need = 0;
+    ctx->seedRep.passValid = false;
     const int rc = assignOnce(ctx, first, count);
     if (ctx->route.on && rc == T1K_OK && count) routeCommit(ctx);  // (opt-in: the pass that was kept, once)
+    if (ctx->seedRep.on && rc == T1K_OK && count) seedCommit(ctx);
     if (rc != T1K_ERR_CAPACITY || attempt >= 10) return rc;
     const unsigned long long flags = ctx->lastCapFlags;
     bool grew = false;
@@ -1222,6 +1233,47 @@ int t1k_route_report_get(t1k_ctx *ctx, t1k_route_totals *totals, t1k_route_rec *
   if (recs) {
     if (cap < *nRecs) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_route_report_get: room for " + std::to_string(cap) + " records, " + std::to_string(*nRecs) + " held");
     if (*nRecs) memcpy(recs, ctx->route.keptRecs.data(), *nRecs * sizeof(t1k_route_rec));
+  }
+  return T1K_OK;
+}
+
+int t1k_seed_report_enable(t1k_ctx *ctx, int on) {
+  if (!ctx) return T1K_ERR_ARG;
+  ctx->seedRep.on = on != 0;
+  ctx->seedRep.passValid = false;
+  ctx->seedRep.pass = t1k_ctx::SeedRange{};
+  ctx->seedRep.kept.clear();
+  return T1K_OK;
+}
+
+int t1k_seed_report_get(t1k_ctx *ctx, uint8_t *seen, uint32_t *counts, uint32_t *masks, t1k_seed_used *used, uint64_t cap, uint64_t *nUsed) {
+  if (!ctx || !nUsed) return T1K_ERR_ARG;
+  if (!ctx->seedRep.on) return t1k_fail(ctx, T1K_ERR_STATE, "t1k_seed_report_get: the seed report is off (t1k_seed_report_enable)");
+  const uint64_t n = ctx->reads.nReadEnds;
+  constexpr uint32_t MW = 2 * T1K_SEED_MASK_WORDS;
+  // the record that answers for each read-end: the last kept range that held it
+  std::vector<uint32_t> owner(n, 0xFFFFFFFFu);
+  const auto &kept = ctx->seedRep.kept;
+  for (size_t r = 0; r < kept.size(); ++r)
+    for (uint64_t i = kept[r].first; i < kept[r].first + kept[r].count && i < n; ++i) owner[i] = (uint32_t)r;
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < n; ++i)
+    if (owner[i] != 0xFFFFFFFFu) { const auto &k = kept[owner[i]]; const uint64_t j = i - k.first; total += k.usedPtr[j + 1] - k.usedPtr[j]; }
+  *nUsed = total;
+  if (used && cap < total) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_seed_report_get: room for " + std::to_string(cap) + " used entries, " + std::to_string(total) + " held");
+  uint64_t at = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const bool have = owner[i] != 0xFFFFFFFFu;
+    if (seen) seen[i] = have ? 1 : 0;
+    if (counts) { counts[2 * i] = 0; counts[2 * i + 1] = 0; }
+    if (masks) std::fill_n(masks + i * MW, MW, 0u);
+    if (!have) continue;
+    const auto &k = kept[owner[i]];
+    const uint64_t j = i - k.first;
+    if (counts) { counts[2 * i] = k.counts[2 * j]; counts[2 * i + 1] = k.counts[2 * j + 1]; }
+    if (masks) std::copy_n(&k.masks[j * MW], MW, masks + i * MW);
+    if (used) std::copy(k.used.begin() + k.usedPtr[j], k.used.begin() + k.usedPtr[j + 1], used + at);
+    at += k.usedPtr[j + 1] - k.usedPtr[j];
   }
   return T1K_OK;
 }

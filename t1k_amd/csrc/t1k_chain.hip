@@ -1531,6 +1531,52 @@ static int routeCollect(t1k_ctx *ctx, const ChainArgs &a, bool longReads, bool x
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Seed report (t1k_seed_report_enable): what the seeding kernels decided for every read-end of the pass that has just ended, copied
+// from the buffers ChainArgs names -- usedCount, usedOut (read offset and list length of each used k-mer; the first usedCount[2 re]
+// entries are the read-end as given) and usedMask.  k_seed_groups writes a read-end's masks only where it seeds it (k <= len <=
+// T1K_MAX_READ_LEN, not linked to an earlier window): the others' words are whatever the block held and are reported as zero.  Host
+// only, like the route report: the stream is idle, the buffers are not used again before the next range.
+// ------------------------------------------------------------------------------------------------------------------
+static_assert(T1K_SEED_MASK_WORDS == T1K_USED_MASK_WORDS, "the seed report hands the kernels' used-offset masks out as they are");
+static int seedCollect(t1k_ctx *ctx, const ChainArgs &a) {
+  auto &p = ctx->seedRep.pass;
+  const uint32_t n = a.reads.nReadEnds;
+  constexpr uint32_t MW = 2 * T1K_USED_MASK_WORDS;
+  p.first = (uint64_t)(a.reads.len - ctx->reads.len); p.count = n;  // the range's first read-end in the uploaded set
+  p.counts.assign((size_t)n * 2, 0); p.masks.assign((size_t)n * MW, 0); p.usedPtr.assign((size_t)n + 1, 0); p.used.clear();
+  std::vector<uint32_t> masks((size_t)n * MW);
+  std::vector<uint16_t> len(n);
+  std::vector<uint8_t> skip(a.reads.skip ? n : 0);
+  T1K_HIP(ctx, hipMemcpy(p.counts.data(), a.usedCount, (size_t)n * 2 * 4, hipMemcpyDeviceToHost));
+  T1K_HIP(ctx, hipMemcpy(masks.data(), a.usedMask, (size_t)n * MW * 4, hipMemcpyDeviceToHost));
+  T1K_HIP(ctx, hipMemcpy(len.data(), a.reads.len, (size_t)n * 2, hipMemcpyDeviceToHost));
+  if (a.reads.skip) T1K_HIP(ctx, hipMemcpy(skip.data(), a.reads.skip, n, hipMemcpyDeviceToHost));
+  const size_t stride = (size_t)a.maxK * 4;  // words of a read-end's used-list table
+  const uint32_t slab = (uint32_t)std::max<size_t>(1, (size_t)(16u << 20) / std::max<size_t>(stride, 1));  // read-ends per copy (64 MB)
+  std::vector<uint32_t> buf;
+  for (uint32_t r0 = 0; r0 < n; r0 += slab) {
+    const uint32_t r1 = (uint32_t)std::min<uint64_t>(n, (uint64_t)r0 + slab);
+    buf.resize((size_t)(r1 - r0) * stride);
+    T1K_HIP(ctx, hipMemcpy(buf.data(), a.usedOut + (size_t)r0 * stride, buf.size() * 4, hipMemcpyDeviceToHost));
+    for (uint32_t re = r0; re < r1; ++re) {
+      const uint32_t plus = p.counts[2 * (size_t)re], all = plus + p.counts[2 * (size_t)re + 1];
+      if (all > a.maxK) return t1k_fail(ctx, T1K_ERR_INTERNAL, "seed report: a read-end has more used k-mers than its table holds");
+      const uint32_t *uo = &buf[(size_t)(re - r0) * stride];
+      for (uint32_t u = 0; u < all; ++u) {
+        t1k_seed_used e{};
+        e.read_off = uo[4 * u]; e.list_len = uo[4 * u + 2]; e.strand = u < plus ? 0 : 1;
+        p.used.push_back(e);
+      }
+      p.usedPtr[(size_t)re + 1] = (uint32_t)p.used.size();
+      const bool seeded = (int)len[re] >= a.k && (int)len[re] <= T1K_MAX_READ_LEN && !(a.reads.skip && skip[re]);
+      if (seeded) std::copy_n(&masks[(size_t)re * MW], MW, &p.masks[(size_t)re * MW]);
+    }
+  }
+  ctx->seedRep.passValid = true;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The chain of one range as ONE submission (round 5).  Rounds 1-4 fetched the counter block six times per range -- after seeding, after
 // the closed-form pass, after the gap walk, twice inside the multi-diagonal path, at the end -- because every consumer's grid and item
 // count were launch arguments.  Here every consumer reads its item count on the device (the total word k_arena_compact leaves where it
@@ -1624,6 +1670,11 @@ int t1k_run_chain(t1k_ctx *ctx, const ChainArgs &aIn, int nWg, int bigBlocks, bo
     const int ar[] = {T1K_AR_GROUPS, T1K_AR_SLOW, T1K_AR_JOBS, T1K_AR_RETRY, T1K_AR_GENERAL, T1K_AR_WAVE, T1K_AR_GENJOBS, T1K_AR_BIG};
     for (int i = 0; i < 8; ++i) t1k_arena_estimate_set(ctx, ar[i], cs[i]->total, nRe);
     ctx->estValid = true;
+  }
+  if (ctx->seedRep.on) {  // (opt-in, and whether or not the range has a multi-diagonal group)
+    ctx->seedRep.passValid = false;
+    if (!hc[T1K_CTR_ERR])
+      if (const int rc = seedCollect(ctx, a)) return rc;
   }
   if (ctx->route.on) {  // (opt-in: nothing above depends on it)
     ctx->route.passRecs.clear();

@@ -1017,6 +1017,9 @@ struct t1k_ctx {
   bool estValid = false;
   // route report (t1k_route_report_enable): `pass` is what the running pass of a range has collected, moved to `kept` when the range ends well
   struct { bool on = false; t1k_route_totals kept{}; std::vector<t1k_route_rec> keptRecs, passRecs; bool passLong = false, passXlong = false; } route;
+  // seed report (t1k_seed_report_enable): the same life cycle; a range's record is indexed by read-end inside the range
+  struct SeedRange { uint64_t first = 0; uint32_t count = 0; std::vector<uint32_t> counts, masks, usedPtr; std::vector<t1k_seed_used> used; };
+  struct { bool on = false, passValid = false; SeedRange pass; std::vector<SeedRange> kept; } seedRep;
   uint64_t pairEpoch = 0;      // epochs handed out to k_pair's allele tables since they were last cleared
   uint64_t pairBigCap = 0;     // entries of k_pair's big arena (scratch of the fragments whose lists exceed a workgroup's own)
   unsigned long long *countersPinned = nullptr;  // page-locked landing buffer of t1k_fetch_counters

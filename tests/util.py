@@ -18,6 +18,7 @@ ORACLE_EXTRACT = os.path.join(ROOT, "oracle", "t1k_oracle_extract")
 REF_EXTRACT = os.path.join(ROOT, "oracle", "_ref", "fastq-extractor")
 REF_ANALYZER = os.path.join(ROOT, "oracle", "_ref", "analyzer")
 REF_READS = os.path.join(ROOT, "oracle", "_ref", "reads_harness")
+REF_SEED = os.path.join(ROOT, "oracle", "_ref", "seed_harness")
 CYP_RNA = os.path.join(GOLDEN, "cyp2d6_rna_seq.fa.gz")
 CYP_DNA = os.path.join(GOLDEN, "cyp2d6_dna_seq.fa.gz")
 CYP_FLAGS = ["--alleleDigitUnits", "1", "--alleleDelimiter", "."]
@@ -121,8 +122,30 @@ def gunzip_to(src, dst):
     return dst
 
 
+def _seed_used(L, h, read, cap=4096):
+    """orc_seed_used: ([(strand, read offset, list length)] in the order the hits were made, lookups, postings) of one read"""
+    L.orc_seed_used.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    st, off, ln = (np.zeros(cap, np.int32) for _ in range(3))
+    lk, po = C.c_ulonglong(), C.c_ulonglong()
+    n = L.orc_seed_used(h, read.encode(), st.ctypes.data, off.ctypes.data, ln.ctypes.data, cap, C.byref(lk), C.byref(po))
+    assert n <= cap
+    return list(zip(st[:n].tolist(), off[:n].tolist(), ln[:n].tolist())), lk.value, po.value
+
+
+def _kmer_len(L, h, kmer):
+    """length of the posting list of one k-mer (ACGT only) in the oracle's index"""
+    L.orc_kmer_postings.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int]
+    return L.orc_kmer_postings(h, kmer.encode(), None, 0)
+
+
 class Oracle:
     """ctypes view of oracle/libt1k_oracle.so (CPU restatement) -- the checker, never the thing under test."""
+
+    def seed_used(self, read):
+        return _seed_used(self.L, self.h, read)
+
+    def kmer_len(self, kmer):
+        return _kmer_len(self.L, self.h, kmer)
 
     def __init__(self, fasta, similarity=0.8, relax=False, max_assign=2000, digit_units=-1, delimiter=b"\0"):
         L = C.CDLL(ORACLE_SO)
@@ -237,6 +260,12 @@ class ExtractOracle:
         self.inferred_k = L.orc_infer_kmer_length(self.h)
         self.k = max(9, self.inferred_k) if k is None else k  # FastqExtractor.cpp:409-416
         L.orc_set_extract_params(self.h, self.k, max(hit_len_required, self.k) if k is None else hit_len_required)
+
+    def seed_used(self, read):
+        return _seed_used(self.L, self.h, read)
+
+    def kmer_len(self, kmer):
+        return _kmer_len(self.L, self.h, kmer)
 
     def low_complexity(self, read):
         return bool(self.L.orc_is_low_complexity(read.encode()))
