@@ -12,6 +12,8 @@
  *   (2) whole-stage job API   t1k_job_*  (host C++ around (1): FASTA/FASTQ parsing, packing, group coalescing,
  *                             equivalence classes, allele selection, TSV writers) and t1k_genotyper_main(), the
  *                             argv-compatible replacement of the reference's genotyper main() (Genotyper.cpp:194-738).
+ *   (3) diagnostics and tests t1k_route_report_* / t1k_seed_report_* (what a range's kernels decided) and t1k_ref_view_* (the reference
+ *                             index as t1k_ref_upload built it, read back slice by slice); none of them changes what a run computes
  */
 #ifndef T1K_GPU_H
 #define T1K_GPU_H
@@ -74,7 +76,9 @@ int t1k_device_memory(int device, uint64_t *freeBytes, uint64_t *totalBytes); /*
 /* ---- reference: SeqSet::InputRefSeq + KmerIndex::BuildIndexFromRead (SeqSet.hpp:906-982, KmerIndex.hpp:107-130) --
  * seqs: nAlleles sequences concatenated as ASCII (ACGT, anything else is treated as N); offsets[nAlleles+1] byte offsets;
  * exon: one byte per base, non-zero = exon position (_validDiff::exon, SeqSet.hpp:638-723).  Packs to 2-bit + masks,
- * builds the direct-address 4^k index (postings in (allele, offset) order with the reference's insert rule). */
+ * builds the direct-address 4^k index (postings in (allele, offset) order with the reference's insert rule).  The context's earlier
+ * reference is released first: after an upload that fails (other than on a NULL pointer, the allele count or the total size) the context
+ * holds no reference, and the calls that need one say so. */
 int t1k_ref_upload(t1k_ctx *ctx, const char *seqs, const uint64_t *offsets, const uint8_t *exon, uint32_t nAlleles);
 
 /* ---- reads: one batch of read-ends resident in HBM -------------------------------------------------------------
@@ -647,6 +651,34 @@ typedef struct {
 } t1k_seed_used;
 int t1k_seed_report_enable(t1k_ctx *ctx, int on);
 int t1k_seed_report_get(t1k_ctx *ctx, uint8_t *seen, uint32_t *counts, uint32_t *masks, t1k_seed_used *used, uint64_t cap, uint64_t *nUsed);
+
+/* ---- reference view: the arrays t1k_ref_upload built, read back (diagnostics and tests) ----------------------------
+ * Host side only: no kernel is launched and nothing in the context changes, so with the view unused t1k_ref_upload issues exactly the
+ * launches and copies it issues without it.  Works on a context that uploaded its reference and on one that took it through
+ * t1k_ref_share.  T1K_ERR_ARG when the context holds no reference.
+ * t1k_ref_view_geometry: the sizes.  len[x] = elements of array x that the build defines (not the slack the kernels may fetch behind
+ * them), elem_bytes[x] = bytes of one element:
+ *   BASES / NMASK / EXON / POSTED   n_words 64-bit words, 32 positions a word, position q of a word in bits 2q (and 2q + 1 of BASES)
+ *   BASES_T                         the transposed copy and the 512 zero words behind it; 0 when it was not built (has_bases_t = 0)
+ *   BLOCK_T                         first word of every block of 64 alleles in BASES_T; 0 when it was not built
+ *   ALLELE_OFF (u64) / ALLELE_LEN (u32) / ALLELE_HAS_N (u8)   one per allele;  SEP_START (u32) one more;  SEP_POS (i32) n_sep
+ *   K_START                         4^k + 1;  K_HAS / K_MULTI  4^k / 32 words (at least 1);  K_HAS_PRE  4^max(1, k - 2) / 32 words
+ *   K_DIR_IDX                       4^k;  K_DIR  dir_rows * dir_stride;  K_DIR_MASK (u64)  dir_rows * dir_mask_words
+ *   K_POST (allele u32, offset u32) / K_POST_ALLELE (u32)     n_postings
+ * t1k_ref_view_copy: elements [first, first + count) of one array to host memory (count * elem_bytes bytes); T1K_ERR_ARG for an unknown
+ * array or a slice that leaves it (count = 0 at first <= len is legal).  At k = 15 K_START alone is 4 GB: read the cells you need. */
+enum { T1K_REF_BASES = 0, T1K_REF_NMASK, T1K_REF_EXON, T1K_REF_POSTED, T1K_REF_BASES_T, T1K_REF_BLOCK_T, T1K_REF_ALLELE_OFF, T1K_REF_ALLELE_LEN,
+       T1K_REF_ALLELE_HAS_N, T1K_REF_SEP_START, T1K_REF_SEP_POS, T1K_REF_K_START, T1K_REF_K_HAS, T1K_REF_K_MULTI, T1K_REF_K_HAS_PRE,
+       T1K_REF_K_DIR_IDX, T1K_REF_K_DIR, T1K_REF_K_DIR_MASK, T1K_REF_K_POST, T1K_REF_K_POST_ALLELE, T1K_REF_ARRAYS };
+typedef struct {
+  uint32_t n_alleles, k;
+  uint64_t total_bases, n_words, n_postings, bases_t_len, n_sep;
+  uint32_t dir_rows, dir_stride, dir_mask_words, has_bases_t;
+  uint64_t len[T1K_REF_ARRAYS];
+  uint32_t elem_bytes[T1K_REF_ARRAYS];
+} t1k_ref_geometry;
+int t1k_ref_view_geometry(t1k_ctx *ctx, t1k_ref_geometry *out);
+int t1k_ref_view_copy(t1k_ctx *ctx, int array, uint64_t first, uint64_t count, void *out);
 
 /* wall time (ms) the context has spent allocating device memory and the bytes it asked for (diagnostics) */
 double t1k_alloc_ms(t1k_ctx *ctx, uint64_t *bytes);

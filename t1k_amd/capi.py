@@ -88,6 +88,19 @@ assert ROUTE_REC_DTYPE.itemsize == 20
 SEED_USED_DTYPE = np.dtype([("read_off", "<u4"), ("list_len", "<u4"), ("strand", "u1"), ("reserved", "u1", (3,))])
 SEED_MASK_WORDS = 10
 assert SEED_USED_DTYPE.itemsize == 12
+# t1k_ref_view_*: the arrays of the reference index in the order of the T1K_REF_* enum, with the dtype of one element
+POSTING_DTYPE = np.dtype([("allele", "<u4"), ("offset", "<u4")])
+REF_ARRAYS = (("bases", "<u8"), ("nmask", "<u8"), ("exon", "<u8"), ("posted", "<u8"), ("basesT", "<u8"), ("blockT", "<u4"), ("alleleOff", "<u8"), ("alleleLen", "<u4"),
+              ("alleleHasN", "u1"), ("sepStart", "<u4"), ("sepPos", "<i4"), ("kStart", "<u4"), ("kHas", "<u4"), ("kMulti", "<u4"), ("kHasPre", "<u4"), ("kDirIdx", "<u4"),
+              ("kDir", "<u4"), ("kDirMask", "<u8"), ("kPost", POSTING_DTYPE), ("kPostAllele", "<u4"))
+
+
+class RefGeometry(C.Structure):  # t1k_ref_geometry
+    _fields_ = [("n_alleles", C.c_uint32), ("k", C.c_uint32), ("total_bases", C.c_uint64), ("n_words", C.c_uint64), ("n_postings", C.c_uint64),
+                ("bases_t_len", C.c_uint64), ("n_sep", C.c_uint64), ("dir_rows", C.c_uint32), ("dir_stride", C.c_uint32), ("dir_mask_words", C.c_uint32),
+                ("has_bases_t", C.c_uint32), ("len", C.c_uint64 * len(REF_ARRAYS)), ("elem_bytes", C.c_uint32 * len(REF_ARRAYS))]
+
+
 CIGAR_FILL = 0xAB  # what Context.cigar_batch fills its output arrays with before the call
 ALT_FILL = 0xCD    # what Context.alt_batch fills its tables with before the call
 ALT_EMPTY = 0xFFFFFFFF  # slotOf of an allele that is not called
@@ -179,6 +192,8 @@ def lib():
     L.t1k_route_report_get.argtypes = [vp, vp, vp, C.c_uint64, u64p]
     L.t1k_seed_report_enable.argtypes = [vp, C.c_int]
     L.t1k_seed_report_get.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
+    L.t1k_ref_view_geometry.argtypes = [vp, vp]
+    L.t1k_ref_view_copy.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp]
     L.t1k_genotyper_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.t1k_job_params_default.argtypes = [C.POINTER(JobParams)]
     L.t1k_job_create.argtypes = [C.POINTER(JobParams), C.c_char_p, C.POINTER(vp)]
@@ -487,6 +502,24 @@ class Context:
         np.cumsum(counts.sum(axis=1, dtype=np.int64), out=ptr[1:])
         assert int(ptr[-1]) == len(used)
         return seen, counts, masks, ptr, used
+
+    def ref_geometry(self):
+        """the sizes of the reference index (t1k_ref_view_geometry) as a dict; "len" maps every name of REF_ARRAYS to its element count"""
+        g = RefGeometry()
+        self._check(lib().t1k_ref_view_geometry(self.h, C.byref(g)), "t1k_ref_view_geometry")
+        out = {f: int(getattr(g, f)) for f, _ in RefGeometry._fields_[:11]}
+        out["len"] = {name: int(g.len[i]) for i, (name, _) in enumerate(REF_ARRAYS)}
+        assert all(g.elem_bytes[i] == np.dtype(t).itemsize for i, (_, t) in enumerate(REF_ARRAYS))
+        return out
+
+    def ref_array(self, name, first=0, count=None):
+        """elements [first, first + count) of one array of the reference index (t1k_ref_view_copy); count None: up to the array's end"""
+        i = [n for n, _ in REF_ARRAYS].index(name)
+        if count is None:
+            count = self.ref_geometry()["len"][name] - first
+        out = np.zeros(max(count, 0), REF_ARRAYS[i][1])
+        self._check(lib().t1k_ref_view_copy(self.h, i, first, count, _ptr(out)), "t1k_ref_view_copy")
+        return out
 
     def align_batch(self, texts, pats, want_ops=True):
         n = len(texts)

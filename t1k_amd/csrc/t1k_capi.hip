@@ -396,6 +396,7 @@ int t1k_ref_share(t1k_ctx *dst, const t1k_ctx *src) {
   dst->ref = src->ref;  // read-only arrays are aliased; they stay owned by src, which must outlive dst
   dst->hAlleleOff = src->hAlleleOff;
   dst->hAlleleLen = src->hAlleleLen;
+  dst->refSizes = src->refSizes;
   T1kDevBuf cov;  // the coverage difference array is per context
   int rc;
   if ((rc = t1k_ensure(dst, cov, 3 * src->ref.covStride * sizeof(int32_t)))) return rc;
@@ -1275,6 +1276,58 @@ int t1k_seed_report_get(t1k_ctx *ctx, uint8_t *seen, uint32_t *counts, uint32_t 
     if (used) std::copy(k.used.begin() + k.usedPtr[j], k.used.begin() + k.usedPtr[j + 1], used + at);
     at += k.usedPtr[j + 1] - k.usedPtr[j];
   }
+  return T1K_OK;
+}
+
+// Reference view: the resident arrays of ctx->ref, their lengths as t1k_ref_upload defined them
+static void refViewArrays(const t1k_ctx *ctx, const void *ptr[T1K_REF_ARRAYS], uint64_t len[T1K_REF_ARRAYS], uint32_t bytes[T1K_REF_ARRAYS]) {
+  const T1kRefDev &r = ctx->ref;
+  const auto &z = ctx->refSizes;
+  const int k = ctx->prm.kmer_length;
+  const uint64_t nKeys = 1ull << (2 * k), nPre = 1ull << (2 * std::max(1, k - 2)), A = r.nAlleles;
+  auto set = [&](int x, const void *p, uint64_t n, uint32_t b) { ptr[x] = p; len[x] = n; bytes[x] = b; };
+  set(T1K_REF_BASES, r.bases, z.nWords, 8); set(T1K_REF_NMASK, r.nmask, z.nWords, 8); set(T1K_REF_EXON, r.exon, z.nWords, 8); set(T1K_REF_POSTED, r.posted, z.nWords, 8);
+  set(T1K_REF_BASES_T, r.basesT, r.basesT ? z.basesTLen : 0, 8); set(T1K_REF_BLOCK_T, r.blockT, r.basesT ? z.nBlocksT : 0, 4);
+  set(T1K_REF_ALLELE_OFF, r.alleleOff, A, 8); set(T1K_REF_ALLELE_LEN, r.alleleLen, A, 4); set(T1K_REF_ALLELE_HAS_N, r.alleleHasN, A, 1);
+  set(T1K_REF_SEP_START, r.sepStart, A + 1, 4); set(T1K_REF_SEP_POS, r.sepPos, z.nSep, 4);
+  set(T1K_REF_K_START, r.kStart, nKeys + 1, 4); set(T1K_REF_K_HAS, r.kHas, (nKeys + 31) / 32, 4); set(T1K_REF_K_MULTI, r.kMulti, (nKeys + 31) / 32, 4);
+  set(T1K_REF_K_HAS_PRE, r.kHasPre, (nPre + 31) / 32, 4);
+  set(T1K_REF_K_DIR_IDX, r.kDirIdx, nKeys, 4); set(T1K_REF_K_DIR, r.kDir, (uint64_t)z.dirRows * r.kDirStride, 4);
+  set(T1K_REF_K_DIR_MASK, r.kDirMask, (uint64_t)z.dirRows * r.kDirMaskWords, 8);
+  set(T1K_REF_K_POST, r.kPost, z.nPost, (uint32_t)sizeof(T1kPosting)); set(T1K_REF_K_POST_ALLELE, r.kPostAllele, z.nPost, 4);
+}
+
+int t1k_ref_view_geometry(t1k_ctx *ctx, t1k_ref_geometry *out) {
+  if (!ctx || !out) return T1K_ERR_ARG;
+  if (!ctx->ref.bases) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_ref_view_geometry: no reference uploaded");
+  const void *ptr[T1K_REF_ARRAYS];
+  t1k_ref_geometry g{};
+  refViewArrays(ctx, ptr, g.len, g.elem_bytes);
+  g.n_alleles = ctx->ref.nAlleles; g.k = (uint32_t)ctx->prm.kmer_length;
+  g.total_bases = ctx->ref.totalBases; g.n_words = ctx->refSizes.nWords; g.n_postings = ctx->refSizes.nPost;
+  g.bases_t_len = g.len[T1K_REF_BASES_T]; g.n_sep = ctx->refSizes.nSep;
+  g.dir_rows = ctx->refSizes.dirRows; g.dir_stride = ctx->ref.kDirStride; g.dir_mask_words = ctx->ref.kDirMaskWords;
+  g.has_bases_t = ctx->ref.basesT ? 1u : 0u;
+  *out = g;
+  return T1K_OK;
+}
+
+int t1k_ref_view_copy(t1k_ctx *ctx, int array, uint64_t first, uint64_t count, void *out) {
+  if (!ctx) return T1K_ERR_ARG;
+  if (!ctx->ref.bases) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_ref_view_copy: no reference uploaded");
+  if (array < 0 || array >= T1K_REF_ARRAYS) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_ref_view_copy: no array " + std::to_string(array));
+  const void *ptr[T1K_REF_ARRAYS];
+  uint64_t len[T1K_REF_ARRAYS];
+  uint32_t bytes[T1K_REF_ARRAYS];
+  refViewArrays(ctx, ptr, len, bytes);
+  if (first > len[array] || count > len[array] - first)
+    return t1k_fail(ctx, T1K_ERR_ARG, "t1k_ref_view_copy: array " + std::to_string(array) + " holds " + std::to_string(len[array]) + " elements, asked for [" +
+                                          std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ")");
+  if (!count) return T1K_OK;
+  if (!out) return t1k_fail(ctx, T1K_ERR_ARG, "t1k_ref_view_copy: no room given");
+  T1K_HIP(ctx, hipSetDevice(ctx->device));
+  T1K_HIP(ctx, hipMemcpyAsync(out, (const char *)ptr[array] + first * bytes[array], count * bytes[array], hipMemcpyDeviceToHost, ctx->stream));
+  T1K_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return T1K_OK;
 }
 

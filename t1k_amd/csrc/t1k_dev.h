@@ -958,6 +958,8 @@ struct t1k_ctx {
   std::vector<uint64_t> hAlleleOff;
   std::vector<uint32_t> hAlleleLen;
   std::vector<T1kDevBuf> refBufs;
+  // sizes of the arrays of `ref` that the struct itself does not carry (host side, for t1k_ref_view_*; copied by t1k_ref_share)
+  struct RefSizes { uint64_t nWords = 0, nPost = 0, basesTLen = 0, nSep = 0; uint32_t dirRows = 0, nBlocksT = 0; } refSizes;
   // reads
   T1kReadsDev reads{};
   T1kDevBuf bReadAscii, bReadOffs, bReadBases, bReadN, bReadLen, bReadWeight, bListPtr, bListCount;

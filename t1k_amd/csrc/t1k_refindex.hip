@@ -188,6 +188,8 @@ extern "C" int t1k_ref_upload(t1k_ctx *ctx, const char *seqs, const uint64_t *of
   (void)hipStreamSynchronize(st);
   for (auto &b : ctx->refBufs) if (b.p) (void)t1k_dev_free(b.p);
   ctx->refBufs.clear();
+  ctx->ref = T1kRefDev{};  // an upload that fails from here on leaves NO reference: nothing may read the freed arrays through the old pointers
+  ctx->refSizes = t1k_ctx::RefSizes{};
   const int k = ctx->prm.kmer_length;
   const int nCode = ctx->prm.n_base_code & 3;
   const bool dbgPhases = getenv("T1K_DEBUG_PHASES") != nullptr;
@@ -219,6 +221,7 @@ extern "C" int t1k_ref_upload(t1k_ctx *ctx, const char *seqs, const uint64_t *of
   std::vector<uint32_t> sepStart(nAlleles + 1, 0);
   std::vector<uint8_t> alleleHasN(nAlleles, 0);
   std::vector<int32_t> sepPos;
+  t1k_ctx::RefSizes sizes;  // for t1k_ref_view_*
   {
     const unsigned T = std::max(1u, std::min({16u, std::thread::hardware_concurrency(), nAlleles}));
     std::vector<std::vector<int32_t>> part(T);
@@ -236,6 +239,7 @@ extern "C" int t1k_ref_upload(t1k_ctx *ctx, const char *seqs, const uint64_t *of
     for (auto &x : th) x.join();
     for (uint32_t a = 0; a < nAlleles; ++a) sepStart[a + 1] = sepStart[a] + cnt[a];
     for (auto &p : part) sepPos.insert(sepPos.end(), p.begin(), p.end());
+    sizes.nSep = sepPos.size();
     if (sepPos.empty()) sepPos.push_back(0);
   }
   lap("layout + separator scan (host)");
@@ -293,6 +297,7 @@ extern "C" int t1k_ref_upload(t1k_ctx *ctx, const char *seqs, const uint64_t *of
       hipLaunchKernelGGL(k_ref_transpose, dim3((unsigned)((totalT + 255) / 256)), dim3(256), 0, st, (const uint64_t *)dBases, (const uint64_t *)dAlleleOff, (const uint32_t *)dAlleleLen,
                          (const uint32_t *)dBlockT, nBlocks, nAlleles, totalT, (uint64_t *)dBasesT);
       RU_HIP(hipStreamSynchronize(st));  // (blockT is a local: the copy must have left it)
+      sizes.basesTLen = totalT + 512; sizes.nBlocksT = nBlocks;
     }
   }
   lap("text upload + pack");
@@ -376,6 +381,8 @@ extern "C" int t1k_ref_upload(t1k_ctx *ctx, const char *seqs, const uint64_t *of
   r.kPost = (const T1kPosting *)dPost; r.kPostAllele = (const uint32_t *)dPostAllele;
   r.covDiff = (int32_t *)dCov;
   ctx->ref = r;
+  sizes.nWords = nWords; sizes.nPost = M; sizes.dirRows = rows;
+  ctx->refSizes = sizes;
   ctx->covFullLen = 0; ctx->covFullDirty = false;
   lap("bucket starts + bitmaps + directory + coverage arrays");
   return T1K_OK;

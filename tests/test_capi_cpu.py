@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol(built):
     L = C.CDLL(t1k_amd.lib_path())
     names = declared_symbols()
     assert len(names) >= 30
-    assert {"t1k_route_report_enable", "t1k_route_report_get", "t1k_seed_report_enable", "t1k_seed_report_get"} <= set(names)
+    assert {"t1k_route_report_enable", "t1k_route_report_get", "t1k_seed_report_enable", "t1k_seed_report_get", "t1k_ref_view_geometry", "t1k_ref_view_copy"} <= set(names)
     for n in names:
         assert hasattr(L, n), "missing export " + n
     t1k_amd.lib()  # argtypes binding resolves every function it names

@@ -19,6 +19,7 @@ REF_EXTRACT = os.path.join(ROOT, "oracle", "_ref", "fastq-extractor")
 REF_ANALYZER = os.path.join(ROOT, "oracle", "_ref", "analyzer")
 REF_READS = os.path.join(ROOT, "oracle", "_ref", "reads_harness")
 REF_SEED = os.path.join(ROOT, "oracle", "_ref", "seed_harness")
+REF_INDEX = os.path.join(ROOT, "oracle", "_ref", "index_harness")
 CYP_RNA = os.path.join(GOLDEN, "cyp2d6_rna_seq.fa.gz")
 CYP_DNA = os.path.join(GOLDEN, "cyp2d6_dna_seq.fa.gz")
 CYP_FLAGS = ["--alleleDigitUnits", "1", "--alleleDelimiter", "."]
