@@ -332,6 +332,36 @@ int t1k_em_update(t1k_ctx *ctx, const double *x0, double *x1, double *ecReadCoun
 /* TEST-ONLY: the step sizes of t1k_em_update's ordered sums: out[0] = entries per ordered piece (a read group's row and a class are added
  * one piece at a time, the sum carried from piece to piece), out[1] = entries per step of the class pass (the unit of its prefetches). */
 void t1k_em_limits(uint32_t out[2]);
+/* Replaces count[nGroups] of the structure t1k_em_setup left on the context (host pointer); nothing else of it changes.  The serial
+ * bootstrap (T1K_BOOTSTRAP_SERIAL=1) runs every replicate through this and t1k_em_update. */
+int t1k_em_set_count(t1k_ctx *ctx, const double *count);
+
+/* ---- bootstrap of the EM (genotyper --bootstrap; no counterpart in the reference) ------------------------------------------
+ * Poisson bootstrap of the read groups of the structure t1k_em_setup left on the context, which is read in place and not changed.  Replicate
+ * r = 0 .. nReplicates; replicate 0 is the data.  Group g of count c_g has n_g = max(1, llrint(c_g)) draws: k[g][r] = sum over i < n_g of
+ * X(u(seed, r, g, i)), X the Poisson(1) draw of a 64-bit hash (DESIGN §16 gives u and the thresholds of X), and the replicate's count is
+ * c'[g][r] = c_g * (double)k / (double)n_g (k = n_g for replicate 0, and for every replicate when identity != 0).  Integer arithmetic only:
+ * the same k on every run.  Counts must lie in 0 .. 2^27 (T1K_ERR_CAPACITY).
+ * Every per-replicate array of these calls is replicate-minor with stride Rpad = t1k_boot_stride(nReplicates), the replicates padded to a
+ * multiple of 64: element (i, r) at [i * Rpad + r].  Padding replicates (r > nReplicates) have k = 0 and may not be active.
+ *   t1k_boot_begin     draws k and c' on the device and keeps them there until t1k_boot_end (or the next t1k_boot_begin)
+ *   t1k_boot_nonempty  nonEmpty[Rpad]: 1 where some c'[g][r] is not 0 (an EM of a replicate without counts has nothing to estimate)
+ *   t1k_boot_counts    TEST-ONLY (and the serial bootstrap): k[nGroups][Rpad], count[nGroups][Rpad]; either may be NULL
+ *   t1k_boot_update    one EMupdate of every replicate with active[r] != 0, as t1k_em_update on c'[.][r]: x0, x1, ecReadCount are
+ *                      [nEc][Rpad], diff is [Rpad] (host pointers; x1 may not overlap x0).  Bit for bit the doubles t1k_em_update gives
+ *                      with c'[.][r] as the counts.  Nothing of an inactive replicate is written, on the device or in the caller's arrays;
+ *                      a block of 64 replicates without an active one costs nothing
+ *   t1k_boot_limits    TEST-ONLY: out[0] = entries whose operands the row and class passes request ahead of their additions, out[1] = the
+ *                      n_g from which the lanes of a wavefront share a replicate's draws, out[2] = replicates per block
+ *   t1k_boot_times     device ms of the row passes, of the class passes, and the updates run since t1k_boot_begin */
+int t1k_boot_begin(t1k_ctx *ctx, uint32_t nReplicates /* 1 .. 1000 */, uint64_t seed, int identity);
+uint32_t t1k_boot_stride(uint32_t nReplicates);
+int t1k_boot_nonempty(t1k_ctx *ctx, uint8_t *nonEmpty);
+int t1k_boot_counts(t1k_ctx *ctx, uint32_t *k, double *count);
+int t1k_boot_update(t1k_ctx *ctx, const uint8_t *active, const double *x0, double *x1, double *ecReadCount, double *diff);
+void t1k_boot_end(t1k_ctx *ctx);
+void t1k_boot_limits(uint32_t out[3]);
+void t1k_boot_times(const t1k_ctx *ctx, double ms3[3]);
 
 /* ---- per-barcode allele EM (analyzer --barcodeEM; no counterpart in the reference; estimator: DESIGN §11) ---------------------
  * One independent EM per barcode, the whole iteration loop in one launch.  Barcode b (of the slice [0, nBarcodes)):
@@ -708,6 +738,8 @@ typedef struct {
   int32_t device;                                                     /* GPU ordinal; -1 = host-only job (group bookkeeping only, cannot run) */
   int32_t output_read_assignment;                                     /* --outputReadAssignment */
   int32_t batch_fragments;                                            /* fragments per device batch (0 = default) */
+  uint64_t bootstrap_seed;                                            /* --bootstrapSeed (default 1) */
+  int32_t bootstrap;                                                  /* --bootstrap: replicates of the quantification, 1 .. 1000; 0 = no table */
   int32_t alternatives;                                               /* --alternatives: alternatives listed per called allele, 1 .. 1000; 0 = no table */
   int32_t diplotypes;                                                 /* --diplotypes: allele pairs listed per gene, 1 .. 1000; 0 = no table */
   int32_t diplo_candidates;                                           /* --diploCandidates: candidates per gene, 2 .. 2048 (default 512) */
@@ -750,7 +782,7 @@ int t1k_job_run(t1k_job *job);
 /* optional, before t1k_job_run: the *_aligned*.fa files (which only need the fragmentAssigned flags) are then written by background
  * threads while the classes are built and the EM runs; t1k_job_write_outputs with the same prefix waits for them */
 int t1k_job_set_output_prefix(t1k_job *job, const char *prefix);
-/* <prefix>_genotype.tsv, _allele.tsv, _aligned*.fa, (_assign.tsv) (Genotyper.cpp:653-718), (_alternatives.tsv: prm.alternatives > 0), (_diplotypes.tsv: prm.diplotypes > 0) */
+/* <prefix>_genotype.tsv, _allele.tsv, _aligned*.fa, (_assign.tsv) (Genotyper.cpp:653-718), (_alternatives.tsv: prm.alternatives > 0), (_diplotypes.tsv: prm.diplotypes > 0), (_bootstrap.tsv: prm.bootstrap > 0) */
 int t1k_job_write_outputs(t1k_job *job, const char *prefix);
 /* results in memory: one line per gene, same text as _genotype.tsv */
 int t1k_job_genotype_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
@@ -758,6 +790,18 @@ int t1k_job_genotype_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *neede
 int t1k_job_alternatives_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
 /* after t1k_job_run of a job with prm.diplotypes > 0 (the rank that writes the tables): the text of <prefix>_diplotypes.tsv */
 int t1k_job_diplotypes_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
+/* after t1k_job_run of a job with prm.bootstrap > 0 (the rank that writes the tables): the text of <prefix>_bootstrap.tsv */
+int t1k_job_bootstrap_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
+/* ... and what it was computed from: abundance[(B + 1)][nAlleles], row r the per-allele abundance replicate r ended with (row 0: the data,
+ * bit for bit the abundances of t1k_job_allele_table); rounds[B + 1]: SQUAREM rounds of each replicate's EM (0: none was run);
+ * valid[B + 1]: 0 for a replicate without counts or with an abundance that is not finite.  Any array may be NULL; the two sizes always come back. */
+int t1k_job_bootstrap_matrix(t1k_job *job, double *abundance, int32_t *rounds, uint8_t *valid, uint32_t *nReplicates, uint32_t *nAlleles);
+/* TEST-ONLY: what the job's EM ran on besides the read groups, per allele of the reference and in its order: ec[a], its equivalence class (-1: in no
+ * read group; a class's members in ascending order are its members in the EM's order), weight[a], the start weight, effLen[a] (a class's
+ * length is the smallest of its members'), series[a], its major allele as an index into t1k_job_series_names.  Any array may be NULL. */
+int t1k_job_em_alleles(t1k_job *job, int32_t *ec, int32_t *weight, int32_t *effLen, int32_t *series, uint32_t *nAlleles);
+/* the names of the series (major alleles, the unit _genotype.tsv names), one per line, in reference order */
+int t1k_job_series_names(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed);
 /* per allele of the job's reference, in its order: the gene (index into the lines of _genotype.tsv) and, after t1k_job_run, the abundance; either may be NULL */
 int t1k_job_allele_table(t1k_job *job, int32_t *gene, double *abundance, uint32_t *nAlleles);
 int t1k_job_counts(t1k_job *job, uint64_t *fragments, uint64_t *assignedFragments, uint64_t *groups, uint64_t *ecs, int32_t *emIterations);

@@ -31,8 +31,8 @@ class JobParams(C.Structure):
     _fields_ = [("dev", Params), ("filter_frac", C.c_double), ("filter_cov", C.c_double),
                 ("cross_gene_rate", C.c_double), ("squarem_min_alpha", C.c_double), ("allele_digit_units", C.c_int32),
                 ("allele_delimiter", C.c_char), ("threads", C.c_int32), ("device", C.c_int32),
-                ("output_read_assignment", C.c_int32), ("batch_fragments", C.c_int32), ("alternatives", C.c_int32),
-                ("diplotypes", C.c_int32), ("diplo_candidates", C.c_int32)]
+                ("output_read_assignment", C.c_int32), ("batch_fragments", C.c_int32), ("bootstrap_seed", C.c_uint64),
+                ("bootstrap", C.c_int32), ("alternatives", C.c_int32), ("diplotypes", C.c_int32), ("diplo_candidates", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -146,6 +146,23 @@ def lib():
     L.t1k_em_shard.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
     L.t1k_em_limits.argtypes = [vp]
     L.t1k_em_limits.restype = None
+    L.t1k_em_set_count.argtypes = [vp, vp]
+    L.t1k_boot_begin.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_int]
+    L.t1k_boot_stride.argtypes = [C.c_uint32]
+    L.t1k_boot_stride.restype = C.c_uint32
+    L.t1k_boot_nonempty.argtypes = [vp, vp]
+    L.t1k_boot_counts.argtypes = [vp, vp, vp]
+    L.t1k_boot_update.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.t1k_boot_end.argtypes = [vp]
+    L.t1k_boot_end.restype = None
+    L.t1k_boot_limits.argtypes = [vp]
+    L.t1k_boot_limits.restype = None
+    L.t1k_boot_times.argtypes = [vp, vp]
+    L.t1k_boot_times.restype = None
+    L.t1k_job_bootstrap_text.argtypes = [vp, C.c_char_p, C.c_uint64, u64p]
+    L.t1k_job_bootstrap_matrix.argtypes = [vp, vp, vp, vp, u32p, u32p]
+    L.t1k_job_em_alleles.argtypes = [vp, vp, vp, vp, vp, u32p]
+    L.t1k_job_series_names.argtypes = [vp, C.c_char_p, C.c_uint64, u64p]
     L.t1k_barcode_em.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int32, vp, vp, C.POINTER(C.c_double)]
     L.t1k_umi_collapse.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int32, vp, C.POINTER(C.c_uint32), vp, vp, vp, vp, vp, vp,
                                    C.POINTER(UmiStats)]
@@ -595,6 +612,59 @@ class Context:
         diff = C.c_double()
         self._check(lib().t1k_em_update(self.h, _ptr(x0), _ptr(x1), _ptr(n), C.byref(diff)), "t1k_em_update")
         return x1, n, diff.value
+
+    def em_set_count(self, count):
+        """replaces the counts of the structure em_setup left (t1k_em_set_count)"""
+        ct = np.ascontiguousarray(count, np.float64)
+        assert len(ct) == len(self._em_keep[2])
+        self._check(lib().t1k_em_set_count(self.h, _ptr(ct)), "t1k_em_set_count")
+
+    # bootstrap of the EM over the structure em_setup left (t1k_boot_*; DESIGN §16).  The library's arrays are replicate-minor with stride
+    # boot_stride(B); the binding hands out and takes replicate-major ones, [replicate][...], of the B + 1 real replicates.
+    def boot_begin(self, n_replicates, seed=1, identity=False, raw=False):
+        rc = lib().t1k_boot_begin(self.h, n_replicates, seed, 1 if identity else 0)
+        if raw:
+            return rc
+        self._check(rc, "t1k_boot_begin")
+        self._boot_reps, self._boot_stride = n_replicates + 1, boot_stride(n_replicates)
+
+    def boot_nonempty(self):
+        """[B + 1] bool: the replicate has a count that is not 0"""
+        out = np.zeros(self._boot_stride, np.uint8)
+        self._check(lib().t1k_boot_nonempty(self.h, _ptr(out)), "t1k_boot_nonempty")
+        assert not out[self._boot_reps:].any()
+        return out[:self._boot_reps].astype(bool)
+
+    def boot_counts(self):
+        """(k uint32 [B + 1][G], c' float64 [B + 1][G]); the padding replicates must be empty"""
+        G = len(self._em_keep[2])
+        k, c = np.zeros((G, self._boot_stride), np.uint32), np.zeros((G, self._boot_stride), np.float64)
+        self._check(lib().t1k_boot_counts(self.h, _ptr(k), _ptr(c)), "t1k_boot_counts")
+        assert not k[:, self._boot_reps:].any() and not c[:, self._boot_reps:].any()
+        return np.ascontiguousarray(k[:, :self._boot_reps].T), np.ascontiguousarray(c[:, :self._boot_reps].T)
+
+    def boot_update(self, active, x0, fill=None):
+        """one update of the replicates with active[r]: x0 [B + 1][E] -> (x1 [B + 1][E], n [B + 1][E], diff [B + 1]).  The output arrays
+        are filled with `fill` (default 0.0) before the call: what an inactive replicate's outputs must still hold after it"""
+        R, S, E = self._boot_reps, self._boot_stride, self._em_nec
+        act = np.zeros(S, np.uint8)
+        act[:R] = np.asarray(active, bool)
+        xin = np.zeros((E, S), np.float64)
+        xin[:, :R] = np.asarray(x0, np.float64).T
+        f = 0.0 if fill is None else fill
+        x1, n, diff = np.full((E, S), f, np.float64), np.full((E, S), f, np.float64), np.full(S, f, np.float64)
+        self._check(lib().t1k_boot_update(self.h, _ptr(act), _ptr(xin), _ptr(x1), _ptr(n), _ptr(diff)), "t1k_boot_update")
+        for a in (x1[:, R:], n[:, R:], diff[R:]):
+            assert (a == f).all() or (np.isnan(f) and np.isnan(a).all())
+        return np.ascontiguousarray(x1[:, :R].T), np.ascontiguousarray(n[:, :R].T), diff[:R].copy()
+
+    def boot_times(self):
+        out = np.zeros(3, np.float64)
+        lib().t1k_boot_times(self.h, _ptr(out))
+        return dict(rows_ms=out[0], cols_ms=out[1], updates=int(out[2]))
+
+    def boot_end(self):
+        lib().t1k_boot_end(self.h)
 
     def barcode_em(self, bc_allele_ptr, bc_allele, bc_group_ptr, group_count, group_entry_ptr, entry_local, rho, n_alleles, alpha=0.0, tol=1e-7,
                    max_iter=1000, raw=False):
@@ -1099,6 +1169,18 @@ class Rowset:
         return sizes, ent, first
 
 
+def boot_limits():
+    """(entries requested ahead of the additions, the n_g from which the lanes share a replicate's draws, replicates per block) of t1k_boot_* as built"""
+    out = np.zeros(3, np.uint32)
+    lib().t1k_boot_limits(_ptr(out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def boot_stride(n_replicates):
+    """the stride of the library's replicate-minor arrays: B + 1 replicates padded to whole blocks"""
+    return int(lib().t1k_boot_stride(n_replicates))
+
+
 def em_limits():
     """(entries per ordered piece, entries per step of the class pass) of t1k_em_update's sums as built"""
     out = np.zeros(2, dtype=np.uint32)
@@ -1310,6 +1392,37 @@ class Job:
         buf = C.create_string_buffer(need.value + 1)
         self._check(lib().t1k_job_diplotypes_text(self.h, buf, need.value + 1, C.byref(need)), "t1k_job_diplotypes_text")
         return buf.value.decode()
+
+    def bootstrap_text(self):
+        """the text of <prefix>_bootstrap.tsv (a job created with bootstrap=B, after run())"""
+        need = C.c_uint64()
+        self._check(lib().t1k_job_bootstrap_text(self.h, None, 0, C.byref(need)), "t1k_job_bootstrap_text")
+        buf = C.create_string_buffer(need.value + 1)
+        self._check(lib().t1k_job_bootstrap_text(self.h, buf, need.value + 1, C.byref(need)), "t1k_job_bootstrap_text")
+        return buf.value.decode()
+
+    def bootstrap_matrix(self):
+        """(abundance float64 [B + 1][A], rounds int32 [B + 1], valid bool [B + 1]) of the replicates 0 .. B (0: the data)"""
+        b, a = C.c_uint32(), C.c_uint32()
+        self._check(lib().t1k_job_bootstrap_matrix(self.h, None, None, None, C.byref(b), C.byref(a)), "t1k_job_bootstrap_matrix")
+        ab, rounds, valid = np.zeros((b.value + 1, a.value), np.float64), np.zeros(b.value + 1, np.int32), np.zeros(b.value + 1, np.uint8)
+        self._check(lib().t1k_job_bootstrap_matrix(self.h, _ptr(ab), _ptr(rounds), _ptr(valid), C.byref(b), C.byref(a)), "t1k_job_bootstrap_matrix")
+        return ab, rounds, valid.astype(bool)
+
+    def em_alleles(self):
+        """(ec, weight, eff_len, series: int32 [A] each) of the job's alleles: what its EM ran on besides the read groups (t1k_job_em_alleles)"""
+        n = C.c_uint32()
+        self._check(lib().t1k_job_em_alleles(self.h, None, None, None, None, C.byref(n)), "t1k_job_em_alleles")
+        out = [np.zeros(n.value, np.int32) for _ in range(4)]
+        self._check(lib().t1k_job_em_alleles(self.h, *[_ptr(a) for a in out], C.byref(n)), "t1k_job_em_alleles")
+        return tuple(out)
+
+    def series_names(self):
+        need = C.c_uint64()
+        self._check(lib().t1k_job_series_names(self.h, None, 0, C.byref(need)), "t1k_job_series_names")
+        buf = C.create_string_buffer(need.value + 1)
+        self._check(lib().t1k_job_series_names(self.h, buf, need.value + 1, C.byref(need)), "t1k_job_series_names")
+        return buf.value.decode().splitlines()
 
     def allele_table(self):
         """(gene int32 [A], abundance float64 [A]) of the job's alleles, in the order of its reference"""

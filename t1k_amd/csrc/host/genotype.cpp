@@ -279,38 +279,31 @@ int Genotyper::quantify(t1k_ctx *ctx, t1k_comm *comm, std::string &err) {
     x0[e] = 0;
     for (int a : ecAlleles[e]) x0[e] += R.al[a].weight;
   }
-  const int maxIterations = 1000, maskEvery = 10;
-  int rounds = 0;
   double diff = 0;
   auto em = [&](std::vector<double> &from, std::vector<double> &to) {
     if (E == 0) return true;
     if (t1k_em_update(ctx, from.data(), to.data(), n.data(), &diff) != T1K_OK) { err = t1k_last_error(ctx); return false; }
     return true;
   };
-  for (int t = 0; t < maxIterations; ++t) {
-    ++rounds;
+  EmRun run;
+  run.x0 = x0.data(); run.x1 = x1.data(); run.x2 = x2.data(); run.x3 = x3.data(); run.n = n.data();
+  const std::function<void(EmRun &)> mask = [&](EmRun &) {
+    setAbundance(n.data(), ecLen);
+    for (auto &a : R.al)
+      if (majorAbund[a.major] < prm.filter_frac * 0.5 * geneMaxMajor[a.gene]) { a.abundance = 0; a.ecAbundance = 0; }
+    for (size_t e = 0; e < E; ++e) x0[e] = R.al[ecAlleles[e][0]].ecAbundance;
+  };
+  while (!run.done) {
     if (!em(x0, x1) || !em(x1, x2)) return -1;
-    double r2 = 0, v2 = 0;  // SQUAREMalpha (424-437)
-    for (size_t e = 0; e < E; ++e) {
-      r2 += (x1[e] - x0[e]) * (x1[e] - x0[e]);
-      v2 += (x2[e] - 2 * x1[e] + x0[e]) * (x2[e] - 2 * x1[e] + x0[e]);
-    }
-    double alpha = v2 == 0 ? -1 : -sqrt(r2) / sqrt(v2);
-    if (prm.squarem_min_alpha < 0 && alpha < prm.squarem_min_alpha) alpha = prm.squarem_min_alpha;
-    for (size_t e = 0; e < E; ++e) x3[e] = x0[e] - 2 * alpha * (x1[e] - x0[e]) + alpha * alpha * (x2[e] - 2 * x1[e] + x0[e]);
+    emExtrapolate(run);
     if (!em(x3, x1)) return -1;
-    double moved = 0;
-    for (size_t e = 0; e < E; ++e) { moved += fabs(x1[e] - x0[e]); x0[e] = x1[e]; }
-    if (moved < 1e-5 && t < maxIterations - 2) t = maxIterations - 2;  // one forced extra round
-    if (t > 0 && t % maskEvery == 0) {
-      setAbundance(n.data(), ecLen);
-      for (auto &a : R.al)
-        if (majorAbund[a.major] < prm.filter_frac * 0.5 * geneMaxMajor[a.gene]) { a.abundance = 0; a.ecAbundance = 0; }
-      for (size_t e = 0; e < E; ++e) x0[e] = R.al[ecAlleles[e][0]].ecAbundance;
-    }
+    emCloseRound(run, mask);
   }
+  const int rounds = run.rounds;
   setAbundance(n.data(), ecLen);
   emIterations = rounds;
+  emEcLen = ecLen;
+  emCount = count;
   if (getenv("T1K_DEBUG_PHASES")) {
     double u[4];
     t1k_em_times(ctx, u);
@@ -318,6 +311,60 @@ int Genotyper::quantify(t1k_ctx *ctx, t1k_comm *comm, std::string &err) {
             tq1 - tq0, tq2 - tq1, ecIdx.size(), hostNowMs() - tq2, u[3], u[0], u[1], u[2]);
   }
   return rounds;
+}
+
+// the two host steps of a SQUAREM round (1234-1314), on one run's vectors
+void Genotyper::emExtrapolate(EmRun &run) const {
+  const size_t E = ecAlleles.size(), S = run.stride;
+  const double *x0 = run.x0, *x1 = run.x1, *x2 = run.x2;
+  double r2 = 0, v2 = 0;  // SQUAREMalpha (424-437)
+  for (size_t e = 0; e < E; ++e) {
+    r2 += (x1[e * S] - x0[e * S]) * (x1[e * S] - x0[e * S]);
+    v2 += (x2[e * S] - 2 * x1[e * S] + x0[e * S]) * (x2[e * S] - 2 * x1[e * S] + x0[e * S]);
+  }
+  double alpha = v2 == 0 ? -1 : -sqrt(r2) / sqrt(v2);
+  if (prm.squarem_min_alpha < 0 && alpha < prm.squarem_min_alpha) alpha = prm.squarem_min_alpha;
+  for (size_t e = 0; e < E; ++e) run.x3[e * S] = x0[e * S] - 2 * alpha * (x1[e * S] - x0[e * S]) + alpha * alpha * (x2[e * S] - 2 * x1[e * S] + x0[e * S]);
+}
+
+void Genotyper::emCloseRound(EmRun &run, const std::function<void(EmRun &)> &mask) const {
+  const int maxIterations = 1000, maskEvery = 10;
+  const size_t E = ecAlleles.size(), S = run.stride;
+  ++run.rounds;
+  double moved = 0;
+  for (size_t e = 0; e < E; ++e) { moved += fabs(run.x1[e * S] - run.x0[e * S]); run.x0[e * S] = run.x1[e * S]; }
+  if (moved < 1e-5 && run.t < maxIterations - 2) run.t = maxIterations - 2;  // one forced extra round
+  if (run.t > 0 && run.t % maskEvery == 0) mask(run);
+  ++run.t;
+  run.done = run.t >= maxIterations;
+}
+
+void Genotyper::abundanceInto(const double *n, size_t stride, Abundances &out) const {
+  const RefSet &R = *ref;
+  const size_t A = R.al.size();
+  out.abundance.assign(A, 0);
+  out.ecAbundance.assign(A, 0);
+  for (size_t e = 0; e < ecAlleles.size(); ++e) {
+    double fpk = 0;
+    fpk += n[e * stride];
+    fpk = fpk / emEcLen[e] * 1000.0;
+    const int size = (int)ecAlleles[e].size();
+    for (int a : ecAlleles[e]) { out.abundance[a] = fpk / size; out.ecAbundance[a] = fpk; }
+  }
+  out.major.assign(R.majorName.size(), 0);
+  out.geneMaxMajor.assign(R.geneName.size(), 0);
+  for (size_t a = 0; a < A; ++a) out.major[R.al[a].major] += out.abundance[a];
+  for (size_t a = 0; a < A; ++a)
+    if (out.major[R.al[a].major] > out.geneMaxMajor[R.al[a].gene]) out.geneMaxMajor[R.al[a].gene] = out.major[R.al[a].major];
+}
+
+void Genotyper::maskInto(EmRun &run) const {
+  const RefSet &R = *ref;
+  Abundances ab;
+  abundanceInto(run.n, run.stride, ab);
+  for (size_t a = 0; a < R.al.size(); ++a)
+    if (ab.major[R.al[a].major] < prm.filter_frac * 0.5 * ab.geneMaxMajor[R.al[a].gene]) { ab.abundance[a] = 0; ab.ecAbundance[a] = 0; }
+  for (size_t e = 0; e < ecAlleles.size(); ++e) run.x0[e * run.stride] = ab.ecAbundance[ecAlleles[e][0]];
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -989,6 +1036,115 @@ std::string Genotyper::diplotypeText(const DiploInput &in, const uint64_t *matri
     if (calledRank > shown) line(calledPair, calledRank, true);
   });
   for (size_t x = 0; x < nGenes; ++x) text += part[x];
+  return text;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// --bootstrap: the table.  Every statistic is a function of the replicates' per-allele abundances alone.
+// ------------------------------------------------------------------------------------------------------------------
+void Genotyper::calledSeries(int gene, std::vector<int> series[2]) const {
+  const RefSet &R = *ref;
+  std::vector<char> shown(R.majorName.size(), 0);  // as geneLine: a major allele is printed once
+  int firstQual = -1;
+  for (int type = 0; type < 2; ++type) {
+    series[type].clear();
+    if (type == 1 && firstQual == 0) std::fill(shown.begin(), shown.end(), 0);
+    int qual = -1;
+    for (auto &s : selected[gene]) {
+      if (s.second != type) continue;
+      const AlleleMeta &m = R.al[s.first];
+      if (shown[m.major]) continue;
+      qual = m.quality;
+      series[type].push_back(m.major);
+      shown[m.major] = 1;
+    }
+    if (qual < 0) series[type].clear();
+    if (type == 0) firstQual = qual;
+  }
+}
+
+std::string Genotyper::bootstrapText(const BootResult &boot) const {
+  const RefSet &R = *ref;
+  const size_t A = R.al.size(), M = R.majorName.size(), nGenes = R.geneName.size();
+  std::vector<int> geneOf(M, -1);
+  for (auto &a : R.al) geneOf[a.major] = a.gene;
+  std::vector<std::vector<int>> ofGene(nGenes);  // a gene's series in reference order
+  for (size_t m = 0; m < M; ++m)
+    if (geneOf[m] >= 0) ofGene[geneOf[m]].push_back((int)m);
+  std::vector<std::vector<double>> values(M);  // per series: its abundance in every valid replicate, in replicate order
+  std::vector<uint32_t> top1(M, 0), top2(M, 0), pass(M, 0);
+  size_t V = 0;
+  std::vector<double> major(M), geneMax(nGenes);
+  for (int r = 1; r <= boot.B; ++r) {
+    if (!boot.valid[r]) continue;
+    ++V;
+    const double *ab = boot.abundance.data() + (size_t)r * A;
+    std::fill(major.begin(), major.end(), 0.0);
+    std::fill(geneMax.begin(), geneMax.end(), 0.0);
+    for (size_t a = 0; a < A; ++a) major[R.al[a].major] += ab[a];  // (SetAlleleAbundance's sums)
+    for (size_t a = 0; a < A; ++a)
+      if (major[R.al[a].major] > geneMax[R.al[a].gene]) geneMax[R.al[a].gene] = major[R.al[a].major];
+    for (size_t m = 0; m < M; ++m) values[m].push_back(major[m]);
+    for (size_t g = 0; g < nGenes; ++g) {
+      int first = -1, second = -1;  // by abundance descending, ties by reference order; 0 never ranks
+      for (int m : ofGene[g]) {
+        if (!(major[m] > 0)) continue;
+        if (first < 0 || major[m] > major[first]) { second = first; first = m; }
+        else if (second < 0 || major[m] > major[second]) second = m;
+      }
+      if (first >= 0) { ++top1[first]; ++top2[first]; }
+      if (second >= 0) ++top2[second];
+      for (int m : ofGene[g])
+        if (major[m] > 0 && !(major[m] < prm.filter_frac * geneMax[g])) ++pass[m];
+    }
+  }
+  struct Stat { double mean = 0, sd = 0, q05 = 0, q50 = 0, q95 = 0; };
+  auto statOf = [&](int m) {
+    Stat s;
+    if (V == 0) return s;
+    const std::vector<double> &v = values[m];
+    double sum = 0;
+    for (double x : v) sum += x;
+    s.mean = sum / (double)V;
+    if (V >= 2) {
+      double ss = 0;
+      for (double x : v) { const double d = x - s.mean; ss += d * d; }
+      s.sd = sqrt(ss / (double)(V - 1));
+    }
+    std::vector<double> asc(v);
+    std::sort(asc.begin(), asc.end());
+    auto q = [&](size_t p) { const size_t k = (p * V + 99) / 100; return asc[k ? k - 1 : 0]; };  // nearest rank
+    s.q05 = q(5); s.q50 = q(50); s.q95 = q(95);
+    return s;
+  };
+  std::string text = "#gene\tseries\tcalled\tabundance\tmean\tsd\tq05\tq50\tq95\ttop1\ttop2\tpass\treplicates\n";
+  char num[2600];
+  for (size_t g = 0; g < nGenes; ++g) {
+    std::vector<int> slot[2];
+    calledSeries((int)g, slot);
+    std::vector<int> lines;
+    std::vector<char> in1(M, 0), in2(M, 0), listed(M, 0);
+    for (int m : slot[0]) in1[m] = 1;
+    for (int m : slot[1]) in2[m] = 1;
+    for (int k = 0; k < 2; ++k)
+      for (int m : slot[k])
+        if (!listed[m]) { listed[m] = 1; lines.push_back(m); }
+    struct Rest { int m; double mean; };
+    std::vector<Rest> rest;
+    for (int m : ofGene[g])
+      if (!listed[m] && top2[m] > 0) rest.push_back(Rest{m, statOf(m).mean});
+    std::sort(rest.begin(), rest.end(), [&](const Rest &x, const Rest &y) {
+      if (top2[x.m] != top2[y.m]) return top2[x.m] > top2[y.m];
+      if (x.mean != y.mean) return x.mean > y.mean;
+      return x.m < y.m;
+    });
+    for (const Rest &x : rest) lines.push_back(x.m);
+    for (int m : lines) {
+      const Stat s = statOf(m);
+      snprintf(num, sizeof num, "\t%.6f\t%.6f\t%.6f\t%.6f\t%.6f\t%.6f\t%u\t%u\t%u\t%zu\n", majorAbund[m], s.mean, s.sd, s.q05, s.q50, s.q95, top1[m], top2[m], pass[m], V);
+      text += R.geneName[g] + "\t" + R.majorName[m] + "\t" + (in1[m] && in2[m] ? "1,2" : in1[m] ? "1" : in2[m] ? "2" : ".") + num;
+    }
+  }
   return text;
 }
 

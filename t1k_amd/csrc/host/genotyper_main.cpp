@@ -1,6 +1,7 @@
 // t1k_amd/csrc/host/genotyper_main.cpp -- t1k_genotyper_main(): the argv-compatible replacement of the reference's genotyper executable
 // (Genotyper.cpp:194-738, invoked by run-t1k:430,434) on top of the job layer.
 #include "job_internal.h"
+#include <cerrno>
 
 extern "C" {
 
@@ -47,6 +48,8 @@ static const char *kUsage =
     "\t--alternatives [INT]: write prefix_alternatives.tsv, the INT closest other alleles of every called allele (default: 5; 1 to 1000)\n"
     "\t--diplotypes [INT]: write prefix_diplotypes.tsv, the INT allele pairs of every gene that explain most reads (default: 10; 1 to 1000)\n"
     "\t--diploCandidates INT: allele classes per gene that --diplotypes pairs up (default: 512; 2 to 2048)\n"
+    "\t--bootstrap [INT]: write prefix_bootstrap.tsv, the spread of every series' abundance over INT resampled quantifications (default: 100; 1 to 1000; not with -a)\n"
+    "\t--bootstrapSeed INT: seed of the resampling (default: 1)\n"
     "\t--squaremMinAlpha FLOAT: lower bound (negative) of the SQUAREM step length\n"
     "\t--device INT: GPU ordinal (default: $T1K_DEVICE or 0)\n"
     "\t--gpus INT: shard the fragments over the first INT GPUs ($T1K_GPUS=0,1,.. names them; a GPU may be named twice)\n";
@@ -60,6 +63,7 @@ int t1k_genotyper_main(int argc, char **argv) {
                                      {"alleleWhitelist", required_argument, 0, 1007}, {"outputReadAssignment", no_argument, 0, 1008},
                                      {"squaremMinAlpha", required_argument, 0, 1009}, {"device", required_argument, 0, 1010}, {"gpus", required_argument, 0, 1011},
                                      {"alternatives", optional_argument, 0, 1012}, {"diplotypes", optional_argument, 0, 1013}, {"diploCandidates", required_argument, 0, 1014},
+                                     {"bootstrap", optional_argument, 0, 1015}, {"bootstrapSeed", required_argument, 0, 1016},
                                      {0, 0, 0, 0}};
   t1k_job_params p;
   t1k_job_params_default(&p);
@@ -118,8 +122,29 @@ int t1k_genotyper_main(int argc, char **argv) {
         p.diplo_candidates = (int32_t)n;
         break;
       }
+      case 1015: {  // "--bootstrap", "--bootstrap=INT" or "--bootstrap INT", as --alternatives
+        const char *v = optarg;
+        if (!v && optind < argc && argv[optind][0] != '-') v = argv[optind++];
+        char *end = nullptr;
+        const long n = v ? strtol(v, &end, 10) : 100;
+        if (v && (end == v || *end || n < 1 || n > 1000)) { fprintf(stderr, "genotyper: --bootstrap takes an integer from 1 to 1000\n%s", kUsage); return EXIT_FAILURE; }
+        p.bootstrap = (int32_t)n;
+        break;
+      }
+      case 1016: {
+        char *end = nullptr;
+        errno = 0;
+        const unsigned long long n = strtoull(optarg, &end, 10);
+        if (end == optarg || *end || errno || optarg[0] == '-') { fprintf(stderr, "genotyper: --bootstrapSeed takes an unsigned 64-bit integer\n%s", kUsage); return EXIT_FAILURE; }
+        p.bootstrap_seed = (uint64_t)n;
+        break;
+      }
       default: fprintf(stderr, "%s", kUsage); return EXIT_FAILURE;
     }
+  }
+  if (p.bootstrap > 0 && !abundance.empty()) {
+    fprintf(stderr, "genotyper: --bootstrap resamples the EM, which -a skips: give one of the two\n%s", kUsage);
+    return EXIT_FAILURE;
   }
   if (refFile.empty()) { fprintf(stderr, "Need to use -f to specify the reference sequences.\n"); return EXIT_FAILURE; }
   if (p.dev.max_assign_cnt == 0) p.dev.max_assign_cnt = -1;  // "-n 0" disables the cap in the reference (maxAssignCnt > 0 test)

@@ -22,6 +22,8 @@ void t1k_job_params_default(t1k_job_params *p) {
   p->alternatives = 0;
   p->diplotypes = 0;
   p->diplo_candidates = 512;
+  p->bootstrap = 0;
+  p->bootstrap_seed = 1;
 }
 
 int t1k_job_create(const t1k_job_params *p, const char *refFasta, t1k_job **out) { return jobCreate(p, refFasta, nullptr, out); }

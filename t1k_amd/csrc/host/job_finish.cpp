@@ -50,6 +50,24 @@ static int jobDiplotypes(t1k_job *job) {
   return T1K_OK;
 }
 
+// --bootstrap: quantify's EM on resampled group counts, all replicates in one pass of t1k_boot_update per update (or one after
+// the other: T1K_BOOTSTRAP_SERIAL=1); the table is formatted once selection has made the calls
+static int jobBootstrap(t1k_job *job) {
+  Genotyper::BootResult &b = job->boot;
+  if (job->gt.bootstrap(job->ctx, job->prm.bootstrap, job->prm.bootstrap_seed, b, job->err) < 0) return T1K_ERR_DEVICE;
+  if (getenv("T1K_DEBUG_PHASES")) {
+    int valid = 0;
+    for (int r = 1; r <= b.B; ++r) valid += b.valid[r];
+    if (b.serial)
+      fprintf(stderr, "[t1k job] bootstrap: %d replicates (%d valid), %llu updates, kernel %.3f ms, total %.1f ms (serial: one replicate after the other)\n", b.B, valid,
+              (unsigned long long)b.updates, b.kernelMs, b.totalMs);
+    else
+      fprintf(stderr, "[t1k job] bootstrap: %d replicates (%d valid), %llu updates, kernel %.3f ms (row passes %.3f ms, class passes %.3f ms), total %.1f ms\n", b.B, valid,
+              (unsigned long long)b.updates, b.kernelMs, b.rowMs, b.colMs, b.totalMs);
+  }
+  return T1K_OK;
+}
+
 extern "C" {
 
 int t1k_job_finish(t1k_job *job) {
@@ -109,6 +127,12 @@ int t1k_job_finish(t1k_job *job) {
       return true;
     };
   }
+  job->boot = Genotyper::BootResult();
+  job->bootText.clear();
+  if (job->prm.bootstrap != 0) {
+    if (job->prm.bootstrap < 0 || job->prm.bootstrap > 1000) return jobFail(job, T1K_ERR_ARG, "bootstrap: 1 .. 1000 replicates");
+    if (!job->abundanceFile.empty()) return jobFail(job, T1K_ERR_ARG, "bootstrap: an abundance file skips the EM, so there is nothing to resample");
+  }
   gt.finalize(cov);
   double t3 = nowMs();
   if (!job->abundanceFile.empty()) {
@@ -117,6 +141,10 @@ int t1k_job_finish(t1k_job *job) {
     if (gt.quantify(job->ctx, job->comm, job->err) < 0) return T1K_ERR_DEVICE;
   }
   double t4 = nowMs();
+  if (job->prm.bootstrap > 0 && job->rank == 0) {  // the rank that writes the tables, over the merged groups and the whole structure: no exchange
+    if ((rc = jobBootstrap(job)) != T1K_OK) return rc;
+  }
+  const double t4a = nowMs();  // (the bootstrap's time is its own: neither the EM's nor the host stages')
   gt.dropUnlikely();
   double t4b = nowMs();
   gt.select();
@@ -134,12 +162,13 @@ int t1k_job_finish(t1k_job *job) {
     if (job->prm.diplo_candidates < 2 || job->prm.diplo_candidates > 2048) return jobFail(job, T1K_ERR_ARG, "diplo_candidates: 2 .. 2048 per gene");
     if ((rc = jobDiplotypes(job)) != T1K_OK) return rc;
   }
-  job->msHost += (t3 - t2) + (t5 - t4); job->msEm = t4 - t3;
+  if (job->prm.bootstrap > 0 && job->rank == 0) job->bootText = gt.bootstrapText(job->boot);  // (the calls are known now)
+  job->msHost += (t3 - t2) + (t5 - t4a); job->msEm = t4 - t3;
   job->stats.ms_total = job->msLoad + job->msDevice + job->msCoalesce + job->msHost + job->msEm;
   job->stats.ms_em = job->msEm;
   if (getenv("T1K_DEBUG_PHASES"))
     fprintf(stderr, "[t1k job] device+download %.1f ms, host coalesce+finalize %.1f ms, EM %.1f ms, dropUnlikely %.1f ms, select %.1f ms\n", job->msDevice,
-            job->msHost, t4 - t3, t4b - t4, t5 - t4b);
+            job->msHost, t4 - t3, t4b - t4a, t5 - t4b);
   job->ran = true;
   return T1K_OK;
 }
@@ -345,6 +374,51 @@ int t1k_job_diplotypes_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *nee
   if (!job || !job->ran) return jobFail(job, T1K_ERR_STATE, "the job has not run");
   if (job->prm.diplotypes <= 0 || job->rank != 0) return jobFail(job, T1K_ERR_STATE, "the job keeps no diplotypes table");
   const std::string &s = job->diploText;
+  if (needed) *needed = s.size();
+  if (buf && cap > s.size()) { memcpy(buf, s.data(), s.size()); buf[s.size()] = 0; }
+  else if (buf) return T1K_ERR_ARG;
+  return T1K_OK;
+}
+
+int t1k_job_bootstrap_text(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed) {
+  if (!job || !job->ran) return jobFail(job, T1K_ERR_STATE, "the job has not run");
+  if (job->prm.bootstrap <= 0 || job->rank != 0) return jobFail(job, T1K_ERR_STATE, "the job keeps no bootstrap table");
+  const std::string &s = job->bootText;
+  if (needed) *needed = s.size();
+  if (buf && cap > s.size()) { memcpy(buf, s.data(), s.size()); buf[s.size()] = 0; }
+  else if (buf) return T1K_ERR_ARG;
+  return T1K_OK;
+}
+
+int t1k_job_bootstrap_matrix(t1k_job *job, double *abundance, int32_t *rounds, uint8_t *valid, uint32_t *nReplicates, uint32_t *nAlleles) {
+  if (!job || !job->ran) return jobFail(job, T1K_ERR_STATE, "the job has not run");
+  if (job->prm.bootstrap <= 0 || job->rank != 0) return jobFail(job, T1K_ERR_STATE, "the job keeps no bootstrap table");
+  const Genotyper::BootResult &b = job->boot;
+  if (nReplicates) *nReplicates = (uint32_t)b.B;
+  if (nAlleles) *nAlleles = (uint32_t)b.nAlleles;
+  if (abundance && !b.abundance.empty()) memcpy(abundance, b.abundance.data(), b.abundance.size() * 8);
+  if (rounds) memcpy(rounds, b.rounds.data(), b.rounds.size() * 4);
+  if (valid) memcpy(valid, b.valid.data(), b.valid.size());
+  return T1K_OK;
+}
+
+int t1k_job_em_alleles(t1k_job *job, int32_t *ec, int32_t *weight, int32_t *effLen, int32_t *series, uint32_t *nAlleles) {
+  if (!job) return T1K_ERR_ARG;
+  if (nAlleles) *nAlleles = (uint32_t)job->ref.al.size();
+  for (size_t a = 0; a < job->ref.al.size(); ++a) {
+    const AlleleMeta &m = job->ref.al[a];
+    if (ec) ec[a] = m.ec;
+    if (weight) weight[a] = m.weight;
+    if (effLen) effLen[a] = m.effLen;
+    if (series) series[a] = m.major;
+  }
+  return T1K_OK;
+}
+
+int t1k_job_series_names(t1k_job *job, char *buf, uint64_t cap, uint64_t *needed) {
+  if (!job) return T1K_ERR_ARG;
+  std::string s;
+  for (const std::string &m : job->ref.majorName) s += m + "\n";
   if (needed) *needed = s.size();
   if (buf && cap > s.size()) { memcpy(buf, s.data(), s.size()); buf[s.size()] = 0; }
   else if (buf) return T1K_ERR_ARG;

@@ -60,6 +60,8 @@ struct t1k_job {
   std::string assignText;           // --outputReadAssignment rows
   std::string altText;              // --alternatives: the table (on the rank that writes _genotype.tsv)
   std::string diploText;            // --diplotypes: the table (on the same rank)
+  Genotyper::BootResult boot;       // --bootstrap: the replicates' abundances and the table (on the same rank)
+  std::string bootText;
   t1k_stats stats{};
   uint64_t distinctReadEnds = 0, readEnds = 0;
   double msLoad = 0, msDevice = 0, msHost = 0, msEm = 0, msCoalesce = 0, msWrite = 0;

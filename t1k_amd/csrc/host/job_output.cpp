@@ -231,6 +231,7 @@ int t1k_job_write_outputs(t1k_job *job, const char *prefix) {
     if (job->prm.output_read_assignment && !writeText(pfx + "_assign.tsv", job->assignText, job->err)) return T1K_ERR_IO;
     if (job->prm.alternatives > 0 && !writeText(pfx + "_alternatives.tsv", job->altText, job->err)) return T1K_ERR_IO;
     if (job->prm.diplotypes > 0 && !writeText(pfx + "_diplotypes.tsv", job->diploText, job->err)) return T1K_ERR_IO;
+    if (job->prm.bootstrap > 0 && !writeText(pfx + "_bootstrap.tsv", job->bootText, job->err)) return T1K_ERR_IO;
   }
   if (job->bgStarted && job->outPrefix == pfx) {  // already under way since the end of the device loop
     if (job->bgWriter.joinable()) job->bgWriter.join();

@@ -226,6 +226,44 @@ struct Genotyper {
   };
   void diplotypeInput(int maxCand, DiploInput &in) const;
   std::string diplotypeText(const DiploInput &in, const uint64_t *matrix, int top) const;
+
+  // One EM run's place in the SQUAREM loop of QuantifyAlleleEquivalentClass (1234-1314) and its vectors: element e of a vector at
+  // p[e * stride] (quantify: stride 1; a replicate of the lockstep bootstrap: its column of the replicate-minor arrays).  A round is
+  // update x0 -> x1, update x1 -> x2, emExtrapolate (alpha, x3), update x3 -> x1, emCloseRound (x0 = x1, the forced extra round, the
+  // masking of every 10th round through `mask`, which rewrites x0 from n); the updates are the caller's.
+  struct EmRun {
+    double *x0 = nullptr, *x1 = nullptr, *x2 = nullptr, *x3 = nullptr, *n = nullptr;
+    size_t stride = 1;
+    int t = 0, rounds = 0;
+    bool done = false;
+  };
+  void emExtrapolate(EmRun &run) const;
+  void emCloseRound(EmRun &run, const std::function<void(EmRun &)> &mask) const;
+  // SetAlleleAbundance (957-1014) and the masking rule of quantify's loop into arrays of the caller's instead of RefSet::al: the same sums
+  // in the same order.  ecReadCount[e] at n[e * stride].
+  struct Abundances { std::vector<double> abundance, ecAbundance, major, geneMaxMajor; };
+  void abundanceInto(const double *n, size_t stride, Abundances &out) const;
+  void maskInto(EmRun &run) const;
+  std::vector<int> emEcLen;      // per class: the effective length quantify gave t1k_em_setup
+  std::vector<double> emCount;   // per read group: the count it gave
+  // --bootstrap (no counterpart in the reference): replicates 1 .. B of quantify's EM on Poisson-resampled group counts,
+  // replicate 0 on the counts themselves, over the structure quantify left on the context (so: after quantify, before dropUnlikely thins
+  // the classes).  Reads RefSet::al, writes nothing outside `out`.  T1K_BOOTSTRAP_SERIAL=1: one replicate after the other through
+  // t1k_em_set_count + t1k_em_update instead of t1k_boot_update for all of them; T1K_BOOTSTRAP_IDENTITY=1: every replicate is the data.
+  struct BootResult {
+    int B = 0;
+    size_t nAlleles = 0;
+    std::vector<double> abundance;   // [(B + 1)][nAlleles]
+    std::vector<int32_t> rounds;     // [B + 1]
+    std::vector<uint8_t> valid;      // [B + 1]
+    uint64_t updates = 0;            // update calls (lockstep: one for all active replicates)
+    double rowMs = 0, colMs = 0, kernelMs = 0, totalMs = 0;
+    bool serial = false;
+  };
+  int bootstrap(t1k_ctx *ctx, int B, uint64_t seed, BootResult &out, std::string &err) const;
+  // the major alleles field k of geneLine names, in its order (empty where it prints ".")
+  void calledSeries(int gene, std::vector<int> series[2]) const;
+  std::string bootstrapText(const BootResult &boot) const;   // <prefix>_bootstrap.tsv; after select()
 };
 
 // host/variants.cpp: novel-variant calling of the analyzer stage (VariantCaller.hpp), host code over the fragments' assignment lists and

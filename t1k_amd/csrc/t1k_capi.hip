@@ -305,6 +305,7 @@ static void freeBuf(T1kDevBuf &b) {
 void t1k_ctx_destroy(t1k_ctx *ctx) {
   if (ctx && ctx->emPinned) { (void)hipHostFree(ctx->emPinned); ctx->emPinned = nullptr; }
   if (ctx && ctx->countersPinned) { (void)hipHostFree(ctx->countersPinned); ctx->countersPinned = nullptr; }
+  if (ctx && ctx->boot.pinned) { (void)hipHostFree(ctx->boot.pinned); ctx->boot.pinned = nullptr; }
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);  // nothing of this context may be in flight when its blocks go back to the pool
@@ -313,7 +314,7 @@ void t1k_ctx_destroy(t1k_ctx *ctx) {
                       &ctx->bWgStage, &ctx->bWgBig, &ctx->bWgCache, &ctx->bLists, &ctx->bCand, &ctx->bExt, &ctx->bCandStart, &ctx->bCandCount, &ctx->bListPtr, &ctx->bListCount,
                       &ctx->bOvlWork, &ctx->bOvlUpload, &ctx->bDedupScratch, &ctx->bDedupBases, &ctx->bDedupN, &ctx->bDedupLen, &ctx->bDedupWeight, &ctx->bOvlStart, &ctx->bOvlCount, &ctx->bCounters, &ctx->bSlowQueue, &ctx->bSlowScratch, &ctx->bSortScratch, &ctx->bSelClass, &ctx->bEqTrace, &ctx->bSortTmp, &ctx->bJobSort, &ctx->bEnd1, &ctx->bEnd2,
                       &ctx->bHasN, &ctx->bRows, &ctx->bRowStart, &ctx->bRowCount, &ctx->bFragAssigned, &ctx->bPairScratch, &ctx->bPairOverflow, &ctx->bPairBig, &ctx->bExtractHuge, &ctx->bEmRowPtr, &ctx->bEmEc,
-                      &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bExtract, &ctx->bPileup, &ctx->bPileupIn};
+                      &ctx->bEmCount, &ctx->bEmLen, &ctx->bEmX0, &ctx->bEmN, &ctx->bEmPsum, &ctx->bEmColPtr, &ctx->bEmRowOf, &ctx->bBoot, &ctx->bExtract, &ctx->bPileup, &ctx->bPileupIn};
   for (auto *b : all) freeBuf(*b);
   for (T1kStage *s : {&ctx->sp, &ctx->sup, &ctx->ind, &ctx->ph}) t1k_stage_blocks(*s, [](const std::string &, T1kDevBuf &b) { freeBuf(b); });
   for (auto &slot : ctx->storeChunks)
@@ -335,7 +336,7 @@ uint64_t t1k_ctx_mem_report(t1k_ctx *ctx, const char *tag, int print) {
     B(bWgStage), B(bWgBig), B(bWgCache), B(bLists), B(bCand), B(bExt), B(bCandStart), B(bCandCount), B(bListPtr), B(bListCount), B(bOvlWork), B(bOvlUpload), B(bDedupScratch), B(bDedupBases), B(bDedupN),
     B(bDedupLen), B(bDedupWeight), B(bOvlStart), B(bOvlCount), B(bCounters), B(bSlowQueue), B(bSlowScratch), B(bSortScratch), B(bSelClass), B(bEqTrace), B(bSortTmp), B(bJobSort), B(bEnd1),
     B(bEnd2), B(bHasN), B(bRows), B(bRowStart), B(bRowCount), B(bFragAssigned), B(bPairScratch), B(bPairOverflow), B(bPairBig), B(bExtractHuge), B(bEmRowPtr), B(bEmEc), B(bEmCount),
-    B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bExtract), B(bPileup), B(bPileupIn)};
+    B(bEmLen), B(bEmX0), B(bEmN), B(bEmPsum), B(bEmColPtr), B(bEmRowOf), B(bBoot), B(bExtract), B(bPileup), B(bPileupIn)};
 #undef B
   uint64_t tot = 0, ref = 0, store = 0, align = 0;
   std::string line;

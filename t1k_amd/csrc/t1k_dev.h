@@ -943,6 +943,17 @@ inline void t1k_stage_blocks(T1kStage &s, F &&f) {
   for (T1kStageBuf &m : s.more) f(std::string(m.name), m.b);
 }
 
+// an open bootstrap of the EM (t1k_boot.hip; t1k_boot_begin .. _end): the pieces of its device block bBoot, all replicate-minor with stride
+// Rpad; which replicates have a count that is not 0; page-locked staging [x | n]; device ms of the row passes | of the class passes | updates
+struct T1kBoot {
+  bool open = false;
+  uint32_t nRep = 0, Rpad = 0;  // replicates 0 .. B, padded to whole blocks of 64
+  size_t oCount = 0, oPsum = 0, oK = 0, oX = 0, oN = 0, oNOf = 0, oActive = 0, oNonEmpty = 0;
+  std::vector<uint8_t> nonEmpty;
+  double *pinned = nullptr;
+  double ms[3] = {0, 0, 0};
+};
+
 // the working capacities of the batch arenas (their rules: kCapRules, t1k_capi.hip)
 enum { T1K_CAP_GROUP = 0, T1K_CAP_LIST, T1K_CAP_RARE, T1K_CAP_JOB, T1K_CAP_GENJOB, T1K_CAP_CAND, T1K_CAP_OVL, T1K_CAP_GENHIT, T1K_NCAP };
 
@@ -1010,6 +1021,9 @@ struct t1k_ctx {
   bool emReduceMode = false;   // T1K_EM_COLLECTIVE=allreduce: partial class totals per rank, all-reduce of E doubles (opt-in: re-associates the sums)
   uint64_t emNnz = 0;
   std::vector<int32_t> hEmLen;
+  // bootstrap of the EM over the structure above (t1k_boot.hip)
+  T1kDevBuf bBoot;
+  T1kBoot boot;
   int traceFetch = 0;          // T1K_DEBUG_TRACE
   // an upload in pieces (t1k_reads_upload_begin .. _end)
   uint32_t upN = 0; int upS = 0, upMaxLen = 0; uint64_t upBytes = 0; bool upOpen = false;
